@@ -1,15 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- training-step throughput of the MI355X hot path on synthetic Hyperkvasir-shaped batches.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cls|mae] [--precision bf16|fp32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cls|mae] [--precision bf16|fp32] [--full]
+                    [--dump-outputs DIR]
         (N > 1 without a launcher: this process starts the N ranks itself, one per GPU -- self_launch below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = zero_grad -> forward -> loss -> backward (-> RCCL gradient all-reduce) -> fused AdamW, inputs
 resident in HBM.  Headline workload = BASELINE.json configs[1]: ViT-B/16 classification
-fine-tune, bf16, bs=64/GPU, 224^2; BASELINE.json's metric names both halves ("MAE pretrain + cls finetune"), so
-the default run also measures configs[2] (MAE pre-train, mask 0.75, bs=256/GPU) in the same process and reports it
-as the `mae` sub-record.  Rank 0 prints ONE JSON line (contract in the task statement) carrying
+fine-tune, bf16, bs=64/GPU, 224^2.  A plain run measures the headline only: set-up, pre-heat + W warm-up steps, K timed
+steps, and rank 0 prints ONE JSON line (`metric`, `value`, `unit`, `ms_per_step`, `dtype`, the step-time spread and the
+roofline fraction the step time implies).  The pre-heat runs until the clocks have settled, so its step count varies; the
+training state is put back to the initial weights and optimizer state after it (then a fixed RESETTLE_STEPS steps), so
+that the steps from there on, warm-up and timed ones, are the same computation in every run.
+--dump-outputs DIR writes what the last timed step handed its caller (loss, logits or MAE pred / mask, seeded samples of the
+updated parameters and of their gradients) as float32 .npy files: two builds can be compared output for output.
+--full adds everything else the line used to carry: BASELINE.json's metric names both halves ("MAE pretrain + cls finetune"),
+so it also measures configs[2] (MAE pre-train, mask 0.75, bs=256/GPU) in the same process and reports it as the `mae`
+sub-record, beside the fp16 / fp32 / ViT-H / C5 sub-records, the host enqueue time, and
   `roofline`      achieved algorithmic TFLOP/s vs the 2.5 PFLOP/s dense bf16 MFMA peak, plus the dominant kernel's own
                   live-measured average duration (HIP events on the stream the kernel runs on),
   `parity`        the HIP path's logits / loss / gradient errors against the CPU oracle on the benched configuration,
@@ -96,6 +104,12 @@ def parse():
     ap.add_argument("--no-c5", action="store_true", help="skip the `finetune_modes` sub-records (none / head+1 / head+2 + eval)")
     ap.add_argument("--graph", choices=["auto", "on", "off"], default="auto",
                     help="replay the step as one hipGraph (auto = off: eager launch keeps up and overlaps the two streams better)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: sub-records (fp16, fp32, MAE, ViT-H, C5), per-kernel statistics, host "
+                         "enqueue time, oracle parity + gates, CPU and PyTorch baselines (the --no-* options trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (float32 .npy, seeded samples of the large "
+                         "arrays, < 64 MB in all) to DIR")
     return ap.parse_args()
 
 
@@ -211,12 +225,15 @@ def make_step(workload, ddp, opt, imgs, labels, lr_every_step=False, noise_buf=N
             opt.step()
         return loss
 
+    outputs = {}  # the forward's results of the latest step (detached views, no copy): --dump-outputs
+
     if workload == "cls":
         def step(im=None, lb=None):
             im, lb = pick(im, lb)
             touch_lr()
             opt.zero_grad(set_to_none=True)
             logits = ddp(im)
+            outputs["logits"] = logits.detach()
             return finish(A.supervised_loss(logits, lb, pos_weight=pos_weight))  # tc.py:3347-3374, 6090-6102 (one HIP launch)
     else:
         def step(im=None, lb=None):
@@ -225,7 +242,15 @@ def make_step(workload, ddp, opt, imgs, labels, lr_every_step=False, noise_buf=N
             opt.zero_grad(set_to_none=True)
             # noise_buf: hipGraph replay -- the masking noise must come from a buffer the caller refills between replays (a draw
             # inside the captured region would be baked into the graph)
-            return finish(ddp(im, mask_ratio=0.75, **({"noise": noise_buf} if noise_buf is not None else {}))[0])
+            loss, pred, mask = ddp(im, mask_ratio=0.75, **({"noise": noise_buf} if noise_buf is not None else {}))
+            outputs.update(pred=pred.detach(), mask=mask.detach())
+            return finish(loss)
+
+    def rewind():
+        """Back to the first step's batch pairing and learning-rate schedule position."""
+        counter[0] = tick[0] = 0
+
+    step.outputs, step.rewind = outputs, rewind
     return step
 
 
@@ -746,6 +771,67 @@ def dist_config(world, rank, local, device_name, sync_info, backend):
     return out
 
 
+def restore_initial_state(model, opt, init_state, rng_offset, device):
+    """Undo the training the pre-heat did (its step count depends on how fast the clocks settle): the initial weights, zero AdamW
+    moments and step counters, the initial loss scale, the device generator's offset the MAE masking noise is drawn from.
+    Everything in place, so that a captured hipGraph still reads the right buffers."""
+    model._rt.wait_updates()
+    torch.cuda.synchronize()
+    model.load_state_dict(init_state)
+    for r in opt._M:
+        opt._M[r].zero_()
+        opt._V[r].zero_()
+    for g in opt.param_groups:
+        g.pop("step", None)
+    if getattr(opt, "_hyper", None) is not None:  # device records: step counter, bias corrections, scaler flags
+        opt._hyper.zero_()
+        opt._hyper_host = None  # lr / betas / eps / wd / grad_scale are pushed again at the next step
+    scaler = getattr(opt, "loss_scaler", None)
+    if scaler is not None and scaler._state is not None:
+        scaler._state.zero_()
+        scaler._state[0] = scaler.init_scale
+    torch.cuda.default_generators[device.index].set_offset(rng_offset)
+    model._rt.ensure(device)  # re-cast the bf16 shadow of the restored weights (a graph replay would not)
+    torch.cuda.synchronize()
+
+
+RESETTLE_STEPS = 20    # untimed steps between restore_initial_state() and the W warm-up steps
+DUMP_SAMPLE = 1 << 21  # elements per seeded sample of a large output (8 MB in float32)
+
+
+def _sample(t, seed):
+    """All of `t` if it is small, else a fixed, seeded, sorted sample of its flattened elements."""
+    t = t.detach()
+    if t.numel() <= DUMP_SAMPLE:
+        return t.float().cpu().numpy()
+    idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort().values
+    return t.reshape(-1)[idx.to(t.device)].float().cpu().numpy()
+
+
+def collect_outputs(model, step, losses):
+    """What the last timed step handed its caller: its loss (and the K losses before it), the forward's results, the updated
+    parameters and their gradients (both flattened in named_parameters() order and sampled).  float32, < 64 MB in all."""
+    model._rt.wait_updates()
+    torch.cuda.synchronize()
+    out = {"losses": torch.stack(losses).float().reshape(-1).cpu().numpy()}
+    out["loss"] = out["losses"][-1:].copy()
+    for i, (name, t) in enumerate(sorted(step.outputs.items())):
+        out[name] = _sample(t, 100 + i)
+    params = [p for _, p in model.named_parameters()]
+    out["param_sample"] = _sample(torch.cat([p.detach().float().reshape(-1) for p in params]), 1)
+    grads = [p.grad for p in params if p.grad is not None]
+    if grads:
+        out["grad_sample"] = _sample(torch.cat([g.float().reshape(-1) for g in grads]), 2)
+    return out
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 def run_workload(args, workload, batch, device, world, rank, headline, finetune_mode="full", light=False, precision=None,
                  kstats=True, eval_forward=None, factory=None):
@@ -763,6 +849,9 @@ def run_workload(args, workload, batch, device, world, rank, headline, finetune_
     imgs, labels = make_batch(workload, batch, device, rank, pool=not args.single_batch)
     pooled = isinstance(imgs, list)
     imgs0, labels0 = (imgs[0], labels[0]) if pooled else (imgs, labels)   # the batch of the parity block / the eval forward
+    # the state the first step starts from (the parity block compares there; the pre-heat's training is undone to it)
+    init_state = {k: v.detach().clone() for k, v in model.state_dict().items()}
+    rng_offset = torch.cuda.default_generators[device.index].get_offset()
     use_graph = args.graph == "on"  # auto: eager (measured faster: graph replay serialises the wgrad side stream)
     if use_graph:
         # a captured step reads fixed addresses: ONE static batch / label / noise buffer, refilled from the resident pool before every
@@ -804,10 +893,9 @@ def run_workload(args, workload, batch, device, world, rank, headline, finetune_
     # the outputs and gradients collapse towards zero and relative errors stop meaning anything), but runs AFTER the timed
     # region on a restored copy of them: its ~10 s of CPU oracle leave the GPU idle, and a timed loop that starts right
     # after an idle phase measures the clock ramp (first steps up to 1.5x slower) instead of the steady state.
-    want_parity = rank == 0 and world == 1 and not args.no_parity
-    if light or not kstats:
+    want_parity = rank == 0 and world == 1 and not args.no_parity and args.full
+    if light or not kstats or not args.full:
         args = argparse.Namespace(**{**vars(args), "no_kernel_stats": True})
-    init_state = {k: v.detach().clone() for k, v in model.state_dict().items()} if want_parity else None
     # Pre-heat: untimed steps of the same step function until args.preheat seconds have passed, so that clocks and power
     # management have settled before the W warm-up steps (a process that starts timing ~0.15 s after its first launch is
     # still on the ramp: scratch/host_time.py shows 16 ms steps for the first ~15 steps, 10.8 ms afterwards).
@@ -826,6 +914,15 @@ def run_workload(args, workload, batch, device, world, rank, headline, finetune_
                 el = t.item()
             if el >= args.preheat:
                 break
+        restore_initial_state(model, opt, init_state, rng_offset, device)
+        eager_step.rewind()
+        if use_graph:
+            tick[0] = 0
+        # a fixed number of steps from the restored state: the step rate needs them to settle again after the restore's pause
+        # (with the W warm-up steps alone right behind it, the timed steps ran 0.35 % slower)
+        for _ in range(RESETTLE_STEPS):
+            step()
+        preheat_steps += RESETTLE_STEPS
     if host_input:
         if use_graph:
             sys.exit("--input host feeds a new batch every step: use eager launch")
@@ -837,8 +934,8 @@ def run_workload(args, workload, batch, device, world, rank, headline, finetune_
     torch.cuda.synchronize()
     # host cost of enqueueing a step, measured on an empty queue (inside the timed loop the host runs ahead until the
     # HIP queue is full and is then throttled to the device's pace, so the loop's own enqueue time says nothing)
-    t_enq = float("nan")
-    if not host_input:
+    t_enq = float("nan") if args.full else None  # (--full: the host's enqueue time of one step)
+    if not host_input and args.full:
         t_h = time.perf_counter()
         for _ in range(3):
             step()
@@ -876,6 +973,8 @@ def run_workload(args, workload, batch, device, world, rank, headline, finetune_
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
+    if headline and rank == 0 and args.dump_outputs:  # before anything else runs a step on this model
+        write_outputs(args.dump_outputs, collect_outputs(model, eager_step, losses))
     busy = None
     if args.host_busy > 0 and headline and not host_input:
         # N spinners pinned to nothing in particular: the scheduler shares the granted cores between them and this process
@@ -920,7 +1019,7 @@ def run_workload(args, workload, batch, device, world, rank, headline, finetune_
         c = scaler.counters()
         scale_info = {"loss_scale": scaler.get_scale(), "skipped_steps_in_timed_region": c["skipped"] - skipped0,
                       "skipped_steps_total": c["skipped"], "optimizer_steps_total": c["steps"]}
-    sync_info = measure_sync(ddp, eager_step, device) if ddp.sync is not None else None
+    sync_info = measure_sync(ddp, eager_step, device) if ddp.sync is not None and args.full else None
     rec = None
     stats = None
     parity = None
@@ -999,7 +1098,8 @@ def run_workload(args, workload, batch, device, world, rank, headline, finetune_
             roof["hbm_kernels"] = hb        # in-step (beside the weight-gradient stream), algorithmic bytes / time
             roof["gemm_share_of_step"] = round(gt / (dt / args.steps), 3)
         rec = {"value": round(ips, 2), "unit": "images/sec", "ms_per_step": round(dt / args.steps * 1e3, 3),
-               "host_enqueue_ms_per_step": round(t_enq * 1e3, 3), "step_ms": step_ms, "preheat_steps": preheat_steps,
+               "host_enqueue_ms_per_step": round(t_enq * 1e3, 3) if t_enq is not None else None, "step_ms": step_ms,
+               "preheat_steps": preheat_steps,
                "timed_region_unix": [round(t0_unix, 3), round(t1_unix, 3)],  # (for scratch/telemetry.py traces)
                "config": {"workload": WORKLOAD_NAME[workload] + f", bs={batch}/GPU, 224^2, AdamW, random init"
                                       + (f", finetune mode {finetune_mode} (finetune.py:49-91)" if workload == "cls" else ""),
@@ -1219,7 +1319,8 @@ def main():
         dist.init_process_group("nccl", init_method=f"tcp://127.0.0.1:{port}", rank=0, world_size=1, device_id=device)
     batch = args.batch or (64 if args.workload == "cls" else 256)
     head = run_workload(args, args.workload, batch, device, world, rank, True, finetune_mode=args.finetune_mode)
-    default_line = args.workload == "cls" and not args.batch and args.input == "resident" and args.precision == "bf16"
+    # --full: the sub-records beside the headline (a plain run is the headline alone)
+    default_line = args.full and args.workload == "cls" and not args.batch and args.input == "resident" and args.precision == "bf16"
     subs = {}
     if default_line and not args.no_fp16:
         # the same fine-tune step in precision mode fp16: the 16-bit mode whose parity gate is SURVEY 8-d as written
@@ -1335,9 +1436,9 @@ def main():
         if c5 is not None:
             out["finetune_modes"] = {m: {k: v for k, v in r.items() if k not in ("host_enqueue_ms_per_step", "preheat_steps")}
                                      for m, r in c5.items()}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_full)
-        if world == 1 and not args.no_torch_baseline and args.precision == "bf16":
+        if world == 1 and args.full and not args.no_torch_baseline and args.precision == "bf16":
             try:
                 out["torch_baseline"] = torch_baseline(device, 64)
             except Exception as e:  # context only: never fail the bench line over it

@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: bash scratch/ab.sh <outdir> "<name>:<ENV=.. ENV=..>" ...   -- bench.py (cls + mae sub-record) per variant, one line each
 O=$1; shift; mkdir -p $O
-B="--no-cpu-baseline --no-torch-baseline --no-parity --no-kernel-stats"
+B="--full --no-cpu-baseline --no-torch-baseline --no-parity --no-kernel-stats"
 for spec in "$@"; do
   name=${spec%%:*}; envs=${spec#*:}
   env $envs python bench.py $B > $O/bench_$name.json 2> $O/bench_$name.err

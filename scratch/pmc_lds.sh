@@ -4,7 +4,7 @@
 TAG=$1; shift
 REPO=$PWD; OUT=$REPO/gpurun_out/pmc_lds_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_LDS_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL SQ_WAIT_INST_LDS SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $OUT -o l --output-format csv -- python3 $REPO/bench.py --steps 3 --warmup 2 --preheat 0 --no-cpu-baseline --no-kernel-stats --no-parity --no-torch-baseline --no-mae "$@" > $OUT/run.log 2>&1
+rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_LDS_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL SQ_WAIT_INST_LDS SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE --kernel-trace -d $OUT -o l --output-format csv -- python3 $REPO/bench.py --full --steps 3 --warmup 2 --preheat 0 --no-cpu-baseline --no-kernel-stats --no-parity --no-torch-baseline --no-mae "$@" > $OUT/run.log 2>&1
 cd $REPO && python3 - $OUT/l_counter_collection.csv > $OUT/summary.txt <<'PY'
 import csv, sys, collections
 agg = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.Counter()

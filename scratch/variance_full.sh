@@ -2,7 +2,7 @@
 # usage: bash scratch/variance_full.sh <outdir> [n]  -- the default bench line (minus the CPU / torch baselines) n times in a row
 O=$1; N=${2:-5}; mkdir -p $O
 for i in $(seq 1 $N); do
-  python bench.py --no-cpu-baseline --no-torch-baseline > $O/full_$i.json 2> $O/full_$i.err
+  python bench.py --full --no-cpu-baseline --no-torch-baseline > $O/full_$i.json 2> $O/full_$i.err
 done
 python - $O <<'PY'
 import json, sys, glob

@@ -9,7 +9,11 @@ N / (n_class * count) (tc.py:5613-5630), pos_weight = neg / pos for the two-clas
 schedule settings (config/base.yaml), and -- with torch, as the reference does (nn.BCEWithLogitsLoss(pos_weight)) -- the loss
 of a fixed logit vector on 8 training labels (every 577th row).  Only data is stored: counts, labels, numbers.
 
-    PYTHONPATH=/root/reference/src python tests/golden/make_c1_fixture.py
+What the loaders returned is stored beside the fixture as well (tests/golden/c1_sun_full_inputs.npz: every row's label and
+frame path per split, the resolved config as JSON), so that the derivation can be replayed without the reference checkout
+(tests/test_c1_plumbing_cpu.py).
+
+    SSL4POLYP_REFERENCE=<reference checkout> python tests/golden/make_c1_fixture.py
 """
 import json
 import os
@@ -19,32 +23,55 @@ from pathlib import Path
 import numpy as np
 import torch
 
-REF = Path(os.environ.get("SSL4POLYP_REFERENCE", "/root/reference"))
-sys.path.insert(0, str(REF / "src"))
+SPLITS = ("train", "val", "test")
+CONFIG_KEYS = ("optimizer", "lr", "weight_decay", "batch_size", "epochs", "amp", "image_size")
+INPUTS = Path(__file__).with_name("c1_sun_full_inputs.npz")
 
 
-def build():
+def read_reference(ref):
+    """What the reference's loaders return for the sun_full pack and exp1.yaml: {split: (labels, frame paths)}, config."""
+    sys.path.insert(0, str(Path(ref) / "src"))
     from ssl4polyp.configs import layered as L
     from ssl4polyp.configs import manifests as M
-    pack = REF / "data_packs" / "sun_full"
-    out = {"pack": "sun_full", "splits": {}}
-    labels = {}
-    for split in ("train", "val", "test"):
+    pack = Path(ref) / "data_packs" / "sun_full"
+    splits = {}
+    for split in SPLITS:
         rows = M.load_split(pack / f"{split}.csv")
-        lab = [int(r["label"]) for r in rows]
-        labels[split] = lab
+        splits[split] = ([int(r["label"]) for r in rows], [r["frame_path"] for r in rows])
+    cfg = L.load_layered_config("exp/exp1.yaml")
+    config = {k: cfg[k] for k in CONFIG_KEYS}
+    config["scheduler"] = dict(cfg["scheduler"])
+    config["seeds"] = list(cfg["seeds"])
+    return splits, config
+
+
+def save_inputs(splits, config, path=INPUTS):
+    arrays = {"config_json": np.array(json.dumps(config, sort_keys=True))}
+    for split, (labels, frames) in splits.items():
+        arrays[f"{split}_labels"] = np.asarray(labels, dtype=np.int8)
+        arrays[f"{split}_frame_paths"] = np.asarray(frames, dtype=np.str_)
+    np.savez_compressed(path, **arrays)
+
+
+def load_inputs(arrays):
+    """The inverse of save_inputs, from the npz's arrays."""
+    splits = {s: ([int(v) for v in arrays[f"{s}_labels"]], [str(v) for v in arrays[f"{s}_frame_paths"]]) for s in SPLITS}
+    return splits, json.loads(str(arrays["config_json"]))
+
+
+def derive(splits, config):
+    out = {"pack": "sun_full", "splits": {}}
+    for split in SPLITS:
+        lab, frames = splits[split]
         counts = np.bincount(lab, minlength=2).tolist()
-        out["splits"][split] = {"rows": len(rows), "class_counts": counts, "first_frame": rows[0]["frame_path"]}
-    train = labels["train"]
+        out["splits"][split] = {"rows": len(lab), "class_counts": counts, "first_frame": frames[0]}
+    train = splits["train"][0]
     counts = np.bincount(train, minlength=2)
     n_class = len(set(train))
     out["n_class"] = n_class
     out["class_weights"] = [float(len(train) / (n_class * c)) for c in counts]   # tc.py:5621-5624
     out["pos_weight"] = float(counts[0]) / float(counts[1])                      # tc.py:6092-6096
-    cfg = L.load_layered_config("exp/exp1.yaml")
-    out["config"] = {k: cfg[k] for k in ("optimizer", "lr", "weight_decay", "batch_size", "epochs", "amp", "image_size")}
-    out["config"]["scheduler"] = dict(cfg["scheduler"])
-    out["config"]["seeds"] = list(cfg["seeds"])
+    out["config"] = dict(config)
     # C1: per-rank batch 8, fp32.  First 8 training labels + a fixed logit vector through the reference's loss construction.
     first8 = train[:: len(train) // 8][:8]  # (the CSV is ordered by case: a strided sample carries both classes)
     rng = np.random.Generator(np.random.PCG64(77))
@@ -56,7 +83,13 @@ def build():
     return out
 
 
+def build(ref=None):
+    return derive(*read_reference(ref or os.environ["SSL4POLYP_REFERENCE"]))
+
+
 if __name__ == "__main__":
+    splits, config = read_reference(os.environ["SSL4POLYP_REFERENCE"])
+    save_inputs(splits, config)
     dst = Path(__file__).with_name("c1_sun_full.json")
-    dst.write_text(json.dumps(build(), indent=1, sort_keys=True) + "\n")
-    print("wrote", dst)
+    dst.write_text(json.dumps(derive(splits, config), indent=1, sort_keys=True) + "\n")
+    print("wrote", dst, "and", INPUTS)

@@ -68,3 +68,21 @@ def test_world_size_mismatch_is_refused():
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "4"], env=env, capture_output=True, text=True,
                        timeout=120)
     assert p.returncode != 0 and "WORLD_SIZE=2" in p.stderr
+
+
+def test_output_dump_samples_are_fixed_and_float32(tmp_path):
+    """--dump-outputs: a large output is reduced to the same seeded sample in every run, a small one is kept whole, and every file
+    is float32 (two builds' dumps are compared element for element)."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, REPO)
+    import bench
+    big = torch.arange(bench.DUMP_SAMPLE + 12345, dtype=torch.float64)
+    a, b = bench._sample(big, 1), bench._sample(big, 1)
+    assert a.shape == (bench.DUMP_SAMPLE,) and np.array_equal(a, b) and np.all(np.diff(a) >= 0)
+    assert not np.array_equal(a, bench._sample(big, 2))
+    small = torch.randn(64, 2, dtype=torch.bfloat16)
+    np.testing.assert_array_equal(bench._sample(small, 1), small.float().numpy())
+    bench.write_outputs(str(tmp_path / "dump"), {"logits": bench._sample(small, 1), "losses": np.arange(3, dtype=np.float64)})
+    for name in ("logits", "losses"):
+        assert np.load(tmp_path / "dump" / f"{name}.npy").dtype == np.float32
