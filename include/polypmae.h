@@ -263,6 +263,13 @@ int pm_aug_resize_u8(const unsigned char* src, unsigned char* tmp, unsigned char
 size_t pm_aug_resized_crop_workspace_bytes(int B, int Hs, int Ws, int out);
 int pm_aug_resized_crop_u8(const unsigned char* src, const int* box, unsigned char* dst, int bicubic, int B, int Hs, int Ws, int out,
                            void* workspace, size_t ws_bytes, void* stream);
+/* The same over a packed ragged batch (frames of different decoded sizes, as an image folder holds them): frame b is HWC uint8 of
+ * hw[b] = (H_b, W_b) (i32 [B][2]) starting at byte offset[b] (i64 [B]) of src; box[b] lies inside frame b; H_b <= Hmax, W_b <= Wmax.
+ * dst [B][out][out][3].  Same arithmetic and the same kernels as pm_aug_resized_crop_u8 (which is this call with uniform frames);
+ * workspace: pm_aug_resized_crop_workspace_bytes(B, Hmax, Wmax, out) bytes, 16-byte aligned.  The tables are device memory and are
+ * not validated here (the caller checks them before the upload).  B <= 65535. */
+int pm_aug_resized_crop_ragged_u8(const unsigned char* src, const long long* offset, const int* hw, const int* box, unsigned char* dst,
+                                  int bicubic, int B, int Hmax, int Wmax, int out, void* workspace, size_t ws_bytes, void* stream);
 
 /* ColorJitter: per sample, ops in `order` (0 brightness, 1 contrast, 2 saturation, 3 hue; -1 = none): ImageEnhance blends (float32,
  * truncating / clipping as Blend.c), contrast against int(mean luminance + 0.5) of the image as it stands before that op, hue as

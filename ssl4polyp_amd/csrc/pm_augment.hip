@@ -106,28 +106,44 @@ __global__ __launch_bounds__(256) void resample_coeffs_kernel(const int* __restr
   bounds[2 * id + 1] = xmax;
 }
 
-// one pass of the cropped resize with per-sample tables: horizontal (rows top .. top + h of src -> tmp rows 0 .. h) or vertical
-// (tmp rows -> dst)
+// one pass of the cropped resize with per-sample tables, sample b = blockIdx.y (its box, base and row stride are wave-uniform):
+//   horizontal: crop rows top .. top + h of frame b -> tmp [B][Hs][out] rows 0 .. h.  Frame b starts at byte offset[b] and has rows
+//               of hw[b][1] pixels -- a packed ragged batch; offset == nullptr: the uniform batch [B][Hs][Ws] (offset b Hs Ws 3,
+//               rows of Ws pixels)
+//   vertical:   tmp [B][Hs][out] -> dst [B][out][out]
+// blockIdx.x strides over the sample's h x out (horizontal) or out x out (vertical) outputs; blocks past a short crop do nothing.
 __global__ __launch_bounds__(256) void resample_crop_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
                                                             const int* __restrict__ box, const int* __restrict__ bounds,
-                                                            const int* __restrict__ taps, int ksize, int B, int Hs, int Ws,
-                                                            int Hd, int Wd, int out_size, int vertical) {
-  // horizontal: src [B][Hs][Ws], dst = tmp [B][Hd = Hs][Wd = out]; vertical: src = tmp [B][Hs][Ws = out], dst [B][Hd = out][Wd = out]
-  const long total = (long)B * Hd * Wd;
+                                                            const int* __restrict__ taps, int ksize,
+                                                            const long long* __restrict__ offset, const int* __restrict__ hw,
+                                                            int Hs, int Ws, int out_size, int vertical) {
+  const int b = blockIdx.y;
+  const unsigned char* img;
+  long stride;  // bytes per source row
+  int rows;
+  if (vertical) {
+    img = src + (long)b * Hs * out_size * 3;
+    stride = (long)out_size * 3;
+    rows = out_size;
+  } else {
+    const int top = box[4 * b], left = box[4 * b + 1];
+    const long base = offset ? offset[b] : (long)b * Hs * Ws * 3;
+    stride = (long)(offset ? hw[2 * b + 1] : Ws) * 3;
+    img = src + base + top * stride + (long)left * 3;
+    rows = box[4 * b + 2];  // rows below the crop are never read
+  }
+  unsigned char* out = dst + (long)b * (vertical ? out_size : Hs) * out_size * 3;
+  const long total = (long)rows * out_size;
   for (long id = (long)blockIdx.x * 256 + threadIdx.x; id < total; id += (long)gridDim.x * 256) {
-    const int xo = id % Wd;
-    const int yo = (id / Wd) % Hd;
-    const int b = id / ((long)Wd * Hd);
-    const int top = box[4 * b], left = box[4 * b + 1], h = box[4 * b + 2];
-    if (!vertical && yo >= h) continue;  // rows below the crop are never read
+    const int xo = id % out_size;
+    const int yo = id / out_size;
     const int o = vertical ? yo : xo;
     const long ti = (long)b * out_size + o;
     const int lo = bounds[2 * ti], n = bounds[2 * ti + 1];
     const int* k = taps + ti * ksize;
     int ss0 = 1 << (kPrecisionBits - 1), ss1 = ss0, ss2 = ss0;
-    const unsigned char* p = vertical ? src + (((long)b * Hs + lo) * Ws + xo) * 3
-                                      : src + (((long)b * Hs + top + yo) * Ws + left + lo) * 3;
-    const long step = vertical ? (long)Ws * 3 : 3;
+    const unsigned char* p = vertical ? img + lo * stride + xo * 3 : img + yo * stride + lo * 3;
+    const long step = vertical ? stride : 3;
     for (int t = 0; t < n; ++t) {
       const int kk = k[t];
       ss0 += p[0] * kk;
@@ -135,7 +151,7 @@ __global__ __launch_bounds__(256) void resample_crop_kernel(const unsigned char*
       ss2 += p[2] * kk;
       p += step;
     }
-    unsigned char* q = dst + (((long)b * Hd + yo) * Wd + xo) * 3;
+    unsigned char* q = out + id * 3;
     ss0 >>= kPrecisionBits; ss1 >>= kPrecisionBits; ss2 >>= kPrecisionBits;
     q[0] = (unsigned char)(ss0 < 0 ? 0 : (ss0 > 255 ? 255 : ss0));
     q[1] = (unsigned char)(ss1 < 0 ? 0 : (ss1 > 255 ? 255 : ss1));
@@ -632,10 +648,12 @@ extern "C" size_t pm_aug_resized_crop_workspace_bytes(int B, int Hs, int Ws, int
   return tables + (size_t)B * Hs * out * 3 + 256;
 }
 
-extern "C" int pm_aug_resized_crop_u8(const unsigned char* src, const int* box, unsigned char* dst, int bicubic, int B, int Hs, int Ws,
-                                      int out, void* workspace, size_t ws_bytes, void* stream) {
+// both resized-crop entries: offset == nullptr -> uniform frames [B][Hs][Ws]; otherwise packed frames no larger than Hs x Ws
+static int resized_crop_launch(const unsigned char* src, const long long* offset, const int* hw, const int* box, unsigned char* dst,
+                               int bicubic, int B, int Hs, int Ws, int out, void* workspace, size_t ws_bytes, void* stream) {
   if (!src || !box || !dst || !workspace) return PM_EINVAL;
   if (B <= 0 || Hs <= 0 || Ws <= 0 || out <= 0) return PM_ESHAPE;
+  if (B > 65535) return PM_ESHAPE;  // (the sample is blockIdx.y)
   if (ws_bytes < pm_aug_resized_crop_workspace_bytes(B, Hs, Ws, out) || ((uintptr_t)workspace & 15)) return PM_EINVAL;
   const int big = Hs > Ws ? Hs : Ws;
   const int ksize = (int)((2.0 * big) / out + 1.0) * 2 + 3;
@@ -648,11 +666,25 @@ extern "C" int pm_aug_resized_crop_u8(const unsigned char* src, const int* box, 
   const int gc = (B * out + 255) / 256;
   hipLaunchKernelGGL(resample_coeffs_kernel, dim3(gc), dim3(256), 0, s, box, 0, out, bicubic ? 1 : 0, ksize, bounds_x, taps_x, B);
   hipLaunchKernelGGL(resample_coeffs_kernel, dim3(gc), dim3(256), 0, s, box, 1, out, bicubic ? 1 : 0, ksize, bounds_y, taps_y, B);
-  hipLaunchKernelGGL(resample_crop_kernel, dim3(aug_grid((long)B * Hs * out)), dim3(256), 0, s, src, tmp, box, bounds_x, taps_x, ksize,
-                     B, Hs, Ws, Hs, out, out, 0);
-  hipLaunchKernelGGL(resample_crop_kernel, dim3(aug_grid((long)B * out * out)), dim3(256), 0, s, tmp, dst, box, bounds_y, taps_y, ksize,
-                     B, Hs, out, out, out, out, 1);
+  // the whole grid is capped as aug_grid caps a flat one: at most 8192 blocks over the B samples
+  const int cap = 8192 / B > 1 ? 8192 / B : 1;
+  hipLaunchKernelGGL(resample_crop_kernel, dim3(aug_grid((long)Hs * out, cap), B), dim3(256), 0, s, src, tmp, box, bounds_x, taps_x,
+                     ksize, offset, hw, Hs, Ws, out, 0);
+  hipLaunchKernelGGL(resample_crop_kernel, dim3(aug_grid((long)out * out, cap), B), dim3(256), 0, s, tmp, dst, box, bounds_y, taps_y,
+                     ksize, nullptr, nullptr, Hs, out, out, 1);
   return pm_check_launch();
+}
+
+extern "C" int pm_aug_resized_crop_u8(const unsigned char* src, const int* box, unsigned char* dst, int bicubic, int B, int Hs, int Ws,
+                                      int out, void* workspace, size_t ws_bytes, void* stream) {
+  return resized_crop_launch(src, nullptr, nullptr, box, dst, bicubic, B, Hs, Ws, out, workspace, ws_bytes, stream);
+}
+
+extern "C" int pm_aug_resized_crop_ragged_u8(const unsigned char* src, const long long* offset, const int* hw, const int* box,
+                                             unsigned char* dst, int bicubic, int B, int Hmax, int Wmax, int out, void* workspace,
+                                             size_t ws_bytes, void* stream) {
+  if (!offset || !hw) return PM_EINVAL;
+  return resized_crop_launch(src, offset, hw, box, dst, bicubic, B, Hmax, Wmax, out, workspace, ws_bytes, stream);
 }
 
 extern "C" int pm_aug_color_jitter_u8(const unsigned char* src, unsigned char* dst, const pm_aug_jitter* jitter,

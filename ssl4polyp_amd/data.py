@@ -7,7 +7,10 @@ previous step computes (a uint8 batch is a quarter of the float32 bytes on PCIe)
 stages on the device in one HBM-bound kernel (`pm_preprocess_u8`): optional horizontal / vertical flip, ToTensor,
 Normalize -- bit-exact with torchvision's float32 arithmetic.  `DeviceAugmenter` (round 3) moves the rest of the train transform
 there as well -- Resize, ColorJitter, GaussianBlur((25, 25)), flips, RandomRotation(180) -- with Pillow's own integer / float
-arithmetic (`pm_aug_*`, csrc/pm_augment.hip), so the workers are left with JPEG decoding only.
+arithmetic (`pm_aug_*`, csrc/pm_augment.hip), so the workers are left with JPEG decoding only.  A batch of frames of different
+decoded sizes (an image folder) travels as one `RaggedFrames` -- the frames packed back to back plus an offset and a size table --
+and its first device stage (the Resize, or the MAE transform's RandomResizedCrop) is a per-sample resized crop that reads each
+frame where it lies (`pm_aug_resized_crop_ragged_u8`); the folder dataset and its loader are in folder.py.
 """
 from __future__ import annotations
 
@@ -126,19 +129,102 @@ def draw_train_params(B: int, generator: Optional[torch.Generator] = None, brigh
             "angle": u(-degrees, degrees).numpy()}
 
 
-def draw_rrc_boxes(B: int, height: int, width: int, generator: Optional[torch.Generator] = None, scale=(0.2, 1.0),
+class RaggedFrames:
+    """A batch of decoded HWC uint8 frames of different sizes, packed back to back: `data` uint8 [total], frame b is the
+    hw[b] = (H_b, W_b) image starting at byte offset[b] (`offset` int64 [B], `hw` int32 [B, 2], on the device of `data`).  A host
+    copy of the two tables travels with the object, so callers on the device side (box draws, validation, workspace sizes) never
+    read them back.  Build one with `from_frames`; `ragged_collate` does so in DataLoader workers."""
+
+    def __init__(self, data: torch.Tensor, offset: torch.Tensor, hw: torch.Tensor, _host=None):
+        import numpy as np
+        if data.dtype != torch.uint8 or data.ndim != 1 or not data.is_contiguous():
+            raise ValueError("RaggedFrames.data must be a contiguous 1-D uint8 tensor")
+        if offset.dtype != torch.int64 or hw.dtype != torch.int32 or offset.ndim != 1 or tuple(hw.shape) != (offset.numel(), 2) \
+                or offset.device != data.device or hw.device != data.device or not offset.is_contiguous() or not hw.is_contiguous():
+            raise ValueError("RaggedFrames needs offset int64 [B] and hw int32 [B, 2] on the device of the data")
+        if _host is None:
+            _host = (offset.cpu().numpy().astype(np.int64), hw.cpu().numpy().astype(np.int64))
+        off_h, hw_h = _host
+        if len(off_h) == 0 or (hw_h <= 0).any() or (off_h < 0).any() or \
+                (off_h + hw_h[:, 0] * hw_h[:, 1] * 3 > data.numel()).any():
+            raise ValueError("RaggedFrames: every frame must be non-empty and lie inside the packed data")
+        self.data, self.offset, self.hw, self._host = data, offset, hw, (off_h, hw_h)
+
+    @classmethod
+    def from_frames(cls, frames) -> "RaggedFrames":
+        """frames: a sequence of HWC uint8 arrays or tensors [H_b, W_b, 3] -> one packed host batch (one copy of the pixels)."""
+        import numpy as np
+        arrs = [f.numpy() if torch.is_tensor(f) else np.asarray(f) for f in frames]
+        if not arrs or any(a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 for a in arrs):
+            raise ValueError("RaggedFrames.from_frames takes a non-empty sequence of uint8 [H, W, 3] frames")
+        hw = np.array([a.shape[:2] for a in arrs], dtype=np.int64)
+        nbytes = hw[:, 0] * hw[:, 1] * 3
+        offset = np.concatenate([[0], np.cumsum(nbytes)[:-1]]).astype(np.int64)
+        data = torch.from_numpy(np.concatenate([a.reshape(-1) for a in arrs]))
+        return cls(data, torch.from_numpy(offset.copy()), torch.from_numpy(hw.astype(np.int32)), _host=(offset, hw))
+
+    def __len__(self) -> int:
+        return len(self._host[0])
+
+    @property
+    def sizes(self):
+        """numpy int64 [B, 2] = (H_b, W_b), host side."""
+        return self._host[1]
+
+    @property
+    def offsets(self):
+        """numpy int64 [B], host side."""
+        return self._host[0]
+
+    @property
+    def device(self) -> torch.device:
+        return self.data.device
+
+    @property
+    def is_cuda(self) -> bool:
+        return self.data.is_cuda
+
+    def is_pinned(self) -> bool:
+        return self.data.is_pinned() and self.offset.is_pinned() and self.hw.is_pinned()
+
+    def to(self, device, non_blocking: bool = False) -> "RaggedFrames":
+        return RaggedFrames(self.data.to(device, non_blocking=non_blocking), self.offset.to(device, non_blocking=non_blocking),
+                            self.hw.to(device, non_blocking=non_blocking), _host=self._host)
+
+    def pin_memory(self, device=None) -> "RaggedFrames":
+        """(called by DataLoader(pin_memory=True) in its pin thread)"""
+        return RaggedFrames(self.data.pin_memory(), self.offset.pin_memory(), self.hw.pin_memory(), _host=self._host)
+
+    def frame(self, b: int) -> torch.Tensor:
+        """A [H_b, W_b, 3] view of frame b."""
+        o, (h, w) = int(self._host[0][b]), (int(v) for v in self._host[1][b])
+        return self.data[o:o + h * w * 3].view(h, w, 3)
+
+
+def _check_ragged_on_device(frames: "RaggedFrames", who: str) -> None:
+    if not frames.is_cuda:
+        raise _lib.PolypMaeError(f"{who} runs on the GPU only (no CPU fallback): move the RaggedFrames to the device first")
+
+
+def draw_rrc_boxes(B: int, height, width, generator: Optional[torch.Generator] = None, scale=(0.2, 1.0),
                    ratio=(3.0 / 4.0, 4.0 / 3.0)):
-    """torchvision 0.10 RandomResizedCrop.get_params for B frames of one size -> int32 [B, 4] = (top, left, h, w)
-    (mae/main_pretrain.py:157: scale (0.2, 1.0), default ratio): up to ten tries of area ~ U(scale) x aspect ~ logU(ratio), then
-    the central-crop fallback."""
+    """torchvision 0.10 RandomResizedCrop.get_params for B frames -> int32 [B, 4] = (top, left, h, w) (mae/main_pretrain.py:157:
+    scale (0.2, 1.0), default ratio): up to ten tries of area ~ U(scale) x aspect ~ logU(ratio), then the central-crop fallback.
+    height / width: one size for the batch, or one per frame (box b is get_params of frame b; one generator serves the batch in
+    frame order, so equal per-frame sizes draw exactly what the scalar form draws)."""
     import math
 
     import numpy as np
     g = generator
-    area = height * width
+    hs = [int(v) for v in height] if isinstance(height, (Sequence, np.ndarray, torch.Tensor)) else [int(height)] * B
+    ws = [int(v) for v in width] if isinstance(width, (Sequence, np.ndarray, torch.Tensor)) else [int(width)] * B
+    if len(hs) != B or len(ws) != B:
+        raise ValueError("height / width: a scalar or one value per frame")
     lr0, lr1 = math.log(ratio[0]), math.log(ratio[1])
     out = np.zeros((B, 4), dtype=np.int32)
     for b in range(B):
+        height, width = hs[b], ws[b]
+        area = height * width
         for _ in range(10):
             target = area * torch.empty(1).uniform_(scale[0], scale[1], generator=g).item()
             aspect = math.exp(torch.empty(1).uniform_(lr0, lr1, generator=g).item())
@@ -200,8 +286,44 @@ class DeviceAugmenter:
         slot[1] = ev
         return dev
 
-    def resize(self, frames: torch.Tensor) -> torch.Tensor:
-        """uint8 [B, Hs, Ws, 3] -> uint8 [B, size, size, 3] (T.Resize((size, size)) on PIL images)."""
+    def _grow(self, name, nbytes: int) -> torch.Tensor:
+        """A uint8 device scratch buffer of at least `nbytes`, reallocated only when a batch needs more than it holds (the size of a
+        ragged batch's workspace follows its largest frame)."""
+        t = self._bufs.get(name)
+        if t is None or t.numel() < nbytes:
+            t = self._bufs[name] = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=self.device)
+        return t
+
+    def _ragged_crop(self, frames: RaggedFrames, boxes, bicubic: bool, name: str) -> torch.Tensor:
+        """pm_aug_resized_crop_ragged_u8: boxes (top, left, h, w) int32 [B, 4], each inside its own frame."""
+        import numpy as np
+        B, S = len(frames), self.size
+        hw = frames.sizes
+        boxes = np.ascontiguousarray(boxes, dtype=np.int32)
+        if boxes.shape != (B, 4) or (boxes[:, 2:] <= 0).any() or (boxes[:, :2] < 0).any() or \
+                (boxes[:, 0] + boxes[:, 2] > hw[:, 0]).any() or (boxes[:, 1] + boxes[:, 3] > hw[:, 1]).any():
+            raise ValueError("crop boxes must be (top, left, h, w) inside their own frame, one per sample")
+        Hmax, Wmax = int(hw[:, 0].max()), int(hw[:, 1].max())
+        lib = _lib.load()
+        ws = self._grow("rrc_ws", int(lib.pm_aug_resized_crop_workspace_bytes(B, Hmax, Wmax, S)))
+        box_d = self._upload(name + "_box", boxes)
+        out = self._buf(name + "_out", (B, S, S, 3), torch.uint8)
+        _lib.check(lib.pm_aug_resized_crop_ragged_u8(frames.data.data_ptr(), frames.offset.data_ptr(), frames.hw.data_ptr(),
+                                                     box_d.data_ptr(), out.data_ptr(), 1 if bicubic else 0, B, Hmax, Wmax, S,
+                                                     ws.data_ptr(), ws.numel(), torch.cuda.current_stream(self.device).cuda_stream),
+                   "pm_aug_resized_crop_ragged_u8")
+        return out
+
+    def resize(self, frames) -> torch.Tensor:
+        """uint8 [B, Hs, Ws, 3] -> uint8 [B, size, size, 3] (T.Resize((size, size)) on PIL images).  A device-resident RaggedFrames
+        goes through the ragged resized crop with the whole frame as the box and the bilinear filter (the same taps)."""
+        if isinstance(frames, RaggedFrames):
+            import numpy as np
+            _check_ragged_on_device(frames, "DeviceAugmenter")
+            hw = frames.sizes
+            boxes = np.zeros((len(frames), 4), dtype=np.int32)
+            boxes[:, 2:] = hw
+            return self._ragged_crop(frames, boxes, False, "rs")
         B, Hs, Ws, _ = frames.shape
         S = self.size
         if (Hs, Ws) == (S, S):
@@ -221,11 +343,17 @@ class DeviceAugmenter:
                                         torch.cuda.current_stream(self.device).cuda_stream), "pm_aug_resize_u8")
         return out
 
-    def random_resized_crop(self, frames: torch.Tensor, boxes=None, generator: Optional[torch.Generator] = None,
+    def random_resized_crop(self, frames, boxes=None, generator: Optional[torch.Generator] = None,
                             bicubic: bool = True) -> torch.Tensor:
-        """uint8 [B, Hs, Ws, 3] -> uint8 [B, size, size, 3]: RandomResizedCrop(size, scale=(0.2, 1.0), interpolation=bicubic) of
-        the MAE pre-train transform (main_pretrain.py:157), one crop box per sample (drawn here unless given)."""
+        """uint8 [B, Hs, Ws, 3] or a device-resident RaggedFrames -> uint8 [B, size, size, 3]: RandomResizedCrop(size,
+        scale=(0.2, 1.0), interpolation=bicubic) of the MAE pre-train transform (main_pretrain.py:157), one crop box per sample
+        (drawn here unless given, for a ragged batch from each frame's own size)."""
         import numpy as np
+        if isinstance(frames, RaggedFrames):
+            _check_ragged_on_device(frames, "DeviceAugmenter")
+            if boxes is None:
+                boxes = draw_rrc_boxes(len(frames), frames.sizes[:, 0], frames.sizes[:, 1], generator)
+            return self._ragged_crop(frames, boxes, bicubic, "rrc")
         if frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[-1] != 3 or not frames.is_contiguous() or not frames.is_cuda:
             raise ValueError("frames must be a contiguous uint8 [B, H, W, 3] tensor on the GPU")
         B, Hs, Ws, _ = frames.shape
@@ -246,26 +374,31 @@ class DeviceAugmenter:
                    "pm_aug_resized_crop_u8")
         return out
 
-    def mae_transform(self, frames: torch.Tensor, boxes=None, hflip=None, generator: Optional[torch.Generator] = None,
+    def mae_transform(self, frames, boxes=None, hflip=None, generator: Optional[torch.Generator] = None,
                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The MAE pre-train transform after decoding (main_pretrain.py:156-160): RandomResizedCrop(bicubic) -> RandomHorizontalFlip
-        -> ToTensor -> Normalize, f32 [B, 3, size, size]."""
-        B = frames.shape[0]
+        -> ToTensor -> Normalize, f32 [B, 3, size, size].  frames: uint8 [B, H, W, 3] or a device-resident RaggedFrames; the
+        generator draws the boxes first, then the flips."""
+        B = len(frames)
         x = self.random_resized_crop(frames, boxes, generator)
         if hflip is None:
             hflip = (torch.rand(B, generator=generator) < 0.5)
         flips = self._upload("mae_flips", torch.as_tensor(hflip).to(torch.uint8).numpy())
         return preprocess_u8(x, flips, self.mean, self.std, out=out)
 
-    def __call__(self, frames: torch.Tensor, params: Optional[dict] = None, generator: Optional[torch.Generator] = None,
+    def __call__(self, frames, params: Optional[dict] = None, generator: Optional[torch.Generator] = None,
                  to_f32: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """frames uint8 [B, H, W, 3] on the device.  Returns f32 [B, 3, size, size] (normalised) or, with to_f32=False, the
-        augmented uint8 frames [B, size, size, 3] (written into `out` when given)."""
+        """frames uint8 [B, H, W, 3] or a RaggedFrames, on the device.  Returns f32 [B, 3, size, size] (normalised) or, with
+        to_f32=False, the augmented uint8 frames [B, size, size, 3] (written into `out` when given).  After the Resize every frame
+        is size x size, so a ragged batch continues down the uniform chain."""
         import numpy as np
-        if frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
-            raise ValueError("frames must be a contiguous uint8 [B, H, W, 3] tensor")
-        if not frames.is_cuda:
-            raise _lib.PolypMaeError("DeviceAugmenter runs on the GPU only (no CPU fallback)")
+        if isinstance(frames, RaggedFrames):
+            _check_ragged_on_device(frames, "DeviceAugmenter")
+        else:
+            if frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
+                raise ValueError("frames must be a contiguous uint8 [B, H, W, 3] tensor")
+            if not frames.is_cuda:
+                raise _lib.PolypMaeError("DeviceAugmenter runs on the GPU only (no CPU fallback)")
         lib = _lib.load()
         st = torch.cuda.current_stream(self.device).cuda_stream
         x = self.resize(frames)
@@ -444,8 +577,9 @@ class DevicePerturber:
     def eval_transform(self, frames: torch.Tensor, rows=None, size: int = 224, mean: Sequence[float] = IMAGENET_MEAN,
                        std: Sequence[float] = IMAGENET_STD) -> torch.Tensor:
         """ClassificationTransforms(stage="val" / "test", enable_perturbations=rows is not None) for a decoded uint8 batch
-        [B, Hs, Ws, 3] of one frame size (transforms.py:234-256): Resize((size, size)) -> [the rows' perturbations] -> ToTensor ->
-        Normalize, f32 [B, 3, size, size] out; three to ten launches, nothing leaves the device."""
+        [B, Hs, Ws, 3] of one frame size, or a device-resident RaggedFrames of mixed sizes (transforms.py:234-256):
+        Resize((size, size)) -> [the rows' perturbations] -> ToTensor -> Normalize, f32 [B, 3, size, size] out; three to ten
+        launches, nothing leaves the device."""
         if self._aug.size != size:
             self._aug = DeviceAugmenter(self.device, size=size)
         x = self._aug.resize(frames)
@@ -454,12 +588,16 @@ class DevicePerturber:
         return preprocess_u8(x, None, mean, std)
 
     def batches(self, loader: Iterable, size: int = 224) -> Iterator[Tuple]:
-        """For the evaluation loop: `loader` yields (decoded uint8 frames [B, Hs, Ws, 3] on the host, labels, rows) -- what
-        PackDataset + pack_collate hand over before the transform (classification/data/packs.py:70-80) -- and this yields
-        (f32 [B, 3, size, size] on the device, labels on the device, rows), i.e. what train.evaluate_cls iterates over, with the
-        rows' perturbations rendered on the way (transforms.py:249-256)."""
+        """For the evaluation loop: `loader` yields (decoded uint8 frames [B, Hs, Ws, 3] or a RaggedFrames, on the host, labels,
+        rows) -- what PackDataset + pack_collate hand over before the transform (classification/data/packs.py:70-80) -- and this
+        yields (f32 [B, 3, size, size] on the device, labels on the device, rows), i.e. what train.evaluate_cls iterates over, with
+        the rows' perturbations rendered on the way (transforms.py:249-256)."""
         for frames, labels, rows in loader:
-            x = self.eval_transform(torch.as_tensor(frames).to(self.device, non_blocking=True).contiguous(), rows, size=size)
+            if isinstance(frames, RaggedFrames):
+                frames = frames.to(self.device, non_blocking=True)
+            else:
+                frames = torch.as_tensor(frames).to(self.device, non_blocking=True).contiguous()
+            x = self.eval_transform(frames, rows, size=size)
             yield x, torch.as_tensor(labels).to(self.device, non_blocking=True), rows
 
     def __call__(self, frames: torch.Tensor, rows) -> torch.Tensor:
@@ -530,23 +668,28 @@ class DevicePerturber:
 
 
 class DevicePrefetcher:
-    """Wraps a loader that yields (frames uint8 [B,H,W,3] on the host, *rest): copies batch i+1 to the device on a
-    side stream (pinned staging, two slots) while batch i is consumed, and yields (imgs float32 [B,3,H,W] on the
-    device, *rest on the device).  The yielded image tensor is a per-slot buffer that is refilled two batches later
-    (consume it within the step, as a training loop does).  `flip_p > 0` draws per-sample horizontal / vertical flips (RandomHorizontalFlip /
-    RandomVerticalFlip of the reference's train transform) from `generator`."""
+    """Wraps a loader that yields (frames, *rest) -- frames uint8 [B,H,W,3] or a RaggedFrames of mixed sizes, on the host --:
+    copies batch i+1 to the device on a side stream (pinned staging, two slots) while batch i is consumed, and yields (imgs
+    float32 [B,3,S,S] on the device, *rest on the device).  The yielded image tensor is a per-slot buffer that is refilled two
+    batches later (consume it within the step, as a training loop does).  `flip_p > 0` draws per-sample horizontal / vertical flips
+    (RandomHorizontalFlip / RandomVerticalFlip of the reference's train transform) from `generator`."""
 
     def __init__(self, loader: Iterable, device, mean: Sequence[float] = IMAGENET_MEAN, std: Sequence[float] = IMAGENET_STD,
                  flip_p: float = 0.0, generator: Optional[torch.Generator] = None, augment: Optional["DeviceAugmenter"] = None,
-                 stream: str = "auto"):
-        """augment: a DeviceAugmenter -> the loader may yield decoded frames of any (batch-uniform) size and the WHOLE train
-        transform of the reference (Resize, ColorJitter, GaussianBlur(25), flips, RandomRotation(180), ToTensor, Normalize) runs
-        on the copy stream; `flip_p` is then ignored (the augmenter draws its own flips from `generator`).
-        LIMITATION: every frame of a batch must have the SAME decoded size (a batch is one [B, H, W, 3] array and the Resize taps
-        are cached per (H, W)); the reference resizes image by image, and Hyperkvasir / SUN mix several native resolutions.  A
-        loader over mixed-size data has to bucket frames by source size per batch (a batch sampler keyed on the manifest's size
-        column) -- or take the per-sample path that `pm_aug_resized_crop_u8` already has for the MAE transform.  The device path
-        is wired into bench.py and the tests; the cls training entry points still take whatever loader the caller passes.
+                 stream: str = "auto", transform: str = "train"):
+        """augment: a DeviceAugmenter -> the loader may yield decoded frames of any size and a transform of the reference runs on
+        the copy stream, drawing its parameters from `generator` (`flip_p` is then ignored):
+          transform="train": the classification train transform (Resize, ColorJitter, GaussianBlur(25), flips,
+                             RandomRotation(180), ToTensor, Normalize; classification/data/transforms.py:234-246);
+          transform="mae":   the MAE pre-train transform (RandomResizedCrop(bicubic), RandomHorizontalFlip, ToTensor, Normalize;
+                             mae/main_pretrain.py:156-160).
+        Frames of mixed decoded sizes -- an image folder such as Hyperkvasir-unlabelled -- arrive as a RaggedFrames (see
+        `ragged_collate`): one host-to-device copy of the packed bytes plus the two small offset / size tables, then the per-sample
+        resized crop (pm_aug_resized_crop_ragged_u8: the Resize of "train" is a crop with the whole frame as its box) brings every
+        frame to S x S on the device, and the rest of the chain is the uniform one.  The pinned and device staging buffers of a
+        ragged batch are sized in bytes, kept per slot and only ever grow; a batch that arrives pinned (DataLoader(pin_memory=True))
+        is copied from where it lies.  Uniform [B, H, W, 3] batches keep their own path (and, without `augment`, the fused
+        flips + ToTensor + Normalize of pm_preprocess_u8 only).
         stream: where the copies and the transform run -- "own": a stream of the prefetcher (a fourth busy stream beside the
         engine's three: one hardware queue each, fastest on a single GPU); "side": the engine's weight-gradient stream (idle
         during the forward pass, when the next batch is staged) -- for data-parallel ranks, where RCCL's stream is the fourth busy
@@ -554,13 +697,19 @@ class DevicePrefetcher:
         "auto": "side" when a torch.distributed process group is initialised, "own" otherwise."""
         if stream not in ("auto", "own", "side"):
             raise ValueError("stream must be 'auto', 'own' or 'side'")
-        self.stream_mode = stream
+        if transform not in ("train", "mae"):
+            raise ValueError("transform must be 'train' or 'mae'")
+        if transform == "mae" and augment is None:
+            raise ValueError("transform='mae' needs a DeviceAugmenter (augment=...)")
+        self.stream_mode, self.transform = stream, transform
         self.loader, self.device = loader, torch.device(device)
         self.mean, self.std, self.flip_p, self.generator = mean, std, float(flip_p), generator
         self.augment = augment
         self._pinned = [None, None]
         self._flip_pin = [None, None]   # per slot: pinned flip flags
         self._dev = [None, None]        # per slot: (uint8 frames, float32 images) on the device
+        self._ragged_pin = [None, None]  # per slot, ragged batches: pinned (bytes, offset, hw), grow-only
+        self._ragged_dev = [None, None]  # per slot, ragged batches: device (bytes, offset, hw), grow-only
         self._consumed = [None, None]   # per slot: event recorded on the consumer's stream after it used the batch
         self._slot_copied = [None, None]  # per slot: event after the slot's host-to-device copies were enqueued
         self._stream: Optional[torch.cuda.Stream] = None
@@ -568,8 +717,59 @@ class DevicePrefetcher:
     def __len__(self):
         return len(self.loader)
 
+    @staticmethod
+    def _grown(t: Optional[torch.Tensor], n: int, dtype, device=None) -> torch.Tensor:
+        """`t` if it holds n elements, else a new buffer of n on `device` (None: pinned host memory) -- grow-only staging."""
+        if t is None or t.numel() < n:
+            t = torch.empty(n, dtype=dtype, device=device, pin_memory=device is None)
+        return t
+
+    def _stage_ragged(self, slot: int, frames: RaggedFrames) -> RaggedFrames:
+        """One host-to-device copy of the packed bytes + the two tables into this slot's grow-only device buffers (through its
+        grow-only pinned buffers unless the batch is pinned already).  Called on the copy stream."""
+        B, nbytes = len(frames), frames.data.numel()
+        if frames.is_pinned():
+            src = (frames.data, frames.offset, frames.hw.view(-1))
+        else:
+            pin = self._ragged_pin[slot] or (None, None, None)
+            pin = tuple(self._grown(t, n, dt) for t, n, dt in zip(pin, (nbytes, B, 2 * B), (torch.uint8, torch.int64, torch.int32)))
+            self._ragged_pin[slot] = pin
+            src = (pin[0][:nbytes], pin[1][:B], pin[2][:2 * B])
+            src[0].copy_(frames.data)
+            src[1].copy_(frames.offset)
+            src[2].copy_(frames.hw.view(-1))
+        dev = self._ragged_dev[slot] or (None, None, None)
+        dev = tuple(self._grown(t, n, dt, device=self.device)
+                    for t, n, dt in zip(dev, (nbytes, B, 2 * B), (torch.uint8, torch.int64, torch.int32)))
+        self._ragged_dev[slot] = dev
+        for d, h in zip(dev, src):
+            d[:h.numel()].copy_(h, non_blocking=True)
+        return RaggedFrames(dev[0][:nbytes], dev[1][:B], dev[2][:2 * B].view(B, 2), _host=frames._host)
+
     def _stage(self, slot: int, batch) -> Tuple:
         frames, rest = batch[0], tuple(batch[1:])
+        if isinstance(frames, RaggedFrames):
+            if self.augment is None:
+                raise ValueError("a RaggedFrames batch needs a DeviceAugmenter (augment=...) to bring its frames to one size")
+            S = self.augment.size
+            bufs = self._dev[slot]
+            if bufs is None or bufs[1].shape != (len(frames), 3, S, S):
+                with torch.cuda.stream(self._stream):
+                    bufs = (None, torch.empty((len(frames), 3, S, S), dtype=torch.float32, device=self.device))
+                self._dev[slot] = bufs
+            with torch.cuda.stream(self._stream):
+                if self._consumed[slot] is not None:
+                    self._stream.wait_event(self._consumed[slot])
+                x = self._stage_ragged(slot, frames)
+                if self.transform == "mae":
+                    imgs = self.augment.mae_transform(x, generator=self.generator, out=bufs[1])
+                else:
+                    imgs = self.augment(x, generator=self.generator, out=bufs[1])
+                rest_dev = tuple(t.to(self.device, non_blocking=True) if torch.is_tensor(t) else t for t in rest)
+                ev = torch.cuda.Event()
+                ev.record(self._stream)
+                self._slot_copied[slot] = ev
+            return imgs, rest_dev, ev
         if frames.dtype != torch.uint8:
             raise ValueError("DevicePrefetcher expects uint8 HWC frames from the loader")
         if frames.is_pinned():  # e.g. DataLoader(pin_memory=True): no staging copy
@@ -593,7 +793,7 @@ class DevicePrefetcher:
         # device buffers are owned per slot and reused (no allocator traffic on the copy stream): the copy stream first
         # waits until the consumer's work on the batch that last used this slot has been enqueued AND executed
         bufs = self._dev[slot]
-        if bufs is None or bufs[0].shape != frames.shape:
+        if bufs is None or bufs[0] is None or bufs[0].shape != frames.shape:
             B, H, W, _ = frames.shape
             S = self.augment.size if self.augment is not None else None
             bufs = (torch.empty(frames.shape, dtype=torch.uint8, device=self.device),
@@ -603,7 +803,9 @@ class DevicePrefetcher:
             if self._consumed[slot] is not None:
                 self._stream.wait_event(self._consumed[slot])
             bufs[0].copy_(pin, non_blocking=True)
-            if self.augment is not None:
+            if self.augment is not None and self.transform == "mae":
+                imgs = self.augment.mae_transform(bufs[0], generator=self.generator, out=bufs[1])
+            elif self.augment is not None:
                 imgs = self.augment(bufs[0], generator=self.generator, out=bufs[1])
             else:
                 fl = flips.to(self.device, non_blocking=True) if flips is not None else None

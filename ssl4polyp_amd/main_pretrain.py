@@ -7,9 +7,14 @@ behaviour: lr = blr * batch_size * accum_iter * world / 256 (:201-204), AdamW(be
     python -m ssl4polyp_amd.main_pretrain --synthetic 50 --epochs 2 --batch_size 256
     python -m torch.distributed.run --nproc-per-node 8 -m ssl4polyp_amd.main_pretrain --synthetic 50 ...
 
-Data: the reference's torchvision ImageFolder + augmentation pipeline is outside this build's scope (SURVEY §8-f
-rank 2); pass `--synthetic N` for N device-resident Hyperkvasir-shaped batches per epoch, or import `run()` and hand
-it your own iterable of (images, _) batches.
+Data (main_pretrain.py:156-190): `--data_path DIR` trains on the image folder DIR/train (DIR itself with `--no_train_dir`, as for
+Hyperkvasir-unlabelled) through folder.folder_loader -- ImageFolder discovery, DistributedSampler(shuffle, seed), drop_last,
+`--num_workers` spawned workers that only decode, `--pin_mem` -- and the MAE transform (RandomResizedCrop(bicubic), flip,
+ToTensor, Normalize) on the device per frame at its native size (data.DevicePrefetcher(transform="mae")).  `--synthetic N`
+instead runs N device-resident Hyperkvasir-shaped batches per epoch; `run(args, data_loader)` takes any iterable of
+(images, _) batches.  Without a folder at the data path and without --synthetic there is no data and the command exits.
+
+    python -m ssl4polyp_amd.main_pretrain --data_path /data/hyperkvasir-unlabelled --no_train_dir --batch_size 64
 """
 from __future__ import annotations
 
@@ -48,7 +53,13 @@ def get_args_parser():
     p.add_argument("--start_epoch", default=0, type=int)
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"],
                    help="fp16 = the reference's `--precision amp` arithmetic (fp16 matmuls, f32 accumulation, dynamic loss scaling)")
-    p.add_argument("--synthetic", default=0, type=int, help="number of synthetic batches per epoch")
+    p.add_argument("--data_path", default="/datasets01/imagenet_full_size/061417/", type=str, help="dataset path")
+    p.add_argument("--no_train_dir", action="store_true", help="do not append /train to data_path (e.g. Hyperkvasir-unlabelled)")
+    p.add_argument("--num_workers", default=10, type=int)
+    p.add_argument("--pin_mem", action="store_true", help="pin CPU memory in the DataLoader")
+    p.add_argument("--no_pin_mem", action="store_false", dest="pin_mem")
+    p.set_defaults(pin_mem=True)
+    p.add_argument("--synthetic", default=0, type=int, help="number of synthetic batches per epoch (instead of --data_path)")
     p.add_argument("--save_every", default=1, type=int)
     p.add_argument("--log_every", default=20, type=int)
     return p
@@ -77,12 +88,25 @@ def run(args, data_loader=None):
     scaler = LossScaler() if args.precision == "fp16" else None  # main_pretrain.py:219: loss_scaler = NativeScaler()
     if args.resume:  # (DataParallel() above already bound the parameters to the flat device storage)
         args.start_epoch = load_mae_checkpoint(args.resume, model, opt, args, loss_scaler=scaler)
+    sampler = None
     if data_loader is None:
-        if args.synthetic <= 0:
-            raise SystemExit("no data: pass --synthetic N or call run(args, data_loader)")
-        data_loader = SyntheticLoader(args.batch_size, args.synthetic, device, args.input_size, seed=1234 + rank, fresh=True)
+        if args.synthetic > 0:
+            data_loader = SyntheticLoader(args.batch_size, args.synthetic, device, args.input_size, seed=1234 + rank, fresh=True)
+        else:
+            data_dir = args.data_path if args.no_train_dir else os.path.join(args.data_path, "train")  # main_pretrain.py:162
+            if not os.path.isdir(data_dir):
+                raise SystemExit(f"no data: {data_dir} is not a directory; pass --data_path DIR, --synthetic N or call "
+                                 "run(args, data_loader)")
+            from .data import DeviceAugmenter, DevicePrefetcher
+            from .folder import folder_loader
+            loader = folder_loader(data_dir, args.batch_size, world, rank, args.seed, args.num_workers, args.pin_mem)
+            sampler = loader.sampler
+            data_loader = DevicePrefetcher(loader, device, augment=DeviceAugmenter(device, size=args.input_size), transform="mae",
+                                           generator=torch.Generator().manual_seed(args.seed + rank))
     log_path = os.path.join(args.output_dir, "log.txt")
     for epoch in range(args.start_epoch, args.epochs):
+        if sampler is not None:
+            sampler.set_epoch(args.seed + epoch)  # main_pretrain.py:286 (the seed is added once more by the sampler itself)
         stats = train_one_epoch_mae(ddp, data_loader, opt, device, epoch, args, log_every=args.log_every, loss_scaler=scaler,
                                     printer=(lambda r: print(f"epoch {epoch} {json.dumps(r)}", flush=True)) if rank == 0 else None)
         if rank == 0:
