@@ -328,6 +328,26 @@ int pm_aug_pil_gaussian_blur_u8(const unsigned char* src, unsigned char* tmp, un
 int pm_aug_occlude_u8(unsigned char* img, const int* rects, int B, int H, int W, void* stream);
 int pm_aug_jpeg_roundtrip_u8(const unsigned char* src, unsigned char* dst, const int* quality, int B, int H, int W, void* stream);
 
+/* Baseline JPEG decode of a batch of files -- what the reference's DataLoader workers do with Pillow (datasets.ImageFolder's
+ * pil_loader: Image.open(f).convert("RGB"), mae/main_pretrain.py:161-190), bit for bit with its libjpeg-turbo, for 8-bit
+ * Huffman-coded sequential files with one scan, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0, any restart interval.  The host
+ * (ssl4polyp_amd/jpeg.py) parses and packs; here: entropy decode (jdhuff.c, one lane per restart interval) -> dequantise + islow
+ * inverse DCT (jidctint.c) -> fancy upsampling (jdsample.c) + YCbCr -> RGB (jdcolor.c), packed HWC uint8 into `out`; frames the
+ * host decoded itself (fallback) are copied to their slots.
+ *   entropy: the unstuffed restart intervals, each on a 16-byte boundary, zero-padded; 16-byte aligned, entropy_bytes a multiple
+ *     of 16.
+ *   intervals int32 [n_intervals][8] = (frame, word offset, byte length, first MCU, MCU count, 0, 0, 0).
+ *   frames int32 [n_frames][32] = (H, W, components, luma h / v sampling, MCU columns / rows, restart interval, DC / AC /
+ *     quantisation table per component, first coefficient block per component, output byte offset lo / hi, first pixel lo / hi).
+ *   huff [n_huff][1024]: derived Huffman tables (jpeg.py derive_huffman); quant int32 [n_quant][64], natural order.
+ *   fallback_table [n_fallback][3] = (offset in `fallback`, offset in `out`, bytes).
+ *   Workspace: coef int16 [blocks * 64] and planes uint8 [blocks * 64], blocks = the batch's coefficient blocks; pixels = the
+ *   device frames' pixels.  A table row that would address memory outside these sizes is skipped. */
+int pm_jpeg_decode(const unsigned char* entropy, long entropy_bytes, const int* intervals, int n_intervals, const int* frames,
+                   int n_frames, const unsigned char* huff, int n_huff, const int* quant, int n_quant, const unsigned char* fallback,
+                   long fallback_bytes, const long long* fallback_table, int n_fallback, short* coef, unsigned char* planes,
+                   long blocks, long pixels, unsigned char* out, long out_bytes, void* stream);
+
 /* One transformer block forward for one range of samples in ONE call (timm Block: models_mae.py:39-41,53-55,166-167,
  * 186-187; models.py:122-123,204-205):  x_mid = x + proj(attn(LN1 x));  x_out = x_mid + fc2(gelu(fc1(LN2 x_mid))).
  * Host-side composition of pm_layernorm_fwd / pm_gemm_ex / pm_attention_fwd on `stream`, launch for launch what a caller

@@ -58,6 +58,7 @@ SIGNATURES = {
     "pm_aug_pil_gaussian_blur_u8": [P, P, P, P, I, I, I, I, P],
     "pm_aug_occlude_u8": [P, P, I, I, I, P],
     "pm_aug_jpeg_roundtrip_u8": [P, P, P, I, I, I, P],
+    "pm_jpeg_decode": [P, L, P, I, P, I, P, I, P, I, P, L, P, I, P, P, L, L, P, L, P],
     "pm_comm_unique_id": [P],
     "pm_comm_create": [P, P, I, I],
     "pm_comm_world": [P, P, P],
@@ -117,7 +118,7 @@ class BlockFwdDesc(ctypes.Structure):
                 [("eps", ctypes.c_float)])
 
 
-PM_ESHAPE = -2
+PM_EINVAL, PM_ESHAPE, PM_EALIGN = -1, -2, -5
 _lib = None
 
 

@@ -473,9 +473,7 @@ __device__ const unsigned char kStdChr[64] = {17, 18, 24, 47, 99, 99, 99, 99, 18
                                               24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
                                               99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
                                               99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99};
-constexpr int kF0298 = 2446, kF0390 = 3196, kF0541 = 4433, kF0765 = 6270, kF0899 = 7373, kF1175 = 9633, kF1501 = 12299, kF1847 = 15137,
-              kF1961 = 16069, kF2053 = 16819, kF2562 = 20995, kF3072 = 25172;
-__device__ __forceinline__ int jdescale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+// (the islow constants, jdescale and the inverse pass jidct8 are in pm_common.h)
 
 // one 8-point forward pass of jfdctint.c on d[0], d[s], ..., d[7 s] (first: rows, output << PASS1_BITS; second: columns)
 __device__ __forceinline__ void jfdct8(int* d, int s, bool first) {
@@ -501,44 +499,6 @@ __device__ __forceinline__ void jfdct8(int* d, int s, bool first) {
   d[3 * s] = jdescale(a6 + z2 + z3, sh);
   d[s] = jdescale(a7 + z1 + z4, sh);
 }
-// one 8-point inverse pass of jidctint.c (first: columns, descale CONST_BITS - PASS1_BITS; second: rows, + 3 more bits)
-__device__ __forceinline__ void jidct8(int* c, int s, bool first) {
-  int z2 = c[2 * s], z3 = c[6 * s];
-  int z1 = (z2 + z3) * kF0541;
-  const int e2 = z1 + z3 * (-kF1847), e3 = z1 + z2 * kF0765;
-  z2 = c[0];
-  z3 = c[4 * s];
-  const int e0 = (z2 + z3) << 13, e1 = (z2 - z3) << 13;
-  const int t10 = e0 + e3, t13 = e0 - e3, t11 = e1 + e2, t12 = e1 - e2;
-  int o0 = c[7 * s], o1 = c[5 * s], o2 = c[3 * s], o3 = c[s];
-  z1 = o0 + o3;
-  z2 = o1 + o2;
-  z3 = o0 + o2;
-  int z4 = o1 + o3;
-  const int z5 = (z3 + z4) * kF1175;
-  o0 *= kF0298;
-  o1 *= kF2053;
-  o2 *= kF3072;
-  o3 *= kF1501;
-  z1 *= -kF0899;
-  z2 *= -kF2562;
-  z3 = z3 * -kF1961 + z5;
-  z4 = z4 * -kF0390 + z5;
-  o0 += z1 + z3;
-  o1 += z2 + z4;
-  o2 += z2 + z3;
-  o3 += z1 + z4;
-  const int sh = first ? 13 - 2 : 13 + 2 + 3;
-  c[0] = jdescale(t10 + o3, sh);
-  c[7 * s] = jdescale(t10 - o3, sh);
-  c[s] = jdescale(t11 + o2, sh);
-  c[6 * s] = jdescale(t11 - o2, sh);
-  c[2 * s] = jdescale(t12 + o1, sh);
-  c[5 * s] = jdescale(t12 - o1, sh);
-  c[3 * s] = jdescale(t13 + o0, sh);
-  c[4 * s] = jdescale(t13 - o0, sh);
-}
-
 // quality: int [B]; <= 0: the sample is copied.  In place is fine (a thread reads and writes its own block only).
 __global__ __launch_bounds__(64) void jpeg_roundtrip_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
                                                             const int* __restrict__ quality, int B, int H, int W) {

@@ -335,3 +335,47 @@ template <typename T> __device__ __forceinline__ f32x4 gelu_act_grad4(f32x4 v) {
 template <typename T> __device__ __forceinline__ f32x4 round_through(f32x4 v) {
   return f32x4{to_f32<T>(from_f32<T>(v[0])), to_f32<T>(from_f32<T>(v[1])), to_f32<T>(from_f32<T>(v[2])), to_f32<T>(from_f32<T>(v[3]))};
 }
+
+// libjpeg's "islow" DCT constants (jfdctint.c / jidctint.c: FIX(x) = x * 2^13 rounded) and DESCALE, shared by the JPEG round trip
+// of pm_augment.hip and the baseline decoder of pm_jpeg.hip
+constexpr int kF0298 = 2446, kF0390 = 3196, kF0541 = 4433, kF0765 = 6270, kF0899 = 7373, kF1175 = 9633, kF1501 = 12299, kF1847 = 15137,
+              kF1961 = 16069, kF2053 = 16819, kF2562 = 20995, kF3072 = 25172;
+__device__ __forceinline__ int jdescale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+
+// one 8-point inverse pass of jidctint.c (first: columns, descale CONST_BITS - PASS1_BITS; second: rows, + 3 more bits)
+__device__ __forceinline__ void jidct8(int* c, int s, bool first) {
+  int z2 = c[2 * s], z3 = c[6 * s];
+  int z1 = (z2 + z3) * kF0541;
+  const int e2 = z1 + z3 * (-kF1847), e3 = z1 + z2 * kF0765;
+  z2 = c[0];
+  z3 = c[4 * s];
+  const int e0 = (z2 + z3) << 13, e1 = (z2 - z3) << 13;
+  const int t10 = e0 + e3, t13 = e0 - e3, t11 = e1 + e2, t12 = e1 - e2;
+  int o0 = c[7 * s], o1 = c[5 * s], o2 = c[3 * s], o3 = c[s];
+  z1 = o0 + o3;
+  z2 = o1 + o2;
+  z3 = o0 + o2;
+  int z4 = o1 + o3;
+  const int z5 = (z3 + z4) * kF1175;
+  o0 *= kF0298;
+  o1 *= kF2053;
+  o2 *= kF3072;
+  o3 *= kF1501;
+  z1 *= -kF0899;
+  z2 *= -kF2562;
+  z3 = z3 * -kF1961 + z5;
+  z4 = z4 * -kF0390 + z5;
+  o0 += z1 + z3;
+  o1 += z2 + z4;
+  o2 += z2 + z3;
+  o3 += z1 + z4;
+  const int sh = first ? 13 - 2 : 13 + 2 + 3;
+  c[0] = jdescale(t10 + o3, sh);
+  c[7 * s] = jdescale(t10 - o3, sh);
+  c[s] = jdescale(t11 + o2, sh);
+  c[6 * s] = jdescale(t11 - o2, sh);
+  c[2 * s] = jdescale(t12 + o1, sh);
+  c[5 * s] = jdescale(t12 - o1, sh);
+  c[3 * s] = jdescale(t13 + o0, sh);
+  c[4 * s] = jdescale(t13 - o0, sh);
+}

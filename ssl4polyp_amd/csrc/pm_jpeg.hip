@@ -1,0 +1,374 @@
+// Baseline JPEG decode on the device, bit for bit with libjpeg-turbo as Pillow runs it (ssl4polyp_amd/jpeg.py packs the batch on
+// the host: unstuffed restart intervals, frame rows, derived Huffman tables, quantisation tables).  Three integer-only stages:
+//   1. jpeg_huff_kernel: entropy decode (jdhuff.c decode_mcu) -> int16 coefficients in natural order.  One lane per restart
+//      interval; a wave packs 64 intervals of different frames (the host sorts them by length so its lanes finish together), so
+//      the decode holds few SIMDs while the training step runs beside it.  The bit reservoir lives in registers and is refilled
+//      from aligned 16-byte loads issued a group ahead.  The coefficients are zeroed on the stream, then only the nonzero ones
+//      are stored.  Lookahead tables in LDS when the batch's tables fit in 31 KiB (with the zigzag table: < 32 KiB).
+//   2. jpeg_idct_kernel: dequantise + islow inverse DCT (jidctint.c) -> uint8 component planes padded to the MCU grid, one thread
+//      per 8 x 8 block as in pm_augment.hip's jpeg_roundtrip_kernel.
+//   3. jpeg_color_kernel: fancy upsampling where libjpeg-turbo uses it (jdsample.c h2v1 / h2v2 triangle filters, downsampled
+//      width > 2; replication otherwise; the rows above / below the plane repeat its first / last real row as jdmainct.c's
+//      context pointers do) + YCbCr -> RGB (jdcolor.c) or grey -> RGB, packed HWC at each frame's output offset.
+//   jpeg_copy_kernel puts the frames decoded on the host (fallback) into their slots.
+// Bad data follows libjpeg's rules, and every access is bounded by construction: a code longer than 16 bits decodes as symbol 0,
+// reading past the interval yields zero bits and the MCUs after the one that ran out stay zero (jdhuff.c insufficient_data), runs
+// index a natural-order table padded with 63, a lane writes its interval's MCUs only, and a table row that would address memory
+// outside the caller's buffers is skipped.  (The pixels of a corrupt frame can still differ from Pillow's where libjpeg-turbo's SIMD
+// IDCT saturates garbage coefficients that the C arithmetic restated here wraps.)
+#include "pm_common.h"
+
+namespace {
+
+struct HuffTable {            // jpeg.py derive_huffman (jdhuff.c d_derived_tbl)
+  unsigned short look[256];   // code length << 8 | symbol for codes of <= 8 bits; 9 << 8: longer
+  int maxcode[18];
+  int valoffset[18];
+  unsigned char huffval[256];
+  uint4 limit[2];             // lengths 9..16: (maxcode + 1) << (16 - l), carried over lengths without codes (non-decreasing)
+  int voff[8];                // lengths 9..16: valoffset
+  unsigned char pad[48];
+};
+static_assert(sizeof(HuffTable) == 1024, "HuffTable layout (jpeg.HUFF_RECORD)");
+
+constexpr int kFrameWords = 32, kIntervalWords = 8;
+constexpr int kLdsTables = 31;  // < 32 KiB of LDS with the zigzag table (the step's GEMMs hold 128 of the CU's 160 KiB)
+
+__device__ const unsigned char kNatural[80] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33,
+                                               40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36,
+                                               29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54,
+                                               47, 55, 62, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63};
+
+// frame row (jpeg.py JpegBatch.from_bytes): 0 H, 1 W, 2 components, 3 / 4 luma sampling h / v, 5 / 6 MCU columns / rows,
+// 7 restart interval, 8-10 DC table, 11-13 AC table, 14-16 quantisation table, 17-19 first coefficient block per component,
+// 20-21 output byte offset (lo, hi), 22-23 first pixel among the device frames (lo, hi)
+__device__ __forceinline__ long frame_long(const int* F, int i) { return (long)(((unsigned long)(unsigned)F[i + 1] << 32) | (unsigned)F[i]); }
+
+// a frame row whose MCU grid is one of the supported layouts, with every component plane inside `blocks`
+__device__ __forceinline__ bool frame_ok(const int* F, long blocks) {
+  const int ncomp = F[2], hs = F[3], vs = F[4], mcux = F[5], mcuy = F[6];
+  if ((ncomp != 1 && ncomp != 3) || hs < 1 || hs > 2 || vs < 1 || vs > hs || mcux <= 0 || mcuy <= 0) return false;
+  if (ncomp == 1 && (hs != 1 || vs != 1)) return false;
+  if (F[0] <= 0 || F[1] <= 0 || F[0] > mcuy * 8 * vs || F[1] > mcux * 8 * hs) return false;
+  for (int c = 0; c < ncomp; ++c) {
+    const long n = (long)mcux * mcuy * (c == 0 ? hs * vs : 1);
+    if (F[17 + c] < 0 || F[17 + c] + n > blocks) return false;
+  }
+  return true;
+}
+
+// The bit reservoir: 64 bits in registers, refilled 32 bits at a time from 16-byte groups of the interval, two groups in flight (the
+// group being consumed and the next one, loaded when the one before it was taken up: ~128 bits ahead of its use).  `left` counts
+// the interval's bits not yet consumed; below zero, a decode has read past its data (libjpeg's insufficient_data).
+struct BitReader {
+  const uint4* groups;
+  long g, gend;            // next group to load, end of the interval's groups
+  unsigned long long buf;  // the next `bits` bits of the interval, left-aligned; zeros below them
+  int bits, ci;            // ci: words of `cur` taken up
+  long left;
+  uint4 cur, nxt;
+  __device__ __forceinline__ uint4 load() {
+    const uint4 v = g < gend ? groups[g] : make_uint4(0u, 0u, 0u, 0u);  // past the interval: zero bits
+    ++g;
+    return v;
+  }
+  __device__ __forceinline__ void init(const uint4* p, long g0, long n, long nbits) {
+    groups = p;
+    g = g0;
+    gend = g0 + n;
+    buf = 0;
+    bits = 0;
+    ci = 0;
+    left = nbits;
+    cur = load();
+    nxt = load();
+  }
+  __device__ __forceinline__ void fill() {  // afterwards at least 32 bits are in the reservoir
+    if (bits <= 32) {
+      const unsigned v = ci == 0 ? cur.x : (ci == 1 ? cur.y : (ci == 2 ? cur.z : cur.w));
+      buf |= (unsigned long long)__builtin_bswap32(v) << (32 - bits);
+      bits += 32;
+      if (++ci == 4) {
+        cur = nxt;
+        nxt = load();
+        ci = 0;
+      }
+    }
+  }
+  __device__ __forceinline__ unsigned peek(int n) const { return (unsigned)(buf >> (64 - n)); }  // 1 <= n <= 32
+  __device__ __forceinline__ void skip(int n) {
+    buf <<= n;
+    bits -= n;
+    left -= n;
+  }
+};
+
+// jdhuff.c HUFF_DECODE + jpeg_huff_decode: at most 17 bits (a code over 16 bits is symbol 0).  A code longer than the lookahead
+// finds its length from the eight left-justified limits at once (two 16-byte reads) instead of one maxcode read per extra bit:
+// the first l with (16 bits) < limit[l] is the first l with code_l <= maxcode[l], which is where jpeg_huff_decode's loop stops.
+__device__ __forceinline__ int huff_decode(BitReader& br, const HuffTable* t) {
+  const unsigned p16 = br.peek(16);
+  const unsigned look = t->look[p16 >> 8];
+  int nb = look >> 8, sym = look & 0xFF;
+  if (nb > 8) {
+    const uint4 a = t->limit[0], b = t->limit[1];
+    const int l = 9 + (p16 >= a.x) + (p16 >= a.y) + (p16 >= a.z) + (p16 >= a.w) + (p16 >= b.x) + (p16 >= b.y) + (p16 >= b.z) +
+                  (p16 >= b.w);
+    if (l > 16) {
+      sym = 0;
+      nb = 17;
+    } else {
+      sym = t->huffval[((p16 >> (16 - l)) + t->voff[l - 9]) & 0xFF];
+      nb = l;
+    }
+  }
+  br.skip(nb);
+  return sym;
+}
+
+__device__ __forceinline__ int huff_extend(int r, int s) { return r < (1 << (s - 1)) ? r - (1 << s) + 1 : r; }
+
+// one block of decode_mcu: DC difference + prediction, then the AC run / size symbols; only nonzero coefficients are stored
+__device__ __forceinline__ void decode_block(BitReader& br, const HuffTable* dc, const HuffTable* ac, int& pred, short* blk,
+                                             const unsigned char* nat) {
+  br.fill();
+  int s = huff_decode(br, dc);
+  s = s > 15 ? 15 : s;  // (DC tables are checked on the host: symbols <= 15)
+  int diff = 0;
+  if (s) {
+    diff = huff_extend((int)br.peek(s), s);
+    br.skip(s);
+  }
+  pred = (int)((unsigned)pred + (unsigned)diff);  // (libjpeg-turbo adds as unsigned: corrupt data may wrap)
+  if ((short)pred != 0) blk[0] = (short)pred;
+  for (int k = 1; k < 64; ++k) {
+    br.fill();
+    const int sym = huff_decode(br, ac);
+    const int r = sym >> 4;
+    s = sym & 15;
+    if (s) {
+      k += r;  // <= 78: the padded table keeps it inside the block
+      const int v = huff_extend((int)br.peek(s), s);
+      br.skip(s);
+      blk[nat[k]] = (short)v;
+    } else {
+      if (r != 15) break;
+      k += 15;
+    }
+  }
+}
+
+template <bool kLds>
+__global__ __launch_bounds__(64) void jpeg_huff_kernel(const unsigned* __restrict__ words, long n_words, const int* __restrict__ iv,
+                                                       int n_iv, const int* __restrict__ fr, int n_fr,
+                                                       const HuffTable* __restrict__ huff, int n_huff, short* __restrict__ coef,
+                                                       long blocks) {
+  __shared__ HuffTable lds_tab[kLds ? kLdsTables : 1];
+  __shared__ unsigned char nat[80];
+  if (kLds) {
+    const unsigned* src = reinterpret_cast<const unsigned*>(huff);
+    unsigned* dst = reinterpret_cast<unsigned*>(lds_tab);
+    for (int i = threadIdx.x; i < n_huff * 256; i += 64) dst[i] = src[i];
+  }
+  for (int i = threadIdx.x; i < 80; i += 64) nat[i] = kNatural[i];
+  __syncthreads();
+  const HuffTable* tabs = kLds ? lds_tab : huff;
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n_iv) return;
+  const int* I = iv + (long)i * kIntervalWords;
+  const int f = I[0], nbytes = I[2], m0 = I[3], nm = I[4];
+  const long w0 = I[1];
+  if (f < 0 || f >= n_fr || w0 < 0 || (w0 & 3) || nbytes < 0 || m0 < 0 || nm < 0) return;
+  const long ng = ((long)nbytes + 15) >> 4;  // 16-byte groups
+  if (w0 + ng * 4 > n_words) return;
+  const int* F = fr + (long)f * kFrameWords;
+  if (!frame_ok(F, blocks)) return;
+  const int ncomp = F[2], hs = F[3], vs = F[4], mcux = F[5];
+  if ((long)m0 + nm > (long)mcux * F[6]) return;
+  const HuffTable *dc0 = nullptr, *dc1 = nullptr, *dc2 = nullptr, *ac0 = nullptr, *ac1 = nullptr, *ac2 = nullptr;
+  for (int c = 0; c < ncomp; ++c)
+    if (F[8 + c] < 0 || F[8 + c] >= n_huff || F[11 + c] < 0 || F[11 + c] >= n_huff) return;
+  dc0 = tabs + F[8];
+  ac0 = tabs + F[11];
+  if (ncomp == 3) {
+    dc1 = tabs + F[9];
+    dc2 = tabs + F[10];
+    ac1 = tabs + F[12];
+    ac2 = tabs + F[13];
+  }
+  const long base0 = F[17], base1 = F[18], base2 = F[19];
+  const int bw0 = mcux * hs;
+  BitReader br;
+  br.init(reinterpret_cast<const uint4*>(words), w0 >> 2, ng, 8L * nbytes);
+  int p0 = 0, p1 = 0, p2 = 0;  // DC predictors, reset at every interval start
+  for (int m = m0; m < m0 + nm; ++m) {
+    const int my = m / mcux, mx = m - my * mcux;
+    for (int by = 0; by < vs; ++by)
+      for (int bx = 0; bx < hs; ++bx)
+        decode_block(br, dc0, ac0, p0, coef + (base0 + (long)(my * vs + by) * bw0 + mx * hs + bx) * 64, nat);
+    if (ncomp == 3) {
+      const long cb = (long)my * mcux + mx;
+      decode_block(br, dc1, ac1, p1, coef + (base1 + cb) * 64, nat);
+      decode_block(br, dc2, ac2, p2, coef + (base2 + cb) * 64, nat);
+    }
+    if (br.left < 0) break;  // this MCU read past the data: the rest of the interval stays zero (uniform grey), as in decode_mcu
+  }
+}
+
+// the device frame whose first entry (word `word` of its row, an int32 or the low word of an int64) is the last one <= key
+__device__ __forceinline__ int find_frame(const int* fr, int n_fr, long key, bool wide, int word) {
+  int lo = 0, hi = n_fr - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    const int* F = fr + (long)mid * kFrameWords;
+    const long v = wide ? frame_long(F, word) : (long)F[word];
+    if (v <= key) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void jpeg_idct_kernel(const short* __restrict__ coef, unsigned char* __restrict__ planes, long blocks,
+                                                        const int* __restrict__ fr, int n_fr, const int* __restrict__ quant,
+                                                        int n_quant) {
+  const long gb = (long)blockIdx.x * 256 + threadIdx.x;
+  if (gb >= blocks || n_fr <= 0) return;
+  const int* F = fr + (long)find_frame(fr, n_fr, gb, false, 17) * kFrameWords;
+  if (!frame_ok(F, blocks)) return;
+  const int ncomp = F[2], hs = F[3], vs = F[4], mcux = F[5], mcuy = F[6];
+  const int c = ncomp == 3 ? (gb >= F[19] ? 2 : (gb >= F[18] ? 1 : 0)) : 0;
+  const int bw = c == 0 ? mcux * hs : mcux, bh = c == 0 ? mcuy * vs : mcuy;
+  const long local = gb - F[17 + c];
+  if (local < 0 || local >= (long)bw * bh) return;  // (a block between frames: nobody's)
+  const int q = F[14 + c];
+  if (q < 0 || q >= n_quant) return;
+  const int* Q = quant + q * 64;
+  int v[64];
+  const int4* src = reinterpret_cast<const int4*>(coef + gb * 64);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int4 x = src[j];
+    const int e[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (int h = 0; h < 4; ++h) {
+      v[8 * j + 2 * h] = (int)(short)(e[h] & 0xFFFF) * Q[8 * j + 2 * h];
+      v[8 * j + 2 * h + 1] = (int)(short)((unsigned)e[h] >> 16) * Q[8 * j + 2 * h + 1];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 8; ++k) jidct8(v + k, 8, true);
+#pragma unroll
+  for (int r = 0; r < 8; ++r) jidct8(v + 8 * r, 1, false);
+  const long by = local / bw, bx = local - by * bw;
+  unsigned char* dst = planes + (long)F[17 + c] * 64 + by * 8 * (bw * 8) + bx * 8;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    unsigned lo = 0, hi = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      int s = v[8 * r + k] + 128;
+      s = s < 0 ? 0 : (s > 255 ? 255 : s);
+      if (k < 4) lo |= (unsigned)s << (8 * k);
+      else hi |= (unsigned)s << (8 * (k - 4));
+    }
+    *reinterpret_cast<uint2*>(dst + (long)r * bw * 8) = make_uint2(lo, hi);
+  }
+}
+
+// one chroma sample at output pixel (x, y): jdsample.c h2v1 / h2v2 fancy upsampling (dw > 2) or replication; p: the plane
+// (pitch pw), dw / dh: downsampled_width / height
+__device__ __forceinline__ int chroma_at(const unsigned char* p, int pw, int x, int y, int hs, int vs, int dw, int dh) {
+  if (hs == 1) return p[(long)y * pw + x];
+  const int i = x >> 1;
+  const bool odd = x & 1;
+  if (dw <= 2) return p[(long)(vs == 2 ? y >> 1 : y) * pw + i];
+  const int i2 = odd ? min(i + 1, dw - 1) : max(i - 1, 0);
+  if (vs == 1) {
+    const unsigned char* row = p + (long)y * pw;
+    return (3 * row[i] + row[i2] + (odd ? 2 : 1)) >> 2;
+  }
+  const int r = y >> 1, r2 = (y & 1) ? min(r + 1, dh - 1) : max(r - 1, 0);
+  const unsigned char* a = p + (long)r * pw;
+  const unsigned char* b = p + (long)r2 * pw;
+  const int s1 = 3 * a[i] + b[i], s2 = 3 * a[i2] + b[i2];
+  return (3 * s1 + s2 + (odd ? 7 : 8)) >> 4;
+}
+
+__global__ __launch_bounds__(256) void jpeg_color_kernel(const unsigned char* __restrict__ planes, long blocks, const int* __restrict__ fr,
+                                                         int n_fr, long pixels, unsigned char* __restrict__ out, long out_bytes) {
+  const long gp = (long)blockIdx.x * 256 + threadIdx.x;
+  if (gp >= pixels || n_fr <= 0) return;
+  const int* F = fr + (long)find_frame(fr, n_fr, gp, true, 22) * kFrameWords;
+  if (!frame_ok(F, blocks)) return;
+  const int H = F[0], W = F[1], ncomp = F[2], hs = F[3], vs = F[4], mcux = F[5], mcuy = F[6];
+  const long local = gp - frame_long(F, 22), o = frame_long(F, 20);
+  if (local < 0 || local >= (long)H * W || o < 0 || o + (long)H * W * 3 > out_bytes) return;
+  const int y = (int)(local / W), x = (int)(local - (long)y * W);
+  const int yy = planes[(long)F[17] * 64 + (long)y * (mcux * hs * 8) + x];
+  int r = yy, g = yy, b = yy;
+  if (ncomp == 3) {
+    const int pw = mcux * 8, dw = (W + hs - 1) / hs, dh = (H + vs - 1) / vs;
+    (void)mcuy;
+    const int cb = chroma_at(planes + (long)F[18] * 64, pw, x, y, hs, vs, dw, dh) - 128;
+    const int cr = chroma_at(planes + (long)F[19] * 64, pw, x, y, hs, vs, dw, dh) - 128;
+    r = yy + ((91881 * cr + 32768) >> 16);
+    g = yy + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
+    b = yy + ((116130 * cb + 32768) >> 16);
+  }
+  unsigned char* d = out + o + local * 3;
+  d[0] = (unsigned char)(r < 0 ? 0 : (r > 255 ? 255 : r));
+  d[1] = (unsigned char)(g < 0 ? 0 : (g > 255 ? 255 : g));
+  d[2] = (unsigned char)(b < 0 ? 0 : (b > 255 ? 255 : b));
+}
+
+// blockIdx.y: the fallback frame; table row (source offset, output offset, bytes)
+__global__ __launch_bounds__(256) void jpeg_copy_kernel(const unsigned char* __restrict__ src, long src_bytes,
+                                                        const long long* __restrict__ tab, unsigned char* __restrict__ out,
+                                                        long out_bytes) {
+  const long long* T = tab + (long)blockIdx.y * 3;
+  const long s = T[0], d = T[1], n = T[2];
+  if (s < 0 || d < 0 || n < 0 || s + n > src_bytes || d + n > out_bytes) return;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) out[d + i] = src[s + i];
+}
+
+}  // namespace
+
+extern "C" int pm_jpeg_decode(const unsigned char* entropy, long entropy_bytes, const int* intervals, int n_intervals,
+                              const int* frames, int n_frames, const unsigned char* huff, int n_huff, const int* quant, int n_quant,
+                              const unsigned char* fallback, long fallback_bytes, const long long* fallback_table, int n_fallback,
+                              short* coef, unsigned char* planes, long blocks, long pixels, unsigned char* out, long out_bytes,
+                              void* stream) {
+  if (n_intervals < 0 || n_frames < 0 || n_huff < 0 || n_quant < 0 || n_fallback < 0 || n_fallback > 65535 || entropy_bytes < 0 ||
+      fallback_bytes < 0 || blocks < 0 || pixels < 0 || out_bytes < 0)
+    return PM_ESHAPE;
+  if (entropy_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(entropy) % 16 != 0) return PM_EALIGN;
+  if ((n_frames > 0 || n_fallback > 0) && !out) return PM_EINVAL;
+  if (n_frames > 0 && (!frames || (n_intervals > 0 && (!intervals || !entropy || !huff)) || (blocks > 0 && (!coef || !planes || !quant))))
+    return PM_EINVAL;
+  if (n_fallback > 0 && (!fallback_table || (fallback_bytes > 0 && !fallback))) return PM_EINVAL;
+  hipStream_t s = pm_stream(stream);
+  if (n_frames > 0 && blocks > 0) {
+    if (hipMemsetAsync(coef, 0, (size_t)blocks * 64 * sizeof(short), s) != hipSuccess) return PM_ELAUNCH;
+    if (n_intervals > 0) {
+      const dim3 grid((n_intervals + 63) / 64);
+      const HuffTable* t = reinterpret_cast<const HuffTable*>(huff);
+      const unsigned* w = reinterpret_cast<const unsigned*>(entropy);
+      if (n_huff <= kLdsTables)
+        hipLaunchKernelGGL(jpeg_huff_kernel<true>, grid, dim3(64), 0, s, w, entropy_bytes / 4, intervals, n_intervals, frames,
+                           n_frames, t, n_huff, coef, blocks);
+      else
+        hipLaunchKernelGGL(jpeg_huff_kernel<false>, grid, dim3(64), 0, s, w, entropy_bytes / 4, intervals, n_intervals, frames,
+                           n_frames, t, n_huff, coef, blocks);
+    }
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, s, coef, planes, blocks, frames,
+                       n_frames, quant, n_quant);
+    if (pixels > 0)
+      hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, planes, blocks, frames, n_frames,
+                         pixels, out, out_bytes);
+  }
+  if (n_fallback > 0)
+    hipLaunchKernelGGL(jpeg_copy_kernel, dim3(64, n_fallback), dim3(256), 0, s, fallback, fallback_bytes, fallback_table, out,
+                       out_bytes);
+  if (hipGetLastError() != hipSuccess) return PM_ELAUNCH;
+  return PM_OK;
+}

@@ -667,6 +667,44 @@ class DevicePerturber:
         return out
 
 
+class DeviceJpegDecoder:
+    """Baseline JPEG decoding on the device (pm_jpeg_decode, csrc/pm_jpeg.hip): `__call__(batch)` takes a jpeg.JpegBatch that is on
+    the device and returns, on the current stream, the RaggedFrames that RaggedFrames.from_frames([folder.pil_loader(f) for f in
+    files]) gives -- `data`, `offset` and `hw` byte for byte.  Frames the device does not decode were decoded by the packer on the
+    host and are copied into their slots.  The coefficient / plane workspace and the output only grow; the returned frames live in
+    the output buffer until the next call enqueues its decode."""
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self._bufs = {}
+
+    def _grow(self, name, n: int, dtype) -> torch.Tensor:
+        t = self._bufs.get(name)
+        if t is None or t.numel() < n:
+            t = self._bufs[name] = torch.empty(max(int(n), 1), dtype=dtype, device=self.device)
+        return t
+
+    def __call__(self, batch) -> RaggedFrames:
+        from .jpeg import JpegBatch
+        if not isinstance(batch, JpegBatch):
+            raise TypeError("DeviceJpegDecoder takes a jpeg.JpegBatch")
+        if not batch.is_cuda:
+            raise _lib.PolypMaeError("DeviceJpegDecoder runs on the GPU only (no CPU fallback): move the JpegBatch to the device first")
+        m, t = batch.meta, batch.t
+        coef = self._grow("coef", m["blocks"] * 64, torch.int16)
+        planes = self._grow("planes", m["blocks"] * 64, torch.uint8)
+        out = self._grow("out", m["nbytes"], torch.uint8)
+        ptr = lambda x: x.data_ptr() if x.numel() else None
+        lib = _lib.load()
+        _lib.check(lib.pm_jpeg_decode(ptr(t["entropy"]), t["entropy"].numel(), ptr(t["intervals"]), t["intervals"].shape[0],
+                                      ptr(t["frames"]), t["frames"].shape[0], ptr(t["huff"]), t["huff"].shape[0], ptr(t["quant"]),
+                                      t["quant"].shape[0], ptr(t["fallback"]), t["fallback"].numel(), ptr(t["fallback_table"]),
+                                      t["fallback_table"].shape[0], coef.data_ptr(), planes.data_ptr(), m["blocks"], m["pixels"],
+                                      out.data_ptr(), m["nbytes"], torch.cuda.current_stream(self.device).cuda_stream),
+                   "pm_jpeg_decode")
+        return RaggedFrames(out[:m["nbytes"]], t["offset"], t["hw"], _host=(m["offset"], m["hw"]))
+
+
 class DevicePrefetcher:
     """Wraps a loader that yields (frames, *rest) -- frames uint8 [B,H,W,3] or a RaggedFrames of mixed sizes, on the host --:
     copies batch i+1 to the device on a side stream (pinned staging, two slots) while batch i is consumed, and yields (imgs
@@ -688,7 +726,9 @@ class DevicePrefetcher:
         resized crop (pm_aug_resized_crop_ragged_u8: the Resize of "train" is a crop with the whole frame as its box) brings every
         frame to S x S on the device, and the rest of the chain is the uniform one.  The pinned and device staging buffers of a
         ragged batch are sized in bytes, kept per slot and only ever grow; a batch that arrives pinned (DataLoader(pin_memory=True))
-        is copied from where it lies.  Uniform [B, H, W, 3] batches keep their own path (and, without `augment`, the fused
+        is copied from where it lies.  A batch of compressed files (jpeg.JpegBatch, `folder_loader(..., decode="device")`) is
+        staged the same way, one copy per array, and decoded on the copy stream (DeviceJpegDecoder) into the RaggedFrames the
+        ragged path then takes.  Uniform [B, H, W, 3] batches keep their own path (and, without `augment`, the fused
         flips + ToTensor + Normalize of pm_preprocess_u8 only).
         stream: where the copies and the transform run -- "own": a stream of the prefetcher (a fourth busy stream beside the
         engine's three: one hardware queue each, fastest on a single GPU); "side": the engine's weight-gradient stream (idle
@@ -710,6 +750,9 @@ class DevicePrefetcher:
         self._dev = [None, None]        # per slot: (uint8 frames, float32 images) on the device
         self._ragged_pin = [None, None]  # per slot, ragged batches: pinned (bytes, offset, hw), grow-only
         self._ragged_dev = [None, None]  # per slot, ragged batches: device (bytes, offset, hw), grow-only
+        self._jpeg_pin = [None, None]    # per slot, compressed batches: pinned arrays by name, grow-only
+        self._jpeg_dev = [None, None]    # per slot, compressed batches: device arrays by name, grow-only
+        self._decoder: Optional[DeviceJpegDecoder] = None
         self._consumed = [None, None]   # per slot: event recorded on the consumer's stream after it used the batch
         self._slot_copied = [None, None]  # per slot: event after the slot's host-to-device copies were enqueued
         self._stream: Optional[torch.cuda.Stream] = None
@@ -746,11 +789,35 @@ class DevicePrefetcher:
             d[:h.numel()].copy_(h, non_blocking=True)
         return RaggedFrames(dev[0][:nbytes], dev[1][:B], dev[2][:2 * B].view(B, 2), _host=frames._host)
 
+    def _stage_jpeg(self, slot: int, batch) -> RaggedFrames:
+        """A jpeg.JpegBatch: one host-to-device copy per array into this slot's grow-only buffers (as _stage_ragged), then the
+        decode (DeviceJpegDecoder) on the copy stream.  Called on the copy stream."""
+        from .jpeg import JpegBatch
+        pin_bufs = self._jpeg_pin[slot] = self._jpeg_pin[slot] or {}
+        dev_bufs = self._jpeg_dev[slot] = self._jpeg_dev[slot] or {}
+        pinned = batch.is_pinned()
+        staged = {}
+        for name, t in batch.t.items():
+            n = t.numel()
+            src = t.reshape(-1)
+            if not pinned:
+                pin_bufs[name] = self._grown(pin_bufs.get(name), max(n, 1), t.dtype)
+                src = pin_bufs[name][:n]
+                src.copy_(t.reshape(-1))
+            dev_bufs[name] = self._grown(dev_bufs.get(name), max(n, 1), t.dtype, device=self.device)
+            d = dev_bufs[name][:n]
+            d.copy_(src, non_blocking=True)
+            staged[name] = d.view(t.shape)
+        if self._decoder is None:
+            self._decoder = DeviceJpegDecoder(self.device)
+        return self._decoder(JpegBatch(staged, batch.meta))
+
     def _stage(self, slot: int, batch) -> Tuple:
+        from .jpeg import JpegBatch
         frames, rest = batch[0], tuple(batch[1:])
-        if isinstance(frames, RaggedFrames):
+        if isinstance(frames, (RaggedFrames, JpegBatch)):
             if self.augment is None:
-                raise ValueError("a RaggedFrames batch needs a DeviceAugmenter (augment=...) to bring its frames to one size")
+                raise ValueError("a RaggedFrames or JpegBatch batch needs a DeviceAugmenter (augment=...) to bring its frames to one size")
             S = self.augment.size
             bufs = self._dev[slot]
             if bufs is None or bufs[1].shape != (len(frames), 3, S, S):
@@ -760,7 +827,7 @@ class DevicePrefetcher:
             with torch.cuda.stream(self._stream):
                 if self._consumed[slot] is not None:
                     self._stream.wait_event(self._consumed[slot])
-                x = self._stage_ragged(slot, frames)
+                x = self._stage_ragged(slot, frames) if isinstance(frames, RaggedFrames) else self._stage_jpeg(slot, frames)
                 if self.transform == "mae":
                     imgs = self.augment.mae_transform(x, generator=self.generator, out=bufs[1])
                 else:

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from .data import RaggedFrames
+from .jpeg import JpegBatch
 
 # torchvision.datasets.folder.IMG_EXTENSIONS
 IMG_EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")
@@ -54,10 +55,13 @@ def pil_loader(path: str) -> np.ndarray:
 
 
 class ImageFolderFrames(torch.utils.data.Dataset):
-    """torchvision.datasets.ImageFolder(root) without a transform: item i = (decoded RGB frame uint8 [H, W, 3], class index)."""
+    """torchvision.datasets.ImageFolder(root) without a transform: item i = (decoded RGB frame uint8 [H, W, 3], class index).
+    decode="device": item i = (the file's bytes, class index) -- decoding is left to data.DeviceJpegDecoder (see jpeg_collate)."""
 
-    def __init__(self, root: str):
-        self.root = os.fspath(root)
+    def __init__(self, root: str, decode: str = "host"):
+        if decode not in ("host", "device"):
+            raise ValueError("decode must be 'host' or 'device'")
+        self.root, self.decode = os.fspath(root), decode
         self.classes, self.class_to_idx = find_classes(self.root)
         self.samples = make_dataset(self.root, self.class_to_idx)
         self.targets = [t for _, t in self.samples]
@@ -67,6 +71,9 @@ class ImageFolderFrames(torch.utils.data.Dataset):
 
     def __getitem__(self, i: int):
         path, target = self.samples[i]
+        if self.decode == "device":
+            with open(path, "rb") as f:
+                return f.read(), target
         return pil_loader(path), target
 
 
@@ -76,14 +83,22 @@ def ragged_collate(items) -> Tuple[RaggedFrames, torch.Tensor]:
     return RaggedFrames.from_frames(frames), torch.tensor(labels, dtype=torch.int64)
 
 
+def jpeg_collate(items) -> Tuple[JpegBatch, torch.Tensor]:
+    """[(file bytes, label), ...] -> (jpeg.JpegBatch, labels int64 [B]): baseline JPEGs packed for the device decoder, every other
+    file decoded here as pil_loader does."""
+    files, labels = zip(*items)
+    return JpegBatch.from_bytes(files), torch.tensor(labels, dtype=torch.int64)
+
+
 def folder_loader(root: str, batch_size: int, world: int = 1, rank: int = 0, seed: int = 0, num_workers: int = 10,
-                  pin_memory: bool = True) -> torch.utils.data.DataLoader:
+                  pin_memory: bool = True, decode: str = "host") -> torch.utils.data.DataLoader:
     """The reference's pre-training loader over ImageFolder(root) (main_pretrain.py:170-190): DistributedSampler(num_replicas=world,
     rank=rank, shuffle=True, seed=seed), drop_last=True.  Batches are (RaggedFrames, labels); call `loader.sampler.set_epoch(e)`
     once per epoch.  Workers only decode: they are spawned (never forked from a process that has opened the device) and kept
-    alive across epochs."""
-    ds = ImageFolderFrames(root)
+    alive across epochs.  decode="device": the workers only read and pack the files, batches are (jpeg.JpegBatch, labels), and
+    data.DevicePrefetcher decodes them on the device into the same RaggedFrames."""
+    ds = ImageFolderFrames(root, decode=decode)
     sampler = torch.utils.data.DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=True, seed=seed)
     extra = {"multiprocessing_context": "spawn", "persistent_workers": True} if num_workers > 0 else {}
     return torch.utils.data.DataLoader(ds, batch_size=batch_size, sampler=sampler, num_workers=num_workers, pin_memory=pin_memory,
-                                       drop_last=True, collate_fn=ragged_collate, **extra)
+                                       drop_last=True, collate_fn=jpeg_collate if decode == "device" else ragged_collate, **extra)

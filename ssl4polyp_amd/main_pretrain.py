@@ -10,8 +10,9 @@ behaviour: lr = blr * batch_size * accum_iter * world / 256 (:201-204), AdamW(be
 Data (main_pretrain.py:156-190): `--data_path DIR` trains on the image folder DIR/train (DIR itself with `--no_train_dir`, as for
 Hyperkvasir-unlabelled) through folder.folder_loader -- ImageFolder discovery, DistributedSampler(shuffle, seed), drop_last,
 `--num_workers` spawned workers that only decode, `--pin_mem` -- and the MAE transform (RandomResizedCrop(bicubic), flip,
-ToTensor, Normalize) on the device per frame at its native size (data.DevicePrefetcher(transform="mae")).  `--synthetic N`
-instead runs N device-resident Hyperkvasir-shaped batches per epoch; `run(args, data_loader)` takes any iterable of
+ToTensor, Normalize) on the device per frame at its native size (data.DevicePrefetcher(transform="mae")); `--decode device`
+leaves the workers reading and packing files and decodes baseline JPEGs on the device too (slower end to end today).
+`--synthetic N` instead runs N device-resident Hyperkvasir-shaped batches per epoch; `run(args, data_loader)` takes any iterable of
 (images, _) batches.  Without a folder at the data path and without --synthetic there is no data and the command exits.
 
     python -m ssl4polyp_amd.main_pretrain --data_path /data/hyperkvasir-unlabelled --no_train_dir --batch_size 64
@@ -59,6 +60,9 @@ def get_args_parser():
     p.add_argument("--pin_mem", action="store_true", help="pin CPU memory in the DataLoader")
     p.add_argument("--no_pin_mem", action="store_false", dest="pin_mem")
     p.set_defaults(pin_mem=True)
+    p.add_argument("--decode", default="host", choices=["host", "device"],
+                   help="where --data_path JPEGs are decoded: 'device' = the workers only read and pack the files, baseline JPEGs "
+                        "are decoded on the GPU bit for bit as Pillow does (others still on the host)")
     p.add_argument("--synthetic", default=0, type=int, help="number of synthetic batches per epoch (instead of --data_path)")
     p.add_argument("--save_every", default=1, type=int)
     p.add_argument("--log_every", default=20, type=int)
@@ -99,7 +103,8 @@ def run(args, data_loader=None):
                                  "run(args, data_loader)")
             from .data import DeviceAugmenter, DevicePrefetcher
             from .folder import folder_loader
-            loader = folder_loader(data_dir, args.batch_size, world, rank, args.seed, args.num_workers, args.pin_mem)
+            loader = folder_loader(data_dir, args.batch_size, world, rank, args.seed, args.num_workers, args.pin_mem,
+                                   decode=args.decode)
             sampler = loader.sampler
             data_loader = DevicePrefetcher(loader, device, augment=DeviceAugmenter(device, size=args.input_size), transform="mae",
                                            generator=torch.Generator().manual_seed(args.seed + rank))
