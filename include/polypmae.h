@@ -336,7 +336,8 @@ int pm_aug_jpeg_roundtrip_u8(const unsigned char* src, unsigned char* dst, const
  * host decoded itself (fallback) are copied to their slots.
  *   entropy: the unstuffed restart intervals, each on a 16-byte boundary, zero-padded; 16-byte aligned, entropy_bytes a multiple
  *     of 16.
- *   intervals int32 [n_intervals][8] = (frame, word offset, byte length, first MCU, MCU count, 0, 0, 0).
+ *   intervals int32 [n_intervals][8] = (frame, word offset, byte length, first MCU, MCU count, first subsequence, 0, 0); word 5
+ *     is read by pm_jpeg_decode_parallel only.
  *   frames int32 [n_frames][32] = (H, W, components, luma h / v sampling, MCU columns / rows, restart interval, DC / AC /
  *     quantisation table per component, first coefficient block per component, output byte offset lo / hi, first pixel lo / hi).
  *   huff [n_huff][1024]: derived Huffman tables (jpeg.py derive_huffman); quant int32 [n_quant][64], natural order.
@@ -347,6 +348,26 @@ int pm_jpeg_decode(const unsigned char* entropy, long entropy_bytes, const int* 
                    int n_frames, const unsigned char* huff, int n_huff, const int* quant, int n_quant, const unsigned char* fallback,
                    long fallback_bytes, const long long* fallback_table, int n_fallback, short* coef, unsigned char* planes,
                    long blocks, long pixels, unsigned char* out, long out_bytes, void* stream);
+
+/* pm_jpeg_decode with the entropy stage parallel INSIDE a restart interval (files without restart markers are one interval): same
+ * arguments, same bytes in `out`.  The host cuts every interval from its start into ceil(byte length / 128) subsequences numbered
+ * through the interval rows in order: word 5 of an interval row is its first subsequence (the exclusive scan of the counts) and
+ * subseq int32 [n_subseq] names the row of every subsequence.  One lane per subsequence decodes from a guessed state; the guesses
+ * are corrected inside a 256-lane workgroup and, over `sync_rounds` (0..8) further launches, across workgroups; an interval is
+ * accepted only if every lane's entry state equals its predecessor's exit state (which proves them the sequential decoder's
+ * states); every other interval is decoded by one lane as in pm_jpeg_decode.  Nothing is read back and nothing waits on another
+ * workgroup: 1 + sync_rounds + 3 launches replace the one of pm_jpeg_decode.
+ *   workspace: 16-byte aligned, at least pm_jpeg_decode_workspace(n_intervals, n_subseq, &bytes) bytes; its contents on entry do
+ *     not matter.  A smaller one is PM_EINVAL.
+ *   stats (optional, device): int32 [5] = subsequences, intervals, intervals decoded sequentially, in-workgroup steps of the busiest
+ *     workgroup, cross-workgroup rounds in which an entry changed. */
+int pm_jpeg_decode_workspace(int n_intervals, int n_subseq, size_t* bytes);
+int pm_jpeg_decode_parallel(const unsigned char* entropy, long entropy_bytes, const int* intervals, int n_intervals, const int* frames,
+                            int n_frames, const unsigned char* huff, int n_huff, const int* quant, int n_quant,
+                            const unsigned char* fallback, long fallback_bytes, const long long* fallback_table, int n_fallback,
+                            short* coef, unsigned char* planes, long blocks, long pixels, unsigned char* out, long out_bytes,
+                            const int* subseq, int n_subseq, int sync_rounds, void* workspace, size_t ws_bytes, int* stats,
+                            void* stream);
 
 /* One transformer block forward for one range of samples in ONE call (timm Block: models_mae.py:39-41,53-55,166-167,
  * 186-187; models.py:122-123,204-205):  x_mid = x + proj(attn(LN1 x));  x_out = x_mid + fc2(gelu(fc1(LN2 x_mid))).

@@ -59,6 +59,8 @@ SIGNATURES = {
     "pm_aug_occlude_u8": [P, P, I, I, I, P],
     "pm_aug_jpeg_roundtrip_u8": [P, P, P, I, I, I, P],
     "pm_jpeg_decode": [P, L, P, I, P, I, P, I, P, I, P, L, P, I, P, P, L, L, P, L, P],
+    "pm_jpeg_decode_parallel": [P, L, P, I, P, I, P, I, P, I, P, L, P, I, P, P, L, L, P, L, P, I, I, P, ctypes.c_size_t, P, P],
+    "pm_jpeg_decode_workspace": [I, I, P],
     "pm_comm_unique_id": [P],
     "pm_comm_create": [P, P, I, I],
     "pm_comm_world": [P, P, P],

@@ -15,6 +15,7 @@ frame where it lies (`pm_aug_resized_crop_ragged_u8`); the folder dataset and it
 from __future__ import annotations
 
 import concurrent.futures
+import ctypes
 import os
 from typing import Iterable, Iterator, Optional, Sequence, Tuple
 
@@ -668,14 +669,24 @@ class DevicePerturber:
 
 
 class DeviceJpegDecoder:
-    """Baseline JPEG decoding on the device (pm_jpeg_decode, csrc/pm_jpeg.hip): `__call__(batch)` takes a jpeg.JpegBatch that is on
-    the device and returns, on the current stream, the RaggedFrames that RaggedFrames.from_frames([folder.pil_loader(f) for f in
-    files]) gives -- `data`, `offset` and `hw` byte for byte.  Frames the device does not decode were decoded by the packer on the
-    host and are copied into their slots.  The coefficient / plane workspace and the output only grow; the returned frames live in
-    the output buffer until the next call enqueues its decode."""
+    """Baseline JPEG decoding on the device (csrc/pm_jpeg.hip): `__call__(batch)` takes a jpeg.JpegBatch that is on the device and
+    returns, on the current stream, the RaggedFrames that RaggedFrames.from_frames([folder.pil_loader(f) for f in files]) gives --
+    `data`, `offset` and `hw` byte for byte.  Frames the device does not decode were decoded by the packer on the host and are
+    copied into their slots.  The coefficient / plane workspace and the output only grow; the returned frames live in the output
+    buffer until the next call enqueues its decode.
+    mode="parallel" (pm_jpeg_decode_parallel): one lane per 128-byte subsequence of a restart interval, self-synchronising, with
+    `sync_rounds` correction launches across workgroups; an interval whose lanes are not proven synchronised is decoded by one lane.
+    mode="interval" (pm_jpeg_decode): one lane per restart interval.  Both return the same bytes.  `stats()` reads the counters
+    of the last parallel call (one device read: tests and logging only)."""
+    STATS = ("subsequences", "intervals", "sequential_intervals", "max_workgroup_steps", "rounds_changed")
 
-    def __init__(self, device):
+    def __init__(self, device, mode: str = "parallel", sync_rounds: int = 2):
+        if mode not in ("parallel", "interval"):
+            raise ValueError("mode must be 'parallel' or 'interval'")
+        if not 0 <= int(sync_rounds) <= 8:
+            raise ValueError("sync_rounds must be in 0..8")
         self.device = torch.device(device)
+        self.mode, self.sync_rounds = mode, int(sync_rounds)
         self._bufs = {}
 
     def _grow(self, name, n: int, dtype) -> torch.Tensor:
@@ -683,6 +694,13 @@ class DeviceJpegDecoder:
         if t is None or t.numel() < n:
             t = self._bufs[name] = torch.empty(max(int(n), 1), dtype=dtype, device=self.device)
         return t
+
+    def stats(self) -> dict:
+        """The counters of the last mode="parallel" call (synchronises with the device)."""
+        t = self._bufs.get("stats")
+        if t is None:
+            raise _lib.PolypMaeError("DeviceJpegDecoder.stats(): no mode='parallel' call has been made")
+        return dict(zip(self.STATS, t[:len(self.STATS)].tolist()))
 
     def __call__(self, batch) -> RaggedFrames:
         from .jpeg import JpegBatch
@@ -696,12 +714,21 @@ class DeviceJpegDecoder:
         out = self._grow("out", m["nbytes"], torch.uint8)
         ptr = lambda x: x.data_ptr() if x.numel() else None
         lib = _lib.load()
-        _lib.check(lib.pm_jpeg_decode(ptr(t["entropy"]), t["entropy"].numel(), ptr(t["intervals"]), t["intervals"].shape[0],
-                                      ptr(t["frames"]), t["frames"].shape[0], ptr(t["huff"]), t["huff"].shape[0], ptr(t["quant"]),
-                                      t["quant"].shape[0], ptr(t["fallback"]), t["fallback"].numel(), ptr(t["fallback_table"]),
-                                      t["fallback_table"].shape[0], coef.data_ptr(), planes.data_ptr(), m["blocks"], m["pixels"],
-                                      out.data_ptr(), m["nbytes"], torch.cuda.current_stream(self.device).cuda_stream),
-                   "pm_jpeg_decode")
+        args = (ptr(t["entropy"]), t["entropy"].numel(), ptr(t["intervals"]), t["intervals"].shape[0], ptr(t["frames"]),
+                t["frames"].shape[0], ptr(t["huff"]), t["huff"].shape[0], ptr(t["quant"]), t["quant"].shape[0], ptr(t["fallback"]),
+                t["fallback"].numel(), ptr(t["fallback_table"]), t["fallback_table"].shape[0], coef.data_ptr(), planes.data_ptr(),
+                m["blocks"], m["pixels"], out.data_ptr(), m["nbytes"])
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        if self.mode == "interval":
+            _lib.check(lib.pm_jpeg_decode(*args, stream), "pm_jpeg_decode")
+        else:
+            n_sub = t["subseq"].numel()
+            need = ctypes.c_size_t(0)
+            _lib.check(lib.pm_jpeg_decode_workspace(t["intervals"].shape[0], n_sub, ctypes.byref(need)), "pm_jpeg_decode_workspace")
+            ws = self._grow("workspace", need.value, torch.uint8)
+            stats = self._grow("stats", 8, torch.int32)
+            _lib.check(lib.pm_jpeg_decode_parallel(*args, ptr(t["subseq"]), n_sub, self.sync_rounds, ws.data_ptr(), ws.numel(),
+                                                   stats.data_ptr(), stream), "pm_jpeg_decode_parallel")
         return RaggedFrames(out[:m["nbytes"]], t["offset"], t["hw"], _host=(m["offset"], m["hw"]))
 
 

@@ -12,7 +12,9 @@ markers into restart intervals that each start on a 16-byte boundary (one row pe
 MCU, MCU count; sorted by length so that the lanes of a wave finish together), one row per device frame, the Huffman tables of the
 batch (deduplicated, derived as jdhuff.c jpeg_make_d_derived_tbl does), its quantisation tables (deduplicated, natural order), the
 predecoded RGB bytes of the fallback frames, and the offset / size tables of the decoded `RaggedFrames` (packed back to back
-exactly as `RaggedFrames.from_frames` packs them).
+exactly as `RaggedFrames.from_frames` packs them).  For the decoding in parallel inside an interval (pm_jpeg_decode_parallel) every
+interval is cut from its start into ceil(length / SUBSEQ_BYTES) subsequences, numbered through the sorted rows: word 5 of a row is
+its first subsequence, and `subseq` names the row of every subsequence.
 """
 from __future__ import annotations
 
@@ -30,6 +32,7 @@ NATURAL_ORDER = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5
 HUFF_RECORD = 1024   # bytes per derived Huffman table (pm_jpeg.hip HuffTable)
 FRAME_WORDS = 32     # int32 words per frame row (pm_jpeg.hip kFrameWords)
 INTERVAL_WORDS = 8   # int32 words per interval row (pm_jpeg.hip kIntervalWords)
+SUBSEQ_BYTES = 128   # bytes per subsequence of an interval, one lane each in the parallel entropy stage (pm_jpeg.hip kSubBytes)
 
 
 class JpegFallback(Exception):
@@ -310,8 +313,10 @@ class JpegBatch:
     [16 k], intervals int32 [N, 8], frames int32 [F, 32], huff uint8 [T, 1024], quant int32 [Q, 64], fallback uint8 (the fallback
     frames' RGB bytes), fallback_table int64 [K, 3] (source offset, output offset, bytes), offset int64 [B], hw int32 [B, 2].
     `meta` is the host side: the RaggedFrames tables as numpy (`offset`, `hw`), the coefficient `blocks` and device `pixels` the
-    workspace follows, the decoded `nbytes` and the indices of the `fallback` frames."""
-    TENSORS = ("entropy", "intervals", "frames", "huff", "quant", "fallback", "fallback_table", "offset", "hw")
+    workspace follows, the decoded `nbytes`, the indices of the `fallback` frames and `n_subseq`.  intervals[:, 5] is the row's first
+    subsequence (the exclusive scan of ceil(byte length / SUBSEQ_BYTES) over the rows); subseq int32 [n_subseq] is the interval row
+    of every subsequence."""
+    TENSORS = ("entropy", "intervals", "frames", "huff", "quant", "fallback", "fallback_table", "offset", "hw", "subseq")
 
     def __init__(self, tensors: Dict[str, torch.Tensor], meta: dict):
         self.t = tensors
@@ -414,6 +419,12 @@ class JpegBatch:
         entropy = np.concatenate(chunks + [np.zeros(16, dtype=np.uint8)])
         iv = np.concatenate(iv_rows) if iv_rows else np.zeros((0, INTERVAL_WORDS), dtype=np.int64)
         iv = iv[np.argsort(-iv[:, 2], kind="stable")]   # longest first: the 64 lanes of a wave decode similar lengths
+        n_sub = (iv[:, 2] + SUBSEQ_BYTES - 1) // SUBSEQ_BYTES   # (an empty interval has none)
+        iv[:, 5] = np.cumsum(n_sub) - n_sub
+        total_sub = int(n_sub.sum())
+        if total_sub >= 2 ** 31:
+            raise ValueError("JpegBatch: the batch is too large for the device tables")
+        subseq = np.repeat(np.arange(len(iv), dtype=np.int32), n_sub)
         fb_ids = sorted(fb_frames)
         fb_sizes = np.array([fb_frames[b].size for b in fb_ids], dtype=np.int64)
         fb_table = np.zeros((len(fb_ids), 3), dtype=np.int64)
@@ -431,7 +442,8 @@ class JpegBatch:
              "fallback": torch.from_numpy(fallback),
              "fallback_table": torch.from_numpy(fb_table),
              "offset": torch.from_numpy(offset.copy()),
-             "hw": torch.from_numpy(hw.astype(np.int32))}
+             "hw": torch.from_numpy(hw.astype(np.int32)),
+             "subseq": torch.from_numpy(subseq)}
         meta = {"offset": offset, "hw": hw, "blocks": int(blocks), "pixels": int(pixels), "nbytes": int(nbytes.sum()),
-                "fallback": fb_ids}
+                "fallback": fb_ids, "n_subseq": total_sub}
         return cls(t, meta)

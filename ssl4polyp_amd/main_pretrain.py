@@ -11,7 +11,7 @@ Data (main_pretrain.py:156-190): `--data_path DIR` trains on the image folder DI
 Hyperkvasir-unlabelled) through folder.folder_loader -- ImageFolder discovery, DistributedSampler(shuffle, seed), drop_last,
 `--num_workers` spawned workers that only decode, `--pin_mem` -- and the MAE transform (RandomResizedCrop(bicubic), flip,
 ToTensor, Normalize) on the device per frame at its native size (data.DevicePrefetcher(transform="mae")); `--decode device`
-leaves the workers reading and packing files and decodes baseline JPEGs on the device too (slower end to end today).
+leaves the workers reading and packing files and decodes baseline JPEGs on the device too (DESIGN.md has the measured rates).
 `--synthetic N` instead runs N device-resident Hyperkvasir-shaped batches per epoch; `run(args, data_loader)` takes any iterable of
 (images, _) batches.  Without a folder at the data path and without --synthetic there is no data and the command exits.
 
