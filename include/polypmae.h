@@ -369,6 +369,32 @@ int pm_jpeg_decode_parallel(const unsigned char* entropy, long entropy_bytes, co
                             const int* subseq, int n_subseq, int sync_rounds, void* workspace, size_t ws_bytes, int* stats,
                             void* stream);
 
+/* The first two stages of pm_jpeg_decode_parallel alone: entropy decode + inverse DCT into the component planes (the same kernels,
+ * the same arguments without the fallback frames and the output).  No RGB frame is written; pm_jpeg_resized_crop_u8 reads the
+ * planes. */
+int pm_jpeg_decode_planes(const unsigned char* entropy, long entropy_bytes, const int* intervals, int n_intervals, const int* frames,
+                          int n_frames, const unsigned char* huff, int n_huff, const int* quant, int n_quant, short* coef,
+                          unsigned char* planes, long blocks, const int* subseq, int n_subseq, int sync_rounds, void* workspace,
+                          size_t ws_bytes, int* stats, void* stream);
+
+/* pm_aug_resized_crop_ragged_u8 of a decoded JPEG batch without its packed RGB frames: box [B][4] = (top, left, h, w) inside frame b
+ * of hw [B][2] -> dst [B][out][out][3].  The horizontal pass fetches every source pixel from the planes pm_jpeg_decode_planes left
+ * (fancy chroma upsampling + YCbCr -> RGB per fetched pixel, the arithmetic of pm_jpeg_decode's last stage) or, for a frame the host
+ * decoded, from its RGB bytes in `fallback`; the taps, the vertical pass and the workspace layout are those of
+ * pm_aug_resized_crop_ragged_u8, so the bytes equal decoding to RGB first and cropping then.
+ *   source int32 [B] (device): >= 0 the row of `frames` sample b is, -1 - k row k of fallback_table.
+ *   planes / blocks / frames / fallback / fallback_table: as in pm_jpeg_decode.
+ *   workspace: 16-byte aligned, at least pm_jpeg_resized_crop_workspace(B, Hmax, Wmax, out, &bytes) bytes (PM_EINVAL otherwise);
+ *   B <= 65535.  The tables are trusted as those of pm_aug_resized_crop_ragged_u8 are (the caller validates boxes against hw); the
+ *   horizontal pass additionally skips a sample whose tables do not fit together (a frame row outside `blocks`, a size that is not
+ *   hw[b], a box outside the frame, fallback bytes outside the buffer), so nothing outside the buffers is read -- but the vertical
+ *   pass still runs for it: dst[b] is then undefined (whatever the workspace held). */
+int pm_jpeg_resized_crop_workspace(int B, int Hmax, int Wmax, int out, size_t* bytes);
+int pm_jpeg_resized_crop_u8(const unsigned char* planes, long blocks, const int* frames, int n_frames, const unsigned char* fallback,
+                            long fallback_bytes, const long long* fallback_table, int n_fallback, const int* source, const int* hw,
+                            const int* box, unsigned char* dst, int bicubic, int B, int Hmax, int Wmax, int out, void* workspace,
+                            size_t ws_bytes, void* stream);
+
 /* One transformer block forward for one range of samples in ONE call (timm Block: models_mae.py:39-41,53-55,166-167,
  * 186-187; models.py:122-123,204-205):  x_mid = x + proj(attn(LN1 x));  x_out = x_mid + fc2(gelu(fc1(LN2 x_mid))).
  * Host-side composition of pm_layernorm_fwd / pm_gemm_ex / pm_attention_fwd on `stream`, launch for launch what a caller

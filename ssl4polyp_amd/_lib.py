@@ -61,6 +61,9 @@ SIGNATURES = {
     "pm_jpeg_decode": [P, L, P, I, P, I, P, I, P, I, P, L, P, I, P, P, L, L, P, L, P],
     "pm_jpeg_decode_parallel": [P, L, P, I, P, I, P, I, P, I, P, L, P, I, P, P, L, L, P, L, P, I, I, P, ctypes.c_size_t, P, P],
     "pm_jpeg_decode_workspace": [I, I, P],
+    "pm_jpeg_decode_planes": [P, L, P, I, P, I, P, I, P, I, P, P, L, P, I, I, P, ctypes.c_size_t, P, P],
+    "pm_jpeg_resized_crop_workspace": [I, I, I, I, P],
+    "pm_jpeg_resized_crop_u8": [P, L, P, I, P, L, P, I, P, P, P, P, I, I, I, I, I, P, ctypes.c_size_t, P],
     "pm_comm_unique_id": [P],
     "pm_comm_create": [P, P, I, I],
     "pm_comm_world": [P, P, P],

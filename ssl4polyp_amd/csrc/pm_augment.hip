@@ -159,6 +159,79 @@ __global__ __launch_bounds__(256) void resample_crop_kernel(const unsigned char*
   }
 }
 
+// the horizontal pass of resample_crop_kernel for a decoded JPEG batch (pm_jpeg_decode_planes), reading every source pixel where
+// the decoder left it: sample b = blockIdx.y takes its pixels from the component planes of frame row source[b] >= 0 (chroma
+// upsampling + YCbCr -> RGB per fetched pixel: pm_common.h jpeg_pixel_rgb, the arithmetic of pm_jpeg.hip's colour stage, in the
+// frame's own coordinates) or, source[b] = -1 - k, from the RGB bytes of row k of the fallback table (rows of W * 3 bytes).  No
+// full-size RGB frame exists.  The frame row, the box and the plane bases are wave-uniform; the lanes run along the output x of
+// one row, so neighbouring lanes read overlapping source windows.  A sample whose tables do not fit together (a frame row that
+// fails frame_ok, a size that is not hw[b], a box outside the frame, fallback bytes outside the buffer) reads and writes nothing here;
+// the vertical pass still runs over its rows of tmp, so its output is undefined (include/polypmae.h says so).
+__global__ __launch_bounds__(256) void resample_crop_jpeg_kernel(const unsigned char* __restrict__ planes, long blocks,
+                                                                 const int* __restrict__ fr, int n_fr,
+                                                                 const unsigned char* __restrict__ fallback, long fallback_bytes,
+                                                                 const long long* __restrict__ fb_table, int n_fb,
+                                                                 const int* __restrict__ source, const int* __restrict__ hw,
+                                                                 unsigned char* __restrict__ dst, const int* __restrict__ box,
+                                                                 const int* __restrict__ bounds, const int* __restrict__ taps, int ksize,
+                                                                 int Hs, int out_size) {
+  const int b = blockIdx.y;
+  const int top = box[4 * b], left = box[4 * b + 1], rows = box[4 * b + 2], cols = box[4 * b + 3];
+  const int H = hw[2 * b], W = hw[2 * b + 1];
+  if (top < 0 || left < 0 || rows <= 0 || cols <= 0 || rows > Hs || rows > H - top || cols > W - left) return;
+  const int sb = source[b];
+  const int* F = nullptr;
+  const unsigned char* rgb = nullptr;
+  if (sb >= 0) {
+    if (sb >= n_fr) return;
+    F = fr + (long)sb * kFrameWords;
+    if (!frame_ok(F, blocks) || F[0] != H || F[1] != W) return;
+  } else {
+    const long k = -1L - sb;
+    if (k >= n_fb) return;
+    const long s = fb_table[3 * k], n = fb_table[3 * k + 2];
+    if (s < 0 || n != (long)H * W * 3 || s + n > fallback_bytes) return;
+    rgb = fallback + s;
+  }
+  unsigned char* out = dst + (long)b * Hs * out_size * 3;
+  const long total = (long)rows * out_size;  // rows below the crop are never read
+  for (long id = (long)blockIdx.x * 256 + threadIdx.x; id < total; id += (long)gridDim.x * 256) {
+    const int xo = id % out_size;
+    const int y = top + (int)(id / out_size);
+    const long ti = (long)b * out_size + xo;
+    const int lo = bounds[2 * ti];
+    int n = bounds[2 * ti + 1];
+    if (lo < 0 || lo >= cols) n = 0;
+    else if (n > cols - lo) n = cols - lo;
+    const int* k = taps + ti * ksize;
+    int ss0 = 1 << (kPrecisionBits - 1), ss1 = ss0, ss2 = ss0;
+    if (F) {
+      for (int t = 0; t < n; ++t) {
+        int r, g, bl;
+        jpeg_pixel_rgb(planes, F, left + lo + t, y, r, g, bl);
+        const int kk = k[t];
+        ss0 += r * kk;
+        ss1 += g * kk;
+        ss2 += bl * kk;
+      }
+    } else {
+      const unsigned char* p = rgb + ((long)y * W + left + lo) * 3;
+      for (int t = 0; t < n; ++t) {
+        const int kk = k[t];
+        ss0 += p[0] * kk;
+        ss1 += p[1] * kk;
+        ss2 += p[2] * kk;
+        p += 3;
+      }
+    }
+    unsigned char* q = out + id * 3;
+    ss0 >>= kPrecisionBits; ss1 >>= kPrecisionBits; ss2 >>= kPrecisionBits;
+    q[0] = (unsigned char)(ss0 < 0 ? 0 : (ss0 > 255 ? 255 : ss0));
+    q[1] = (unsigned char)(ss1 < 0 ? 0 : (ss1 > 255 ? 255 : ss1));
+    q[2] = (unsigned char)(ss2 < 0 ? 0 : (ss2 > 255 ? 255 : ss2));
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // ColorJitter: four per-pixel ops in a per-sample order; contrast needs the image's mean luminance first
 // ---------------------------------------------------------------------------------------------
@@ -608,10 +681,25 @@ extern "C" size_t pm_aug_resized_crop_workspace_bytes(int B, int Hs, int Ws, int
   return tables + (size_t)B * Hs * out * 3 + 256;
 }
 
-// both resized-crop entries: offset == nullptr -> uniform frames [B][Hs][Ws]; otherwise packed frames no larger than Hs x Ws
+// where the horizontal pass of a decoded JPEG batch reads (resample_crop_jpeg_kernel)
+struct JpegSource {
+  const unsigned char* planes;
+  long blocks;
+  const int* frames;
+  int n_frames;
+  const unsigned char* fallback;
+  long fallback_bytes;
+  const long long* fallback_table;
+  int n_fallback;
+  const int* source;
+};
+
+// the resized-crop entries: offset == nullptr -> uniform frames [B][Hs][Ws]; otherwise packed frames no larger than Hs x Ws;
+// jpeg != nullptr -> the frames of a decoded JPEG batch where the decoder left them (src unused, hw their sizes)
 static int resized_crop_launch(const unsigned char* src, const long long* offset, const int* hw, const int* box, unsigned char* dst,
-                               int bicubic, int B, int Hs, int Ws, int out, void* workspace, size_t ws_bytes, void* stream) {
-  if (!src || !box || !dst || !workspace) return PM_EINVAL;
+                               int bicubic, int B, int Hs, int Ws, int out, void* workspace, size_t ws_bytes, void* stream,
+                               const JpegSource* jpeg = nullptr) {
+  if ((!src && !jpeg) || !box || !dst || !workspace) return PM_EINVAL;
   if (B <= 0 || Hs <= 0 || Ws <= 0 || out <= 0) return PM_ESHAPE;
   if (B > 65535) return PM_ESHAPE;  // (the sample is blockIdx.y)
   if (ws_bytes < pm_aug_resized_crop_workspace_bytes(B, Hs, Ws, out) || ((uintptr_t)workspace & 15)) return PM_EINVAL;
@@ -628,8 +716,13 @@ static int resized_crop_launch(const unsigned char* src, const long long* offset
   hipLaunchKernelGGL(resample_coeffs_kernel, dim3(gc), dim3(256), 0, s, box, 1, out, bicubic ? 1 : 0, ksize, bounds_y, taps_y, B);
   // the whole grid is capped as aug_grid caps a flat one: at most 8192 blocks over the B samples
   const int cap = 8192 / B > 1 ? 8192 / B : 1;
-  hipLaunchKernelGGL(resample_crop_kernel, dim3(aug_grid((long)Hs * out, cap), B), dim3(256), 0, s, src, tmp, box, bounds_x, taps_x,
-                     ksize, offset, hw, Hs, Ws, out, 0);
+  if (jpeg)
+    hipLaunchKernelGGL(resample_crop_jpeg_kernel, dim3(aug_grid((long)Hs * out, cap), B), dim3(256), 0, s, jpeg->planes, jpeg->blocks,
+                       jpeg->frames, jpeg->n_frames, jpeg->fallback, jpeg->fallback_bytes, jpeg->fallback_table, jpeg->n_fallback,
+                       jpeg->source, hw, tmp, box, bounds_x, taps_x, ksize, Hs, out);
+  else
+    hipLaunchKernelGGL(resample_crop_kernel, dim3(aug_grid((long)Hs * out, cap), B), dim3(256), 0, s, src, tmp, box, bounds_x, taps_x,
+                       ksize, offset, hw, Hs, Ws, out, 0);
   hipLaunchKernelGGL(resample_crop_kernel, dim3(aug_grid((long)out * out, cap), B), dim3(256), 0, s, tmp, dst, box, bounds_y, taps_y,
                      ksize, nullptr, nullptr, Hs, out, out, 1);
   return pm_check_launch();
@@ -645,6 +738,26 @@ extern "C" int pm_aug_resized_crop_ragged_u8(const unsigned char* src, const lon
                                              size_t ws_bytes, void* stream) {
   if (!offset || !hw) return PM_EINVAL;
   return resized_crop_launch(src, offset, hw, box, dst, bicubic, B, Hmax, Wmax, out, workspace, ws_bytes, stream);
+}
+
+extern "C" int pm_jpeg_resized_crop_workspace(int B, int Hmax, int Wmax, int out, size_t* bytes) {
+  if (B <= 0 || Hmax <= 0 || Wmax <= 0 || out <= 0 || B > 65535) return PM_ESHAPE;
+  if (!bytes) return PM_EINVAL;
+  *bytes = pm_aug_resized_crop_workspace_bytes(B, Hmax, Wmax, out);
+  return PM_OK;
+}
+
+extern "C" int pm_jpeg_resized_crop_u8(const unsigned char* planes, long blocks, const int* frames, int n_frames,
+                                       const unsigned char* fallback, long fallback_bytes, const long long* fallback_table,
+                                       int n_fallback, const int* source, const int* hw, const int* box, unsigned char* dst,
+                                       int bicubic, int B, int Hmax, int Wmax, int out, void* workspace, size_t ws_bytes,
+                                       void* stream) {
+  if (blocks < 0 || n_frames < 0 || n_fallback < 0 || fallback_bytes < 0) return PM_ESHAPE;
+  if (!source || !hw) return PM_EINVAL;
+  if (n_frames > 0 && (!frames || !planes)) return PM_EINVAL;
+  if (n_fallback > 0 && (!fallback_table || !fallback)) return PM_EINVAL;
+  const JpegSource j = {planes, blocks, frames, n_frames, fallback, fallback_bytes, fallback_table, n_fallback, source};
+  return resized_crop_launch(nullptr, nullptr, hw, box, dst, bicubic, B, Hmax, Wmax, out, workspace, ws_bytes, stream, &j);
 }
 
 extern "C" int pm_aug_color_jitter_u8(const unsigned char* src, unsigned char* dst, const pm_aug_jitter* jitter,

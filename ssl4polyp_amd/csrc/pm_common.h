@@ -379,3 +379,64 @@ __device__ __forceinline__ void jidct8(int* c, int s, bool first) {
   c[3 * s] = jdescale(t13 + o0, sh);
   c[4 * s] = jdescale(t13 - o0, sh);
 }
+
+// A decoded JPEG frame on the device, shared by the colour stage of pm_jpeg.hip and the resized crop of pm_augment.hip that
+// reads the component planes directly.  Frame row (jpeg.py JpegBatch.from_bytes), kFrameWords int32: 0 H, 1 W, 2 components,
+// 3 / 4 luma sampling h / v, 5 / 6 MCU columns / rows, 7 restart interval, 8-10 DC table, 11-13 AC table, 14-16 quantisation
+// table, 17-19 first coefficient block per component (the component's plane starts at byte 64 * that, its pitch is the
+// MCU-padded mcux * hs * 8, mcux * 8 for chroma), 20-21 output byte offset (lo, hi), 22-23 first pixel among the device
+// frames (lo, hi)
+constexpr int kFrameWords = 32;
+__device__ __forceinline__ long frame_long(const int* F, int i) { return (long)(((unsigned long)(unsigned)F[i + 1] << 32) | (unsigned)F[i]); }
+
+// a frame row whose MCU grid is one of the supported layouts, with every component plane inside `blocks`
+__device__ __forceinline__ bool frame_ok(const int* F, long blocks) {
+  const int ncomp = F[2], hs = F[3], vs = F[4], mcux = F[5], mcuy = F[6];
+  if ((ncomp != 1 && ncomp != 3) || hs < 1 || hs > 2 || vs < 1 || vs > hs || mcux <= 0 || mcuy <= 0) return false;
+  if (ncomp == 1 && (hs != 1 || vs != 1)) return false;
+  if (F[0] <= 0 || F[1] <= 0 || F[0] > mcuy * 8 * vs || F[1] > mcux * 8 * hs) return false;
+  for (int c = 0; c < ncomp; ++c) {
+    const long n = (long)mcux * mcuy * (c == 0 ? hs * vs : 1);
+    if (F[17 + c] < 0 || F[17 + c] + n > blocks) return false;
+  }
+  return true;
+}
+
+// one chroma sample at output pixel (x, y): jdsample.c h2v1 / h2v2 fancy upsampling (dw > 2) or replication; p: the plane
+// (pitch pw), dw / dh: downsampled_width / height
+__device__ __forceinline__ int chroma_at(const unsigned char* p, int pw, int x, int y, int hs, int vs, int dw, int dh) {
+  if (hs == 1) return p[(long)y * pw + x];
+  const int i = x >> 1;
+  const bool odd = x & 1;
+  if (dw <= 2) return p[(long)(vs == 2 ? y >> 1 : y) * pw + i];
+  const int i2 = odd ? min(i + 1, dw - 1) : max(i - 1, 0);
+  if (vs == 1) {
+    const unsigned char* row = p + (long)y * pw;
+    return (3 * row[i] + row[i2] + (odd ? 2 : 1)) >> 2;
+  }
+  const int r = y >> 1, r2 = (y & 1) ? min(r + 1, dh - 1) : max(r - 1, 0);
+  const unsigned char* a = p + (long)r * pw;
+  const unsigned char* b = p + (long)r2 * pw;
+  const int s1 = 3 * a[i] + b[i], s2 = 3 * a[i2] + b[i2];
+  return (3 * s1 + s2 + (odd ? 7 : 8)) >> 4;
+}
+
+// RGB (0..255) of pixel (x, y), 0 <= x < W, 0 <= y < H in the frame's own coordinates, of a frame row that passed frame_ok:
+// upsampled chroma (chroma_at) + YCbCr -> RGB (jdcolor.c), or grey -> RGB
+__device__ __forceinline__ void jpeg_pixel_rgb(const unsigned char* __restrict__ planes, const int* __restrict__ F, int x, int y, int& r,
+                                               int& g, int& b) {
+  const int H = F[0], W = F[1], ncomp = F[2], hs = F[3], vs = F[4], mcux = F[5];
+  const int yy = planes[(long)F[17] * 64 + (long)y * (mcux * hs * 8) + x];
+  r = g = b = yy;
+  if (ncomp == 3) {
+    const int pw = mcux * 8, dw = (W + hs - 1) / hs, dh = (H + vs - 1) / vs;
+    const int cb = chroma_at(planes + (long)F[18] * 64, pw, x, y, hs, vs, dw, dh) - 128;
+    const int cr = chroma_at(planes + (long)F[19] * 64, pw, x, y, hs, vs, dw, dh) - 128;
+    r = yy + ((91881 * cr + 32768) >> 16);
+    g = yy + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
+    b = yy + ((116130 * cb + 32768) >> 16);
+    r = r < 0 ? 0 : (r > 255 ? 255 : r);
+    g = g < 0 ? 0 : (g > 255 ? 255 : g);
+    b = b < 0 ? 0 : (b > 255 ? 255 : b);
+  }
+}

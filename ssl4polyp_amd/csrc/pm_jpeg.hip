@@ -46,7 +46,7 @@ struct HuffTable {            // jpeg.py derive_huffman (jdhuff.c d_derived_tbl)
 };
 static_assert(sizeof(HuffTable) == 1024, "HuffTable layout (jpeg.HUFF_RECORD)");
 
-constexpr int kFrameWords = 32, kIntervalWords = 8;
+constexpr int kIntervalWords = 8;  // (the frame row: pm_common.h kFrameWords)
 constexpr int kLdsTables = 31;  // < 32 KiB of LDS with the zigzag table (the step's GEMMs hold 128 of the CU's 160 KiB)
 #ifndef PM_JPEG_SUBSEQ_BYTES
 #define PM_JPEG_SUBSEQ_BYTES 128  // (-DPM_JPEG_SUBSEQ_BYTES=64 / 256 with jpeg.SUBSEQ_BYTES set alike: side builds for the timing script)
@@ -61,24 +61,6 @@ __device__ const unsigned char kNatural[80] = {0,  1,  8,  16, 9,  2,  3,  10, 1
                                                40, 48, 41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36,
                                                29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54,
                                                47, 55, 62, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63, 63};
-
-// frame row (jpeg.py JpegBatch.from_bytes): 0 H, 1 W, 2 components, 3 / 4 luma sampling h / v, 5 / 6 MCU columns / rows,
-// 7 restart interval, 8-10 DC table, 11-13 AC table, 14-16 quantisation table, 17-19 first coefficient block per component,
-// 20-21 output byte offset (lo, hi), 22-23 first pixel among the device frames (lo, hi)
-__device__ __forceinline__ long frame_long(const int* F, int i) { return (long)(((unsigned long)(unsigned)F[i + 1] << 32) | (unsigned)F[i]); }
-
-// a frame row whose MCU grid is one of the supported layouts, with every component plane inside `blocks`
-__device__ __forceinline__ bool frame_ok(const int* F, long blocks) {
-  const int ncomp = F[2], hs = F[3], vs = F[4], mcux = F[5], mcuy = F[6];
-  if ((ncomp != 1 && ncomp != 3) || hs < 1 || hs > 2 || vs < 1 || vs > hs || mcux <= 0 || mcuy <= 0) return false;
-  if (ncomp == 1 && (hs != 1 || vs != 1)) return false;
-  if (F[0] <= 0 || F[1] <= 0 || F[0] > mcuy * 8 * vs || F[1] > mcux * 8 * hs) return false;
-  for (int c = 0; c < ncomp; ++c) {
-    const long n = (long)mcux * mcuy * (c == 0 ? hs * vs : 1);
-    if (F[17 + c] < 0 || F[17 + c] + n > blocks) return false;
-  }
-  return true;
-}
 
 // The bit reservoir: 64 bits in registers, refilled 32 bits at a time from 16-byte groups of the interval, two groups in flight (the
 // group being consumed and the next one, loaded when the one before it was taken up: ~128 bits ahead of its use).  `left` counts
@@ -307,50 +289,23 @@ __global__ __launch_bounds__(256) void jpeg_idct_kernel(const short* __restrict_
   }
 }
 
-// one chroma sample at output pixel (x, y): jdsample.c h2v1 / h2v2 fancy upsampling (dw > 2) or replication; p: the plane
-// (pitch pw), dw / dh: downsampled_width / height
-__device__ __forceinline__ int chroma_at(const unsigned char* p, int pw, int x, int y, int hs, int vs, int dw, int dh) {
-  if (hs == 1) return p[(long)y * pw + x];
-  const int i = x >> 1;
-  const bool odd = x & 1;
-  if (dw <= 2) return p[(long)(vs == 2 ? y >> 1 : y) * pw + i];
-  const int i2 = odd ? min(i + 1, dw - 1) : max(i - 1, 0);
-  if (vs == 1) {
-    const unsigned char* row = p + (long)y * pw;
-    return (3 * row[i] + row[i2] + (odd ? 2 : 1)) >> 2;
-  }
-  const int r = y >> 1, r2 = (y & 1) ? min(r + 1, dh - 1) : max(r - 1, 0);
-  const unsigned char* a = p + (long)r * pw;
-  const unsigned char* b = p + (long)r2 * pw;
-  const int s1 = 3 * a[i] + b[i], s2 = 3 * a[i2] + b[i2];
-  return (3 * s1 + s2 + (odd ? 7 : 8)) >> 4;
-}
-
+// stage 3: one thread per pixel of the device frames (the pixel fetch itself is pm_common.h jpeg_pixel_rgb)
 __global__ __launch_bounds__(256) void jpeg_color_kernel(const unsigned char* __restrict__ planes, long blocks, const int* __restrict__ fr,
                                                          int n_fr, long pixels, unsigned char* __restrict__ out, long out_bytes) {
   const long gp = (long)blockIdx.x * 256 + threadIdx.x;
   if (gp >= pixels || n_fr <= 0) return;
   const int* F = fr + (long)find_frame(fr, n_fr, gp, true, 22) * kFrameWords;
   if (!frame_ok(F, blocks)) return;
-  const int H = F[0], W = F[1], ncomp = F[2], hs = F[3], vs = F[4], mcux = F[5], mcuy = F[6];
+  const int H = F[0], W = F[1];
   const long local = gp - frame_long(F, 22), o = frame_long(F, 20);
   if (local < 0 || local >= (long)H * W || o < 0 || o + (long)H * W * 3 > out_bytes) return;
   const int y = (int)(local / W), x = (int)(local - (long)y * W);
-  const int yy = planes[(long)F[17] * 64 + (long)y * (mcux * hs * 8) + x];
-  int r = yy, g = yy, b = yy;
-  if (ncomp == 3) {
-    const int pw = mcux * 8, dw = (W + hs - 1) / hs, dh = (H + vs - 1) / vs;
-    (void)mcuy;
-    const int cb = chroma_at(planes + (long)F[18] * 64, pw, x, y, hs, vs, dw, dh) - 128;
-    const int cr = chroma_at(planes + (long)F[19] * 64, pw, x, y, hs, vs, dw, dh) - 128;
-    r = yy + ((91881 * cr + 32768) >> 16);
-    g = yy + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
-    b = yy + ((116130 * cb + 32768) >> 16);
-  }
+  int r, g, b;
+  jpeg_pixel_rgb(planes, F, x, y, r, g, b);
   unsigned char* d = out + o + local * 3;
-  d[0] = (unsigned char)(r < 0 ? 0 : (r > 255 ? 255 : r));
-  d[1] = (unsigned char)(g < 0 ? 0 : (g > 255 ? 255 : g));
-  d[2] = (unsigned char)(b < 0 ? 0 : (b > 255 ? 255 : b));
+  d[0] = (unsigned char)r;
+  d[1] = (unsigned char)g;
+  d[2] = (unsigned char)b;
 }
 
 // blockIdx.y: the fallback frame; table row (source offset, output offset, bytes)
@@ -731,26 +686,12 @@ extern "C" int pm_jpeg_decode_workspace(int n_intervals, int n_subseq, size_t* b
   return PM_OK;
 }
 
-extern "C" int pm_jpeg_decode_parallel(const unsigned char* entropy, long entropy_bytes, const int* intervals, int n_intervals,
-                                       const int* frames, int n_frames, const unsigned char* huff, int n_huff, const int* quant,
-                                       int n_quant, const unsigned char* fallback, long fallback_bytes,
-                                       const long long* fallback_table, int n_fallback, short* coef, unsigned char* planes, long blocks,
-                                       long pixels, unsigned char* out, long out_bytes, const int* subseq, int n_subseq,
-                                       int sync_rounds, void* workspace, size_t ws_bytes, int* stats, void* stream) {
-  if (n_intervals < 0 || n_frames < 0 || n_huff < 0 || n_quant < 0 || n_fallback < 0 || n_fallback > 65535 || entropy_bytes < 0 ||
-      fallback_bytes < 0 || blocks < 0 || pixels < 0 || out_bytes < 0 || n_subseq < 0 || sync_rounds < 0 || sync_rounds > 8)
-    return PM_ESHAPE;
-  if (entropy_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(entropy) % 16 != 0 || reinterpret_cast<uintptr_t>(workspace) % 16 != 0)
-    return PM_EALIGN;
-  if ((n_frames > 0 || n_fallback > 0) && !out) return PM_EINVAL;
-  if (n_frames > 0 && (!frames || (n_intervals > 0 && (!intervals || !entropy || !huff)) || (blocks > 0 && (!coef || !planes || !quant))))
-    return PM_EINVAL;
-  if (n_fallback > 0 && (!fallback_table || (fallback_bytes > 0 && !fallback))) return PM_EINVAL;
-  if (n_subseq > 0 && (!subseq || !intervals || !entropy || !huff || n_intervals == 0)) return PM_EINVAL;
-  const ParallelWs ws = parallel_ws(n_intervals, n_subseq);
-  if (!workspace || ws_bytes < ws.bytes) return PM_EINVAL;
-  hipStream_t s = pm_stream(stream);
-  unsigned char* wsb = static_cast<unsigned char*>(workspace);
+// the entropy stage parallel inside an interval + the inverse DCT: coefficients -> component planes.  Arguments as validated by the
+// two entries below; ws: the layout of `workspace`
+static int parallel_to_planes(const unsigned char* entropy, long entropy_bytes, const int* intervals, int n_intervals,
+                              const int* frames, int n_frames, const unsigned char* huff, int n_huff, const int* quant, int n_quant,
+                              short* coef, unsigned char* planes, long blocks, const int* subseq, int n_subseq, int sync_rounds,
+                              unsigned char* wsb, const ParallelWs& ws, hipStream_t s) {
   unsigned* counters = reinterpret_cast<unsigned*>(wsb);
   int* bad = reinterpret_cast<int*>(wsb + ws.bad);
   if (hipMemsetAsync(wsb, 0, ws.acc, s) != hipSuccess) return PM_ELAUNCH;  // the counters and bad[]
@@ -795,14 +736,66 @@ extern "C" int pm_jpeg_decode_parallel(const unsigned char* entropy, long entrop
     }
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, s, coef, planes, blocks, frames,
                        n_frames, quant, n_quant);
-    if (pixels > 0)
-      hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, planes, blocks, frames, n_frames,
-                         pixels, out, out_bytes);
   }
+  return PM_OK;
+}
+
+extern "C" int pm_jpeg_decode_parallel(const unsigned char* entropy, long entropy_bytes, const int* intervals, int n_intervals,
+                                       const int* frames, int n_frames, const unsigned char* huff, int n_huff, const int* quant,
+                                       int n_quant, const unsigned char* fallback, long fallback_bytes,
+                                       const long long* fallback_table, int n_fallback, short* coef, unsigned char* planes, long blocks,
+                                       long pixels, unsigned char* out, long out_bytes, const int* subseq, int n_subseq,
+                                       int sync_rounds, void* workspace, size_t ws_bytes, int* stats, void* stream) {
+  if (n_intervals < 0 || n_frames < 0 || n_huff < 0 || n_quant < 0 || n_fallback < 0 || n_fallback > 65535 || entropy_bytes < 0 ||
+      fallback_bytes < 0 || blocks < 0 || pixels < 0 || out_bytes < 0 || n_subseq < 0 || sync_rounds < 0 || sync_rounds > 8)
+    return PM_ESHAPE;
+  if (entropy_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(entropy) % 16 != 0 || reinterpret_cast<uintptr_t>(workspace) % 16 != 0)
+    return PM_EALIGN;
+  if ((n_frames > 0 || n_fallback > 0) && !out) return PM_EINVAL;
+  if (n_frames > 0 && (!frames || (n_intervals > 0 && (!intervals || !entropy || !huff)) || (blocks > 0 && (!coef || !planes || !quant))))
+    return PM_EINVAL;
+  if (n_fallback > 0 && (!fallback_table || (fallback_bytes > 0 && !fallback))) return PM_EINVAL;
+  if (n_subseq > 0 && (!subseq || !intervals || !entropy || !huff || n_intervals == 0)) return PM_EINVAL;
+  const ParallelWs ws = parallel_ws(n_intervals, n_subseq);
+  if (!workspace || ws_bytes < ws.bytes) return PM_EINVAL;
+  hipStream_t s = pm_stream(stream);
+  unsigned char* wsb = static_cast<unsigned char*>(workspace);
+  const int st = parallel_to_planes(entropy, entropy_bytes, intervals, n_intervals, frames, n_frames, huff, n_huff, quant, n_quant, coef,
+                                    planes, blocks, subseq, n_subseq, sync_rounds, wsb, ws, s);
+  if (st != PM_OK) return st;
+  if (n_frames > 0 && blocks > 0 && pixels > 0)
+    hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((pixels + 255) / 256)), dim3(256), 0, s, planes, blocks, frames, n_frames,
+                       pixels, out, out_bytes);
   if (n_fallback > 0)
     hipLaunchKernelGGL(jpeg_copy_kernel, dim3(64, n_fallback), dim3(256), 0, s, fallback, fallback_bytes, fallback_table, out,
                        out_bytes);
-  if (stats) hipLaunchKernelGGL(jpeg_stats_kernel, dim3(1), dim3(1), 0, s, counters, n_subseq, n_intervals, stats);
+  if (stats)
+    hipLaunchKernelGGL(jpeg_stats_kernel, dim3(1), dim3(1), 0, s, reinterpret_cast<const unsigned*>(wsb), n_subseq, n_intervals, stats);
+  if (hipGetLastError() != hipSuccess) return PM_ELAUNCH;
+  return PM_OK;
+}
+
+extern "C" int pm_jpeg_decode_planes(const unsigned char* entropy, long entropy_bytes, const int* intervals, int n_intervals,
+                                     const int* frames, int n_frames, const unsigned char* huff, int n_huff, const int* quant,
+                                     int n_quant, short* coef, unsigned char* planes, long blocks, const int* subseq, int n_subseq,
+                                     int sync_rounds, void* workspace, size_t ws_bytes, int* stats, void* stream) {
+  if (n_intervals < 0 || n_frames < 0 || n_huff < 0 || n_quant < 0 || entropy_bytes < 0 || blocks < 0 || n_subseq < 0 ||
+      sync_rounds < 0 || sync_rounds > 8)
+    return PM_ESHAPE;
+  if (entropy_bytes % 16 != 0 || reinterpret_cast<uintptr_t>(entropy) % 16 != 0 || reinterpret_cast<uintptr_t>(workspace) % 16 != 0)
+    return PM_EALIGN;
+  if (n_frames > 0 && (!frames || (n_intervals > 0 && (!intervals || !entropy || !huff)) || (blocks > 0 && (!coef || !planes || !quant))))
+    return PM_EINVAL;
+  if (n_subseq > 0 && (!subseq || !intervals || !entropy || !huff || n_intervals == 0)) return PM_EINVAL;
+  const ParallelWs ws = parallel_ws(n_intervals, n_subseq);
+  if (!workspace || ws_bytes < ws.bytes) return PM_EINVAL;
+  hipStream_t s = pm_stream(stream);
+  unsigned char* wsb = static_cast<unsigned char*>(workspace);
+  const int st = parallel_to_planes(entropy, entropy_bytes, intervals, n_intervals, frames, n_frames, huff, n_huff, quant, n_quant, coef,
+                                    planes, blocks, subseq, n_subseq, sync_rounds, wsb, ws, s);
+  if (st != PM_OK) return st;
+  if (stats)
+    hipLaunchKernelGGL(jpeg_stats_kernel, dim3(1), dim3(1), 0, s, reinterpret_cast<const unsigned*>(wsb), n_subseq, n_intervals, stats);
   if (hipGetLastError() != hipSuccess) return PM_ELAUNCH;
   return PM_OK;
 }

@@ -250,6 +250,27 @@ def draw_rrc_boxes(B: int, height, width, generator: Optional[torch.Generator] =
     return out
 
 
+def _upload_pinned(bufs: dict, device, name: str, arr) -> torch.Tensor:
+    """numpy -> device through a pinned staging tensor kept per name in `bufs` (non-blocking; rewritten only after a host sync of
+    the previous copy's event)."""
+    import numpy as np
+    host = torch.from_numpy(np.ascontiguousarray(arr))
+    slot = bufs.get("pin_" + name)
+    if slot is None or slot[0].shape != host.shape or slot[0].dtype != host.dtype:
+        slot = bufs["pin_" + name] = [torch.empty(host.shape, dtype=host.dtype).pin_memory(), None]
+    if slot[1] is not None:
+        slot[1].synchronize()
+    slot[0].copy_(host)
+    dev = bufs.get("dev_" + name)
+    if dev is None or dev.shape != host.shape or dev.dtype != host.dtype:
+        dev = bufs["dev_" + name] = torch.empty(host.shape, dtype=host.dtype, device=device)
+    dev.copy_(slot[0], non_blocking=True)
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(device))
+    slot[1] = ev
+    return dev
+
+
 class DeviceAugmenter:
     """The reference's whole train transform after decoding, on the device: [Resize ->] ColorJitter -> GaussianBlur(25) -> flips
     -> RandomRotation(180) -> ToTensor -> Normalize, six launches over a uint8 batch (pm_aug_*), f32 NCHW out.  The host does
@@ -272,20 +293,7 @@ class DeviceAugmenter:
     def _upload(self, name, arr):
         """numpy -> device through a pinned staging tensor kept per name (non-blocking; rewritten only after a host sync of the
         previous copy's event)."""
-        import numpy as np
-        host = torch.from_numpy(np.ascontiguousarray(arr))
-        slot = self._bufs.get("pin_" + name)
-        if slot is None or slot[0].shape != host.shape or slot[0].dtype != host.dtype:
-            slot = self._bufs["pin_" + name] = [torch.empty(host.shape, dtype=host.dtype).pin_memory(), None]
-        if slot[1] is not None:
-            slot[1].synchronize()
-        slot[0].copy_(host)
-        dev = self._buf("dev_" + name, host.shape, host.dtype)
-        dev.copy_(slot[0], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        slot[1] = ev
-        return dev
+        return _upload_pinned(self._bufs, self.device, name, arr)
 
     def _grow(self, name, nbytes: int) -> torch.Tensor:
         """A uint8 device scratch buffer of at least `nbytes`, reallocated only when a batch needs more than it holds (the size of a
@@ -380,10 +388,14 @@ class DeviceAugmenter:
         """The MAE pre-train transform after decoding (main_pretrain.py:156-160): RandomResizedCrop(bicubic) -> RandomHorizontalFlip
         -> ToTensor -> Normalize, f32 [B, 3, size, size].  frames: uint8 [B, H, W, 3] or a device-resident RaggedFrames; the
         generator draws the boxes first, then the flips."""
-        B = len(frames)
-        x = self.random_resized_crop(frames, boxes, generator)
+        return self.mae_tail(self.random_resized_crop(frames, boxes, generator), hflip, generator, out)
+
+    def mae_tail(self, x: torch.Tensor, hflip=None, generator: Optional[torch.Generator] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """What mae_transform does after its crop: RandomHorizontalFlip -> ToTensor -> Normalize of an already cropped uint8 batch
+        [B, size, size, 3] (the crop may come from elsewhere, e.g. DeviceJpegDecoder.resized_crop)."""
         if hflip is None:
-            hflip = (torch.rand(B, generator=generator) < 0.5)
+            hflip = (torch.rand(len(x), generator=generator) < 0.5)
         flips = self._upload("mae_flips", torch.as_tensor(hflip).to(torch.uint8).numpy())
         return preprocess_u8(x, flips, self.mean, self.std, out=out)
 
@@ -574,27 +586,34 @@ class DevicePerturber:
     def __init__(self, device, key: bytes = DEFAULT_HMAC_KEY, jpeg_fn=None):
         self.device, self.key, self.jpeg_fn = torch.device(device), key, jpeg_fn
         self._aug = DeviceAugmenter(device)   # (its staging / scratch helpers)
+        self._decoder: Optional["DeviceJpegDecoder"] = None   # (batches(): kept across batches once a JpegBatch arrives)
 
     def eval_transform(self, frames: torch.Tensor, rows=None, size: int = 224, mean: Sequence[float] = IMAGENET_MEAN,
-                       std: Sequence[float] = IMAGENET_STD) -> torch.Tensor:
+                       std: Sequence[float] = IMAGENET_STD, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """ClassificationTransforms(stage="val" / "test", enable_perturbations=rows is not None) for a decoded uint8 batch
         [B, Hs, Ws, 3] of one frame size, or a device-resident RaggedFrames of mixed sizes (transforms.py:234-256):
         Resize((size, size)) -> [the rows' perturbations] -> ToTensor -> Normalize, f32 [B, 3, size, size] out; three to ten
-        launches, nothing leaves the device."""
+        launches, nothing leaves the device.  `out`: the f32 tensor to write (as preprocess_u8 takes it)."""
         if self._aug.size != size:
             self._aug = DeviceAugmenter(self.device, size=size)
         x = self._aug.resize(frames)
         if rows is not None:
             x = self(x, rows)
-        return preprocess_u8(x, None, mean, std)
+        return preprocess_u8(x, None, mean, std, out=out)
 
     def batches(self, loader: Iterable, size: int = 224) -> Iterator[Tuple]:
-        """For the evaluation loop: `loader` yields (decoded uint8 frames [B, Hs, Ws, 3] or a RaggedFrames, on the host, labels,
+        """For the evaluation loop: `loader` yields (decoded uint8 frames [B, Hs, Ws, 3], a RaggedFrames or a jpeg.JpegBatch of
+        compressed files -- decoded here on the device by a DeviceJpegDecoder this object keeps --, on the host, labels,
         rows) -- what PackDataset + pack_collate hand over before the transform (classification/data/packs.py:70-80) -- and this
         yields (f32 [B, 3, size, size] on the device, labels on the device, rows), i.e. what train.evaluate_cls iterates over, with
         the rows' perturbations rendered on the way (transforms.py:249-256)."""
+        from .jpeg import JpegBatch
         for frames, labels, rows in loader:
-            if isinstance(frames, RaggedFrames):
+            if isinstance(frames, JpegBatch):
+                if self._decoder is None:
+                    self._decoder = DeviceJpegDecoder(self.device)
+                frames = self._decoder(frames.to(self.device, non_blocking=True))
+            elif isinstance(frames, RaggedFrames):
                 frames = frames.to(self.device, non_blocking=True)
             else:
                 frames = torch.as_tensor(frames).to(self.device, non_blocking=True).contiguous()
@@ -702,17 +721,77 @@ class DeviceJpegDecoder:
             raise _lib.PolypMaeError("DeviceJpegDecoder.stats(): no mode='parallel' call has been made")
         return dict(zip(self.STATS, t[:len(self.STATS)].tolist()))
 
-    def __call__(self, batch) -> RaggedFrames:
+    @staticmethod
+    def _ptr(x: torch.Tensor):
+        return x.data_ptr() if x.numel() else None
+
+    @staticmethod
+    def _check_batch(batch) -> None:
         from .jpeg import JpegBatch
         if not isinstance(batch, JpegBatch):
             raise TypeError("DeviceJpegDecoder takes a jpeg.JpegBatch")
         if not batch.is_cuda:
             raise _lib.PolypMaeError("DeviceJpegDecoder runs on the GPU only (no CPU fallback): move the JpegBatch to the device first")
+
+    def resized_crop(self, batch, boxes, size: int, bicubic: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Decode straight into the resized crop: uint8 [B, size, size, 3] = DeviceAugmenter(size)._ragged_crop(self(batch), boxes,
+        bicubic) byte for byte, without the full-size RGB frames in between (no buffer of meta["nbytes"] is allocated).  The
+        entropy stage and the inverse DCT are those of mode="parallel" (pm_jpeg_decode_planes); the crop's horizontal pass then
+        reads the component planes -- or a host-decoded frame's bytes in `fallback` -- where they lie (pm_jpeg_resized_crop_u8).
+        boxes: (top, left, h, w) int [B, 4], each inside its own frame (batch.meta["hw"])."""
+        import numpy as np
+        self._check_batch(batch)
+        m, t = batch.meta, batch.t
+        B, S = len(batch), int(size)
+        hw = m["hw"]
+        boxes = np.ascontiguousarray(boxes, dtype=np.int32)
+        if S <= 0 or boxes.shape != (B, 4) or (boxes[:, 2:] <= 0).any() or (boxes[:, :2] < 0).any() or \
+                (boxes[:, 0] + boxes[:, 2] > hw[:, 0]).any() or (boxes[:, 1] + boxes[:, 3] > hw[:, 1]).any():
+            raise ValueError("crop boxes must be (top, left, h, w) inside their own frame, one per sample")
+        if out is None:   # (grow-only, as the other buffers: a ragged last batch is a view of it)
+            out = self._grow("crop", B * S * S * 3, torch.uint8)[:B * S * S * 3].view(B, S, S, 3)
+        elif tuple(out.shape) != (B, S, S, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != t["hw"].device:
+            raise ValueError("`out` must be a contiguous uint8 [B, size, size, 3] tensor on the batch's device")
+        # per sample: the frame row it is, or -1 - k for row k of the fallback table (both tables are in frame order)
+        source = np.zeros(B, dtype=np.int32)
+        on_host = np.zeros(B, dtype=bool)
+        on_host[m["fallback"]] = True
+        source[~on_host] = np.arange(B - int(on_host.sum()), dtype=np.int32)
+        source[on_host] = -1 - np.arange(int(on_host.sum()), dtype=np.int32)
+        box_d = _upload_pinned(self._bufs, self.device, "crop_box", boxes)
+        src_d = _upload_pinned(self._bufs, self.device, "crop_source", source)
+        coef = self._grow("coef", m["blocks"] * 64, torch.int16)
+        planes = self._grow("planes", m["blocks"] * 64, torch.uint8)
+        ptr = self._ptr
+        lib = _lib.load()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        n_sub = t["subseq"].numel()
+        need = ctypes.c_size_t(0)
+        _lib.check(lib.pm_jpeg_decode_workspace(t["intervals"].shape[0], n_sub, ctypes.byref(need)), "pm_jpeg_decode_workspace")
+        ws = self._grow("workspace", need.value, torch.uint8)
+        stats = self._grow("stats", 8, torch.int32)
+        _lib.check(lib.pm_jpeg_decode_planes(ptr(t["entropy"]), t["entropy"].numel(), ptr(t["intervals"]), t["intervals"].shape[0],
+                                             ptr(t["frames"]), t["frames"].shape[0], ptr(t["huff"]), t["huff"].shape[0],
+                                             ptr(t["quant"]), t["quant"].shape[0], coef.data_ptr(), planes.data_ptr(), m["blocks"],
+                                             ptr(t["subseq"]), n_sub, self.sync_rounds, ws.data_ptr(), ws.numel(), stats.data_ptr(),
+                                             stream), "pm_jpeg_decode_planes")
+        Hmax, Wmax = int(hw[:, 0].max()), int(hw[:, 1].max())
+        _lib.check(lib.pm_jpeg_resized_crop_workspace(B, Hmax, Wmax, S, ctypes.byref(need)), "pm_jpeg_resized_crop_workspace")
+        cws = self._grow("crop_ws", need.value, torch.uint8)
+        _lib.check(lib.pm_jpeg_resized_crop_u8(planes.data_ptr(), m["blocks"], ptr(t["frames"]), t["frames"].shape[0], ptr(t["fallback"]),
+                                               t["fallback"].numel(), ptr(t["fallback_table"]), t["fallback_table"].shape[0],
+                                               src_d.data_ptr(), t["hw"].data_ptr(), box_d.data_ptr(), out.data_ptr(),
+                                               1 if bicubic else 0, B, Hmax, Wmax, S, cws.data_ptr(), cws.numel(), stream),
+                   "pm_jpeg_resized_crop_u8")
+        return out
+
+    def __call__(self, batch) -> RaggedFrames:
+        self._check_batch(batch)
         m, t = batch.meta, batch.t
         coef = self._grow("coef", m["blocks"] * 64, torch.int16)
         planes = self._grow("planes", m["blocks"] * 64, torch.uint8)
         out = self._grow("out", m["nbytes"], torch.uint8)
-        ptr = lambda x: x.data_ptr() if x.numel() else None
+        ptr = self._ptr
         lib = _lib.load()
         args = (ptr(t["entropy"]), t["entropy"].numel(), ptr(t["intervals"]), t["intervals"].shape[0], ptr(t["frames"]),
                 t["frames"].shape[0], ptr(t["huff"]), t["huff"].shape[0], ptr(t["quant"]), t["quant"].shape[0], ptr(t["fallback"]),
@@ -741,13 +820,23 @@ class DevicePrefetcher:
 
     def __init__(self, loader: Iterable, device, mean: Sequence[float] = IMAGENET_MEAN, std: Sequence[float] = IMAGENET_STD,
                  flip_p: float = 0.0, generator: Optional[torch.Generator] = None, augment: Optional["DeviceAugmenter"] = None,
-                 stream: str = "auto", transform: str = "train"):
+                 stream: str = "auto", transform: str = "train", perturb: Optional["DevicePerturber"] = None,
+                 rest_to_device: bool = True, fused_decode: bool = False):
         """augment: a DeviceAugmenter -> the loader may yield decoded frames of any size and a transform of the reference runs on
         the copy stream, drawing its parameters from `generator` (`flip_p` is then ignored):
           transform="train": the classification train transform (Resize, ColorJitter, GaussianBlur(25), flips,
                              RandomRotation(180), ToTensor, Normalize; classification/data/transforms.py:234-246);
           transform="mae":   the MAE pre-train transform (RandomResizedCrop(bicubic), RandomHorizontalFlip, ToTensor, Normalize;
-                             mae/main_pretrain.py:156-160).
+                             mae/main_pretrain.py:156-160);
+          transform="eval":  ClassificationTransforms(stage="val" / "test") (transforms.py:247-256): Resize((S, S)), the row
+                             perturbations when a DevicePerturber is given as `perturb` (the rows are the LAST element of the
+                             batch), ToTensor, Normalize -- into the slot's own f32 buffer; nothing random.
+        rest_to_device=False leaves the tensors after the frames (the labels) on the host: train.evaluate_cls reads the targets of
+        every batch on the host, which is a device sync per batch when they were moved.
+        fused_decode=True: a JpegBatch is not decoded to full-size RGB frames first; the decoder does the first stage of the
+        transform itself (DeviceJpegDecoder.resized_crop: the whole-frame bilinear Resize of "train" and "eval", the
+        RandomResizedCrop of "mae", its boxes drawn from the batch's sizes by the same generator calls in the same order), so every
+        output byte equals fused_decode=False.  Other batches are not affected.
         Frames of mixed decoded sizes -- an image folder such as Hyperkvasir-unlabelled -- arrive as a RaggedFrames (see
         `ragged_collate`): one host-to-device copy of the packed bytes plus the two small offset / size tables, then the per-sample
         resized crop (pm_aug_resized_crop_ragged_u8: the Resize of "train" is a crop with the whole frame as its box) brings every
@@ -764,11 +853,14 @@ class DevicePrefetcher:
         "auto": "side" when a torch.distributed process group is initialised, "own" otherwise."""
         if stream not in ("auto", "own", "side"):
             raise ValueError("stream must be 'auto', 'own' or 'side'")
-        if transform not in ("train", "mae"):
-            raise ValueError("transform must be 'train' or 'mae'")
-        if transform == "mae" and augment is None:
-            raise ValueError("transform='mae' needs a DeviceAugmenter (augment=...)")
+        if transform not in ("train", "mae", "eval"):
+            raise ValueError("transform must be 'train', 'mae' or 'eval'")
+        if transform in ("mae", "eval") and augment is None:
+            raise ValueError(f"transform='{transform}' needs a DeviceAugmenter (augment=...)")
+        if perturb is not None and transform != "eval":
+            raise ValueError("perturb=... applies to transform='eval' only")
         self.stream_mode, self.transform = stream, transform
+        self.perturb, self.rest_to_device, self.fused_decode = perturb, bool(rest_to_device), bool(fused_decode)
         self.loader, self.device = loader, torch.device(device)
         self.mean, self.std, self.flip_p, self.generator = mean, std, float(flip_p), generator
         self.augment = augment
@@ -816,9 +908,10 @@ class DevicePrefetcher:
             d[:h.numel()].copy_(h, non_blocking=True)
         return RaggedFrames(dev[0][:nbytes], dev[1][:B], dev[2][:2 * B].view(B, 2), _host=frames._host)
 
-    def _stage_jpeg(self, slot: int, batch) -> RaggedFrames:
+    def _stage_jpeg(self, slot: int, batch):
         """A jpeg.JpegBatch: one host-to-device copy per array into this slot's grow-only buffers (as _stage_ragged), then the
-        decode (DeviceJpegDecoder) on the copy stream.  Called on the copy stream."""
+        decode (DeviceJpegDecoder) on the copy stream -- or, with fused_decode, the decode into the first stage of the transform,
+        which returns the uint8 [B, S, S, 3] batch.  Called on the copy stream."""
         from .jpeg import JpegBatch
         pin_bufs = self._jpeg_pin[slot] = self._jpeg_pin[slot] or {}
         dev_bufs = self._jpeg_dev[slot] = self._jpeg_dev[slot] or {}
@@ -837,7 +930,35 @@ class DevicePrefetcher:
             staged[name] = d.view(t.shape)
         if self._decoder is None:
             self._decoder = DeviceJpegDecoder(self.device)
-        return self._decoder(JpegBatch(staged, batch.meta))
+        staged = JpegBatch(staged, batch.meta)
+        if not self.fused_decode:
+            return self._decoder(staged)
+        import numpy as np
+        hw = batch.meta["hw"]
+        if self.transform == "mae":   # (the draws of DeviceAugmenter.random_resized_crop)
+            return self._decoder.resized_crop(staged, draw_rrc_boxes(len(batch), hw[:, 0], hw[:, 1], self.generator),
+                                              self.augment.size, True)
+        boxes = np.zeros((len(batch), 4), dtype=np.int32)   # (DeviceAugmenter.resize: the whole frame, bilinear)
+        boxes[:, 2:] = hw
+        return self._decoder.resized_crop(staged, boxes, self.augment.size, False)
+
+    def _transform(self, x, rest: Tuple, out: torch.Tensor, cropped: bool = False) -> torch.Tensor:
+        """The slot's transform on the copy stream.  x: decoded frames (uniform or ragged) or, cropped=True, the uint8 [B, S, S, 3]
+        batch a fused decode already brought through the first stage (the Resize of "train" / "eval" passes it on as it is)."""
+        if self.transform == "mae":
+            if cropped:
+                return self.augment.mae_tail(x, generator=self.generator, out=out)
+            return self.augment.mae_transform(x, generator=self.generator, out=out)
+        if self.transform == "eval":
+            if self.perturb is not None:
+                return self.perturb.eval_transform(x, rest[-1], size=self.augment.size, mean=self.mean, std=self.std, out=out)
+            return preprocess_u8(self.augment.resize(x), None, self.mean, self.std, out=out)
+        return self.augment(x, generator=self.generator, out=out)
+
+    def _rest(self, rest: Tuple) -> Tuple:
+        if not self.rest_to_device:
+            return rest
+        return tuple(t.to(self.device, non_blocking=True) if torch.is_tensor(t) else t for t in rest)
 
     def _stage(self, slot: int, batch) -> Tuple:
         from .jpeg import JpegBatch
@@ -855,11 +976,8 @@ class DevicePrefetcher:
                 if self._consumed[slot] is not None:
                     self._stream.wait_event(self._consumed[slot])
                 x = self._stage_ragged(slot, frames) if isinstance(frames, RaggedFrames) else self._stage_jpeg(slot, frames)
-                if self.transform == "mae":
-                    imgs = self.augment.mae_transform(x, generator=self.generator, out=bufs[1])
-                else:
-                    imgs = self.augment(x, generator=self.generator, out=bufs[1])
-                rest_dev = tuple(t.to(self.device, non_blocking=True) if torch.is_tensor(t) else t for t in rest)
+                imgs = self._transform(x, rest, bufs[1], cropped=self.fused_decode and isinstance(frames, JpegBatch))
+                rest_dev = self._rest(rest)
                 ev = torch.cuda.Event()
                 ev.record(self._stream)
                 self._slot_copied[slot] = ev
@@ -897,14 +1015,12 @@ class DevicePrefetcher:
             if self._consumed[slot] is not None:
                 self._stream.wait_event(self._consumed[slot])
             bufs[0].copy_(pin, non_blocking=True)
-            if self.augment is not None and self.transform == "mae":
-                imgs = self.augment.mae_transform(bufs[0], generator=self.generator, out=bufs[1])
-            elif self.augment is not None:
-                imgs = self.augment(bufs[0], generator=self.generator, out=bufs[1])
+            if self.augment is not None:
+                imgs = self._transform(bufs[0], rest, bufs[1])
             else:
                 fl = flips.to(self.device, non_blocking=True) if flips is not None else None
                 imgs = preprocess_u8(bufs[0], fl, self.mean, self.std, out=bufs[1])
-            rest_dev = tuple(t.to(self.device, non_blocking=True) if torch.is_tensor(t) else t for t in rest)
+            rest_dev = self._rest(rest)
             ev = torch.cuda.Event()
             ev.record(self._stream)
             self._slot_copied[slot] = ev
@@ -953,7 +1069,7 @@ class DevicePrefetcher:
                 main = torch.cuda.current_stream(self.device)
                 main.wait_event(ev)
                 for t in rest:
-                    if torch.is_tensor(t):
+                    if torch.is_tensor(t) and t.is_cuda:
                         t.record_stream(main)
                 yield (imgs,) + rest
                 # the consumer has enqueued its work on this batch: the slot's buffers may be refilled once that work ran

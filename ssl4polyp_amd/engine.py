@@ -437,6 +437,11 @@ class BlockStack:
             keep_from = g.depth
         cls_top = cls_top and ws.N > 1 and g.depth >= 1
         B, N, M, D, Hd = ws.B, ws.N, ws.M, g.dim, g.hidden
+        if cls_top and x_in.is_cuda:
+            # a new workspace fills its cls-row index tables with launches on THIS stream: they must be enqueued before the fork
+            # below, or the other half's gather reads `rows` on its own stream before they are written (recycled allocator
+            # memory then holds stale indices: an out-of-bounds gather)
+            self.top_compact(ws, g, k.act_dtype, x_in.device)
         # The forward has no second stream of its own work to share the CUs with, so the batch is cut into two halves
         # that run as independent chains on two streams: one half's GEMM tails / attention / LayerNorm fill the CUs
         # the other half's kernels leave idle (every op is per token or per (sample, head), and the halves write

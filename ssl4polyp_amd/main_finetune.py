@@ -1,0 +1,173 @@
+"""Classification fine-tuning from CSV packs on the MI355X engine -- a small command over what the package already has, not a port
+of the reference's train_classification.py: the split CSVs of a pack (`frame_path,label` + metadata, classification/data/packs.py)
+are read by packs.read_pack_csv, the workers only decode (or, `--decode device`, only read and pack the files), and the whole
+transform -- the train augmentation, the eval Resize + row perturbations -- runs on the device (packs.device_pack_loaders).
+
+    python -m ssl4polyp_amd.main_finetune --train_csv data_packs/sun_full/train.csv --val_csv data_packs/sun_full/val.csv \\
+        --test_csv data_packs/sun_full/test.csv --root sun=/data/SUN --mae_checkpoint out/ckpts/last.pth --decode device
+
+Training is the reference's: configure_finetune_parameters(--finetune_mode), AdamW over a head and a backbone group
+(tc.py:5751-5768), the per-epoch cosine factor with warm-up (tc.py:3952-3957), BCE with pos_weight = neg / pos of the train labels
+(tc.py:6092-6096), evaluation on val after every epoch and on test at the end.  One JSON line per epoch goes to
+<output_dir>/log.txt (train loss, lr, img/s, val loss from the returned logits); metrics and thresholds stay in the reference's code
+(DESIGN.md section 6).  `run(args)` returns the model and the last val logits.  Not here: sharded evaluation through the prefetcher.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+
+import torch
+import torch.distributed as dist
+
+from . import models
+from .optim import FusedAdamW, LossScaler
+from .parallel import DataParallel
+from .train import FINETUNE_MODES, cls_cosine_lambda, configure_finetune_parameters, evaluate_cls, save_cls_checkpoint, train_epoch_cls
+
+
+def get_args_parser():
+    p = argparse.ArgumentParser("Classification fine-tuning from CSV packs (MI355X)", add_help=True)
+    p.add_argument("--train_csv", default=None, help="train split of the pack (frame_path,label + metadata columns)")
+    p.add_argument("--val_csv", default=None)
+    p.add_argument("--test_csv", default=None)
+    p.add_argument("--root", action="append", default=[], metavar="KEY=PATH",
+                   help="roots map entry: KEY is the first component of frame_path, or a row's store_id / dataset (repeatable)")
+    p.add_argument("--batch_size", default=64, type=int, help="batch size per GPU")
+    p.add_argument("--epochs", default=50, type=int)
+    p.add_argument("--lr", default=1e-3, type=float)
+    p.add_argument("--weight_decay", default=0.05, type=float)
+    p.add_argument("--warmup_epochs", default=0, type=int)
+    p.add_argument("--finetune_mode", default="full", choices=sorted(FINETUNE_MODES))
+    p.add_argument("--mae_checkpoint", default=None, help="MAE pre-training checkpoint for the backbone (default: random init)")
+    p.add_argument("--imagenet_weights", default=None, help="augreg ViT-B/16 .npz on local disk: the ImageNet-initialised ViT instead")
+    p.add_argument("--random_vit", action="store_true", help="the randomly initialised timm-style ViT instead of the MAE encoder")
+    p.add_argument("--num_classes", default=2, type=int)
+    p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"])
+    p.add_argument("--decode", default="host", choices=["host", "device"],
+                   help="where the frames are decoded: 'device' = the workers only read and pack the files, baseline JPEGs are "
+                        "decoded on the GPU bit for bit as Pillow does (others still on the host)")
+    p.add_argument("--fused_decode", action="store_true",
+                   help="with --decode device: decode straight into the resized frame, no full-size RGB in between (same bytes)")
+    p.add_argument("--num_workers", default=8, type=int)
+    p.add_argument("--pin_mem", action="store_true")
+    p.add_argument("--no_pin_mem", action="store_false", dest="pin_mem")
+    p.set_defaults(pin_mem=True)
+    p.add_argument("--perturb_test", action="store_true", help="render the test rows' perturbations (Exp-5 packs)")
+    p.add_argument("--output_dir", default="./output_dir")
+    p.add_argument("--seed", default=0, type=int)
+    p.add_argument("--log_every", default=20, type=int)
+    return p
+
+
+def parse_roots(specs) -> dict:
+    roots = {}
+    for spec in specs or []:
+        key, sep, path = str(spec).partition("=")
+        if not sep or not key or not path:
+            raise SystemExit(f"--root takes KEY=PATH (got {spec!r})")
+        roots[key] = path
+    return roots
+
+
+def build_model(args):
+    if args.imagenet_weights or args.random_vit:
+        return models.get_ImageNet_or_random_ViT(True, args.num_classes, False, None, args.imagenet_weights or False,
+                                                 precision=args.precision)
+    return models.get_MAE_backbone(args.mae_checkpoint, True, args.num_classes, False, None, precision=args.precision)
+
+
+def host_loss(logits: torch.Tensor, targets: torch.Tensor, pos_weight) -> float:
+    """The fine-tune loss (tc.py:3347-3374) of a finished pass, on the host from the returned logits."""
+    import torch.nn.functional as F
+    if logits.numel() == 0:
+        return float("nan")
+    if logits.shape[1] == 2:
+        pw = None if pos_weight is None else torch.tensor(float(pos_weight))
+        return F.binary_cross_entropy_with_logits(logits[:, 1] - logits[:, 0], targets.float(), pos_weight=pw).item()
+    return F.cross_entropy(logits, targets.long()).item()
+
+
+def run(args):
+    if not (args.train_csv or args.val_csv or args.test_csv):
+        raise SystemExit("no data: pass --train_csv (and --val_csv / --test_csv), each a split CSV of a pack")
+    if args.fused_decode and args.decode != "device":
+        raise SystemExit("--fused_decode needs --decode device")
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local)
+    device = torch.device("cuda", local)
+    from .engine import reserve_streams
+    reserve_streams(device)  # before RCCL creates its streams: one hardware queue per engine stream (engine.reserve_streams)
+    if world > 1 and not dist.is_initialized():
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group("nccl", device_id=device)
+    from .packs import device_pack_loaders, read_pack_csv
+    roots = parse_roots(args.root)
+    splits = {name: read_pack_csv(path, roots) for name, path in
+              (("train", args.train_csv), ("val", args.val_csv), ("test", args.test_csv)) if path}
+    loaders, sampler = device_pack_loaders(splits, device, args.batch_size, decode=args.decode, world=world, rank=rank, seed=args.seed,
+                                           num_workers=args.num_workers, pin_memory=args.pin_mem,
+                                           perturbation_splits=("test",) if args.perturb_test else (),
+                                           fused_decode=args.fused_decode)
+    torch.manual_seed(args.seed)   # the same initialisation on every rank
+    model = build_model(args)
+    configure_finetune_parameters(model, args.finetune_mode)
+    ddp = DataParallel(model, device)
+    head = list(model.lin_head.parameters())
+    head_ids = {id(p) for p in head}
+    groups = [{"params": head, "name": "head"},   # tc.py:5751-5768: every parameter, frozen ones are skipped for want of a gradient
+              {"params": [p for p in model.parameters() if id(p) not in head_ids], "name": "backbone"}]
+    opt = FusedAdamW(model, groups, lr=args.lr, betas=(0.9, 0.999), weight_decay=args.weight_decay)
+    opt.grad_sync = ddp.sync
+    opt.grad_scale = 1.0 / world
+    scaler = LossScaler() if args.precision == "fp16" else None
+    pos_weight = pos_weight_host = None
+    if "train" in splits and args.num_classes == 2:
+        labels = splits["train"][1]
+        pos = sum(1 for v in labels if v == 1)
+        pos_weight_host = (len(labels) - pos) / pos if pos > 0 else 1.0   # tc.py:6092-6096
+        pos_weight = torch.tensor(pos_weight_host, dtype=torch.float32, device=device)
+    log_path = os.path.join(args.output_dir, "log.txt")
+    val_logits = None
+    if rank == 0:
+        os.makedirs(args.output_dir, exist_ok=True)
+
+    def log(record):
+        if rank == 0:
+            with open(log_path, "a") as f:
+                f.write(json.dumps(record) + "\n")
+
+    if "train" in loaders:
+        for epoch in range(args.epochs):
+            if isinstance(sampler, torch.utils.data.DistributedSampler):
+                sampler.set_epoch(epoch)
+            factor = cls_cosine_lambda(epoch, args.warmup_epochs, args.epochs)
+            for g in opt.param_groups:
+                g["lr"] = args.lr * factor
+            stats = train_epoch_cls(ddp, loaders["train"], opt, device, pos_weight=pos_weight, log_every=args.log_every,
+                                    printer=(lambda r: print(f"epoch {epoch} {json.dumps(r)}", flush=True)) if rank == 0 else None,
+                                    loss_scaler=scaler)
+            record = {"epoch": epoch, "train_loss": stats.loss, "lr": stats.lr, "samples_per_sec": stats.samples_per_sec}
+            if "val" in loaders:
+                val_logits, val_targets, _ = evaluate_cls(model, loaders["val"], device, shard=False, return_probs=True)
+                record["val_loss"] = host_loss(val_logits, val_targets, pos_weight_host)
+            log(record)
+            save_cls_checkpoint(os.path.join(args.output_dir, "ckpts", f"finetune_e{epoch + 1}.pth"), epoch + 1, model, opt,
+                                loss=record.get("val_loss", stats.loss), pointer=os.path.join(args.output_dir, "ckpts", "last.pth"),
+                                loss_scaler=scaler)
+    elif "val" in loaders:
+        val_logits, val_targets, _ = evaluate_cls(model, loaders["val"], device, shard=False, return_probs=True)
+        log({"val_loss": host_loss(val_logits, val_targets, pos_weight_host)})
+    if "test" in loaders:
+        test_logits, test_targets, _ = evaluate_cls(model, loaders["test"], device, shard=False, return_probs=True)
+        log({"test_loss": host_loss(test_logits, test_targets, pos_weight_host), "test_samples": int(test_logits.shape[0])})
+    if world > 1:
+        dist.destroy_process_group()
+    return model, val_logits
+
+
+if __name__ == "__main__":
+    run(get_args_parser().parse_args())

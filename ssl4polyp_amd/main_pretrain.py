@@ -11,7 +11,8 @@ Data (main_pretrain.py:156-190): `--data_path DIR` trains on the image folder DI
 Hyperkvasir-unlabelled) through folder.folder_loader -- ImageFolder discovery, DistributedSampler(shuffle, seed), drop_last,
 `--num_workers` spawned workers that only decode, `--pin_mem` -- and the MAE transform (RandomResizedCrop(bicubic), flip,
 ToTensor, Normalize) on the device per frame at its native size (data.DevicePrefetcher(transform="mae")); `--decode device`
-leaves the workers reading and packing files and decodes baseline JPEGs on the device too (DESIGN.md has the measured rates).
+leaves the workers reading and packing files and decodes baseline JPEGs on the device too (DESIGN.md has the measured rates);
+`--fused_decode` then decodes straight into the resized crop (data.DeviceJpegDecoder.resized_crop), the same bytes.
 `--synthetic N` instead runs N device-resident Hyperkvasir-shaped batches per epoch; `run(args, data_loader)` takes any iterable of
 (images, _) batches.  Without a folder at the data path and without --synthetic there is no data and the command exits.
 
@@ -63,6 +64,8 @@ def get_args_parser():
     p.add_argument("--decode", default="host", choices=["host", "device"],
                    help="where --data_path JPEGs are decoded: 'device' = the workers only read and pack the files, baseline JPEGs "
                         "are decoded on the GPU bit for bit as Pillow does (others still on the host)")
+    p.add_argument("--fused_decode", action="store_true",
+                   help="with --decode device: decode straight into the resized crop, no full-size RGB frames in between (same bytes)")
     p.add_argument("--synthetic", default=0, type=int, help="number of synthetic batches per epoch (instead of --data_path)")
     p.add_argument("--save_every", default=1, type=int)
     p.add_argument("--log_every", default=20, type=int)
@@ -70,6 +73,9 @@ def get_args_parser():
 
 
 def run(args, data_loader=None):
+    fused = bool(getattr(args, "fused_decode", False))
+    if fused and getattr(args, "decode", "host") != "device":   # (as main_finetune: never a silent host-decoded run)
+        raise SystemExit("--fused_decode needs --decode device")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -107,7 +113,8 @@ def run(args, data_loader=None):
                                    decode=args.decode)
             sampler = loader.sampler
             data_loader = DevicePrefetcher(loader, device, augment=DeviceAugmenter(device, size=args.input_size), transform="mae",
-                                           generator=torch.Generator().manual_seed(args.seed + rank))
+                                           generator=torch.Generator().manual_seed(args.seed + rank),
+                                           fused_decode=fused)
     log_path = os.path.join(args.output_dir, "log.txt")
     for epoch in range(args.start_epoch, args.epochs):
         if sampler is not None:
