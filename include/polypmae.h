@@ -573,6 +573,35 @@ int pm_comm_world(const pm_comm* c, int* rank, int* world);
 int pm_comm_allreduce_f32(pm_comm* c, float* base, const long* lo, const long* hi, int n_buckets, void* stream);
 int pm_comm_destroy(pm_comm* c);
 
+/* ---- cluster-bootstrap replicates of the binary test metrics --------------------------------------------------------------
+ * Replaces the loop of the reference's report modules (classification/analysis/exp*_report.py) over
+ * common_metrics.sample_cluster_ids + compute_binary_metrics (common_metrics.py:100-232; eight scikit-learn calls on a gathered
+ * sample per replicate).  A replicate is a multiset of the N scored frames: frame i counts w = (number of entries of draws[r]
+ * that name cluster[i]) times.  M runs that scored the same frames share the draws (the paired comparisons of the reports).
+ *   score   f64 [M, N]  probabilities of the positive class, finite
+ *   order   i32 [M, N]  per run, the frame indices in descending score order (ties in any order)
+ *   label   u8  [N]     0 / 1
+ *   cluster i32 [N]     values in [0, C)
+ *   draws   i32 [R, K]  cluster indices; -1 is padding
+ *   tau     f64 [M]     decision threshold per run (prediction = score >= tau)
+ *   out     f64 [R, M, 16] in the reference's key order: count, n_pos, n_neg, prevalence, tp, fp, tn, fn, auprc, auroc, recall,
+ *           precision, f1, balanced_accuracy, mcc, loss.  Counts are exact; average precision and AUROC treat tied scores as one
+ *           threshold, as sklearn's curves do; the f64 sums run in a fixed order, so equal inputs give equal bits however R is cut
+ *           into calls.  A replicate without positives or without negatives gets what scikit-learn 1.7 returns for such a sample
+ *           (AUROC NaN, average precision 0 without positives, empty ratios 0); an empty replicate is NaN beyond the counts.
+ * Limits (PM_ESHAPE before any launch): 1 <= N, K, C <= 2^20, M <= 256, R <= 4096 per call, N * K < 2^31 (a replicate's total
+ * weight fits 31 bits).  Table entries outside their range (an order index, a cluster, a draw) count as weight zero / no draw.
+ * workspace: 16-byte aligned, at least pm_boot_metrics_workspace(N, M, R, K, C, &bytes) bytes (PM_EINVAL otherwise).  Its head
+ * holds the sorted view of the runs (score, per-frame loss, cluster and label in `order`), which does not depend on the replicates.
+ * sorted_ready = 0: the contents on entry do not matter and the view is built (one memset and three launches on `stream`).
+ * sorted_ready != 0: the caller states that an earlier call on this stream with sorted_ready = 0 and the same score, order, label,
+ * cluster, N, M and C built the view in this workspace (R may differ: the view lies before everything sized by R) and that nothing
+ * else wrote there since; the view is reused (one memset and two launches).  This is how R replicates are cut into several calls. */
+int pm_boot_metrics_workspace(int N, int M, int R, int K, int C, size_t* bytes);
+int pm_boot_metrics(const double* score, const int* order, const unsigned char* label, const int* cluster, const int* draws,
+                    const double* tau, double* out, int N, int M, int R, int K, int C, int sorted_ready, void* workspace,
+                    size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,8 @@ SIGNATURES = {
     "pm_grad_stats": [P, L, P, P],
     "pm_loss_scale_update": [P, P, P, I, F, F, I, P],
     "pm_dgelu": [P, P, P, I, L, P],
+    "pm_boot_metrics_workspace": [I, I, I, I, I, P],
+    "pm_boot_metrics": [P, P, P, P, P, P, P, I, I, I, I, I, I, P, ctypes.c_size_t, P],
 }
 
 ABI_VERSION = 14  # pm_abi_version() of the library these signatures describe

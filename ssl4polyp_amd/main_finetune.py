@@ -9,13 +9,17 @@ transform -- the train augmentation, the eval Resize + row perturbations -- runs
 Training is the reference's: configure_finetune_parameters(--finetune_mode), AdamW over a head and a backbone group
 (tc.py:5751-5768), the per-epoch cosine factor with warm-up (tc.py:3952-3957), BCE with pos_weight = neg / pos of the train labels
 (tc.py:6092-6096), evaluation on val after every epoch and on test at the end.  One JSON line per epoch goes to
-<output_dir>/log.txt (train loss, lr, img/s, val loss from the returned logits); metrics and thresholds stay in the reference's code
-(DESIGN.md section 6).  `run(args)` returns the model and the last val logits.  Not here: sharded evaluation through the prefetcher.
+<output_dir>/log.txt (train loss, lr, img/s, val loss from the returned logits).  `--metrics` adds the reference's binary metrics at
+tau = 0.5 to the val and test records; `--bootstrap R` adds their 95 % cluster-bootstrap intervals (`bootstrap`, `ci_lower`,
+`ci_upper`) to the test record, with or without `--metrics` (metrics.py: one device call per chunk of replicates); a value that is
+not finite is logged as null; threshold selection stays in the reference's code.  `run(args)` returns
+the model and the last val logits.  Not here: sharded evaluation through the prefetcher.
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 
 import torch
@@ -58,6 +62,11 @@ def get_args_parser():
     p.add_argument("--output_dir", default="./output_dir")
     p.add_argument("--seed", default=0, type=int)
     p.add_argument("--log_every", default=20, type=int)
+    p.add_argument("--metrics", action="store_true",
+                   help="log the binary metrics of val and test at tau = 0.5 (AUPRC, AUROC, recall, precision, F1, balanced accuracy, MCC, loss)")
+    p.add_argument("--bootstrap", default=0, type=int, metavar="R",
+                   help="R > 0: 95 %% intervals of the test metrics from R cluster-bootstrap replicates (clusters: case_id per label)")
+    p.add_argument("--bootstrap_seed", default=12345, type=int)
     return p
 
 
@@ -89,9 +98,44 @@ def host_loss(logits: torch.Tensor, targets: torch.Tensor, pos_weight) -> float:
     return F.cross_entropy(logits, targets.long()).item()
 
 
+METRICS_TAU = 0.5
+
+
+def strict(values) -> list:
+    """The values as a list with None where one is not finite: json.dumps would write a bare NaN, which is not JSON."""
+    return [v if math.isfinite(v) else None for v in values]
+
+
+def metric_records(prefix: str, logits: torch.Tensor, targets: torch.Tensor, rows, device, metrics: bool = True, bootstrap: int = 0,
+                   seed: int = 0) -> dict:
+    """The entries `--metrics` / `--bootstrap` add to a record.  metrics: <prefix>_metrics, the 16 values of the reference's
+    compute_binary_metrics at tau = 0.5.  bootstrap > 0: `bootstrap`, ci_lower / ci_upper per reported metric from that many
+    replicates that resample whole cases per label (rows without a case_id are clusters of their own).  A value that is not finite
+    (AUROC of a split without positives or without negatives) is logged as null, so that every line stays strict JSON."""
+    import numpy as np
+    from . import metrics as MX
+    probs = MX.positive_probs(logits.to(device))
+    out = {}
+    if metrics:
+        values = MX.binary_metrics(probs, targets, METRICS_TAU, device=device)
+        out[f"{prefix}_metrics"] = dict(zip(values, strict(values.values())))
+    if bootstrap > 0 and logits.shape[0] > 0:
+        clusters = MX.build_cluster_set(rows, targets.tolist())
+        draws = MX.draw_cluster_samples(clusters, np.random.default_rng(seed), bootstrap)
+        reps = MX.bootstrap_binary_metrics(probs, targets, METRICS_TAU, clusters.cluster, draws, n_clusters=clusters.n_clusters,
+                                           device=device)[:, 0, len(MX.METRIC_KEYS) - len(MX.REPORTED_KEYS):]
+        lo, hi = MX.percentile_ci(reps, 0.95)
+        out["bootstrap"] = int(bootstrap)
+        out["ci_lower"] = dict(zip(MX.REPORTED_KEYS, strict(lo.tolist())))
+        out["ci_upper"] = dict(zip(MX.REPORTED_KEYS, strict(hi.tolist())))
+    return out
+
+
 def run(args):
     if not (args.train_csv or args.val_csv or args.test_csv):
         raise SystemExit("no data: pass --train_csv (and --val_csv / --test_csv), each a split CSV of a pack")
+    if (args.metrics or args.bootstrap > 0) and args.num_classes != 2:
+        raise SystemExit("--metrics / --bootstrap report the binary metrics: they need --num_classes 2")
     if args.fused_decode and args.decode != "device":
         raise SystemExit("--fused_decode needs --decode device")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -154,16 +198,25 @@ def run(args):
             if "val" in loaders:
                 val_logits, val_targets, _ = evaluate_cls(model, loaders["val"], device, shard=False, return_probs=True)
                 record["val_loss"] = host_loss(val_logits, val_targets, pos_weight_host)
+                if args.metrics and rank == 0:
+                    record.update(metric_records("val", val_logits, val_targets, splits["val"][2], device))
             log(record)
             save_cls_checkpoint(os.path.join(args.output_dir, "ckpts", f"finetune_e{epoch + 1}.pth"), epoch + 1, model, opt,
                                 loss=record.get("val_loss", stats.loss), pointer=os.path.join(args.output_dir, "ckpts", "last.pth"),
                                 loss_scaler=scaler)
     elif "val" in loaders:
         val_logits, val_targets, _ = evaluate_cls(model, loaders["val"], device, shard=False, return_probs=True)
-        log({"val_loss": host_loss(val_logits, val_targets, pos_weight_host)})
+        record = {"val_loss": host_loss(val_logits, val_targets, pos_weight_host)}
+        if args.metrics and rank == 0:
+            record.update(metric_records("val", val_logits, val_targets, splits["val"][2], device))
+        log(record)
     if "test" in loaders:
         test_logits, test_targets, _ = evaluate_cls(model, loaders["test"], device, shard=False, return_probs=True)
-        log({"test_loss": host_loss(test_logits, test_targets, pos_weight_host), "test_samples": int(test_logits.shape[0])})
+        record = {"test_loss": host_loss(test_logits, test_targets, pos_weight_host), "test_samples": int(test_logits.shape[0])}
+        if (args.metrics or args.bootstrap > 0) and rank == 0:
+            record.update(metric_records("test", test_logits, test_targets, splits["test"][2], device, args.metrics, args.bootstrap,
+                                         args.bootstrap_seed))
+        log(record)
     if world > 1:
         dist.destroy_process_group()
     return model, val_logits

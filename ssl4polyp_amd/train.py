@@ -333,8 +333,8 @@ def evaluate_cls(model, loader: Iterable, device, max_batches: Optional[int] = N
                  return_probs: bool = False):
     """tc.py:4652-4812 forward part: forward-only kernels in eval mode; logits (and optionally probabilities) of the whole
     pass stay ON THE DEVICE and cross to the host once at the end -- the reference does `logits.detach().cpu()` + `torch.cat`
-    per batch (tc.py:4790-4812), a host sync per batch that drains the queue.  Targets never leave the host.  Metrics stay in
-    the reference's code.
+    per batch (tc.py:4790-4812), a host sync per batch that drains the queue.  Targets never leave the host.  The metrics of
+    the returned logits and their bootstrap intervals: metrics.py.
     shard (default: whenever torch.distributed is initialised with world > 1): rank r evaluates batches r, r + world, ...
     through a rank-local batch sampler (it never decodes another rank's frames); the pieces are all-gathered (one padded
     device collective) and returned in loader order on every rank -- the reference validates on rank 0 only while the other
