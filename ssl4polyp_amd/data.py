@@ -16,9 +16,11 @@ from __future__ import annotations
 
 import concurrent.futures
 import ctypes
+import math
 import os
 from typing import Iterable, Iterator, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -27,14 +29,19 @@ IMAGENET_MEAN: Sequence[float] = (0.485, 0.456, 0.406)   # transforms.py:16
 IMAGENET_STD: Sequence[float] = (0.229, 0.224, 0.225)    # transforms.py:17
 
 
+def _check_u8_frames(frames: torch.Tensor, who: str, host_error=_lib.PolypMaeError) -> None:
+    """A uniform batch: contiguous uint8 [B, H, W, 3] on the GPU (`host_error`: what a host tensor raises)."""
+    if frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise ValueError("frames must be a contiguous uint8 [B, H, W, 3] tensor")
+    if not frames.is_cuda:
+        raise host_error(f"{who} runs on the GPU only (no CPU fallback)")
+
+
 def preprocess_u8(frames: torch.Tensor, flips: Optional[torch.Tensor] = None, mean: Sequence[float] = IMAGENET_MEAN,
                   std: Sequence[float] = IMAGENET_STD, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """frames: uint8 [B, H, W, 3] on the GPU; flips: uint8 [B] (bit 0 horizontal, bit 1 vertical) or None.
     Returns float32 [B, 3, H, W] = Normalize(mean, std)(ToTensor(frame)) of the (flipped) frames."""
-    if frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
-        raise ValueError("frames must be a contiguous uint8 [B, H, W, 3] tensor")
-    if not frames.is_cuda:
-        raise _lib.PolypMaeError("preprocess_u8 runs on the GPU only (no CPU fallback)")
+    _check_u8_frames(frames, "preprocess_u8")
     B, H, W, _ = frames.shape
     if out is None:
         out = torch.empty(B, 3, H, W, dtype=torch.float32, device=frames.device)
@@ -54,9 +61,6 @@ def preprocess_u8(frames: torch.Tensor, flips: Optional[torch.Tensor] = None, me
 def _resample_coeffs(in_size: int, out_size: int):
     """Pillow Resample.c precompute_coeffs (bilinear filter, support 1, antialiased) + normalize_coeffs_8bpc: for every output
     index the first source index, the tap count and the 22-bit fixed-point taps.  Double arithmetic, as in the C source."""
-    import math
-
-    import numpy as np
     scale = in_size / out_size
     filterscale = max(scale, 1.0)
     support = filterscale
@@ -82,7 +86,6 @@ def _resample_coeffs(in_size: int, out_size: int):
 
 def _gaussian_taps(ksize: int, sigma):
     """torchvision functional_tensor._get_gaussian_kernel1d in float32, one row per sigma."""
-    import numpy as np
     half = (ksize - 1) * 0.5
     x = np.linspace(-half, half, ksize, dtype=np.float32)
     rows = []
@@ -96,7 +99,6 @@ def _rotation_geom(angle_deg: float, w: int, h: int, flips: int):
     """Image.rotate(angle, NEAREST, expand=False, center=None) -> the pm_aug_geom record: Pillow's inverse affine map about the
     image centre (coefficients rounded to 15 decimals, then FIX(v) = floor(v * 65536 + 0.5), half-pixel offsets folded into
     a2 / a5 as Geometry.c affine_fixed does), or one of its transpose fast paths."""
-    import math
     ang = angle_deg % 360.0
     if ang == 0:
         return (1, 0, 0, 0, 0, 0, 0, flips)
@@ -137,7 +139,6 @@ class RaggedFrames:
     read them back.  Build one with `from_frames`; `ragged_collate` does so in DataLoader workers."""
 
     def __init__(self, data: torch.Tensor, offset: torch.Tensor, hw: torch.Tensor, _host=None):
-        import numpy as np
         if data.dtype != torch.uint8 or data.ndim != 1 or not data.is_contiguous():
             raise ValueError("RaggedFrames.data must be a contiguous 1-D uint8 tensor")
         if offset.dtype != torch.int64 or hw.dtype != torch.int32 or offset.ndim != 1 or tuple(hw.shape) != (offset.numel(), 2) \
@@ -154,7 +155,6 @@ class RaggedFrames:
     @classmethod
     def from_frames(cls, frames) -> "RaggedFrames":
         """frames: a sequence of HWC uint8 arrays or tensors [H_b, W_b, 3] -> one packed host batch (one copy of the pixels)."""
-        import numpy as np
         arrs = [f.numpy() if torch.is_tensor(f) else np.asarray(f) for f in frames]
         if not arrs or any(a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 for a in arrs):
             raise ValueError("RaggedFrames.from_frames takes a non-empty sequence of uint8 [H, W, 3] frames")
@@ -213,9 +213,6 @@ def draw_rrc_boxes(B: int, height, width, generator: Optional[torch.Generator] =
     scale (0.2, 1.0), default ratio): up to ten tries of area ~ U(scale) x aspect ~ logU(ratio), then the central-crop fallback.
     height / width: one size for the batch, or one per frame (box b is get_params of frame b; one generator serves the batch in
     frame order, so equal per-frame sizes draw exactly what the scalar form draws)."""
-    import math
-
-    import numpy as np
     g = generator
     hs = [int(v) for v in height] if isinstance(height, (Sequence, np.ndarray, torch.Tensor)) else [int(height)] * B
     ws = [int(v) for v in width] if isinstance(width, (Sequence, np.ndarray, torch.Tensor)) else [int(width)] * B
@@ -250,25 +247,59 @@ def draw_rrc_boxes(B: int, height, width, generator: Optional[torch.Generator] =
     return out
 
 
-def _upload_pinned(bufs: dict, device, name: str, arr) -> torch.Tensor:
-    """numpy -> device through a pinned staging tensor kept per name in `bufs` (non-blocking; rewritten only after a host sync of
-    the previous copy's event)."""
-    import numpy as np
-    host = torch.from_numpy(np.ascontiguousarray(arr))
-    slot = bufs.get("pin_" + name)
-    if slot is None or slot[0].shape != host.shape or slot[0].dtype != host.dtype:
-        slot = bufs["pin_" + name] = [torch.empty(host.shape, dtype=host.dtype).pin_memory(), None]
-    if slot[1] is not None:
-        slot[1].synchronize()
-    slot[0].copy_(host)
-    dev = bufs.get("dev_" + name)
-    if dev is None or dev.shape != host.shape or dev.dtype != host.dtype:
-        dev = bufs["dev_" + name] = torch.empty(host.shape, dtype=host.dtype, device=device)
-    dev.copy_(slot[0], non_blocking=True)
-    ev = torch.cuda.Event()
-    ev.record(torch.cuda.current_stream(device))
-    slot[1] = ev
-    return dev
+def _check_boxes(boxes, hw) -> np.ndarray:
+    """Crop boxes (top, left, h, w), one per frame, each non-empty and inside its own frame -- hw: int [B, 2] = (H_b, W_b), a
+    uniform batch's one size broadcast -- as the int32 C-contiguous [B, 4] table the crop kernels read."""
+    boxes = np.ascontiguousarray(boxes, dtype=np.int32)
+    if boxes.shape != (len(hw), 4) or (boxes[:, 2:] <= 0).any() or (boxes[:, :2] < 0).any() or \
+            (boxes[:, :2] + boxes[:, 2:] > hw).any():
+        raise ValueError("crop boxes must be (top, left, h, w) inside their own frame, one per sample")
+    return boxes
+
+
+def _whole_frame_boxes(hw) -> np.ndarray:
+    """The boxes (0, 0, H_b, W_b) that make a resized crop the Resize of the whole frame."""
+    boxes = np.zeros((len(hw), 4), dtype=np.int32)
+    boxes[:, 2:] = hw
+    return boxes
+
+
+class _Scratch:
+    """The device buffers one object keeps across calls, by name (`bufs`), so that a steady stream of batches allocates nothing."""
+
+    def __init__(self, device):
+        self.device, self.bufs = torch.device(device), {}
+
+    def exact(self, name: str, shape, dtype) -> torch.Tensor:
+        """A tensor of this shape and dtype, reallocated when either differs from the last call's."""
+        t = self.bufs.get(name)
+        if t is None or t.shape != torch.Size(shape) or t.dtype != dtype:
+            t = self.bufs[name] = torch.empty(shape, dtype=dtype, device=self.device)
+        return t
+
+    def grow(self, name: str, n: int, dtype) -> torch.Tensor:
+        """A flat tensor of at least n elements, reallocated only when a call needs more than it holds (callers take a view of
+        its front: a workspace follows the largest batch seen)."""
+        t = self.bufs.get(name)
+        if t is None or t.numel() < n or t.dtype != dtype:
+            t = self.bufs[name] = torch.empty(max(int(n), 1), dtype=dtype, device=self.device)
+        return t
+
+    def upload(self, name: str, arr) -> torch.Tensor:
+        """numpy -> device through a pinned staging tensor kept per name (non-blocking; rewritten only after a host sync of the
+        previous copy's event)."""
+        host = torch.from_numpy(np.ascontiguousarray(arr))
+        slot = self.bufs.get("pin_" + name)
+        if slot is None or slot[0].shape != host.shape or slot[0].dtype != host.dtype:
+            slot = self.bufs["pin_" + name] = [torch.empty(host.shape, dtype=host.dtype).pin_memory(), None]
+        if slot[1] is not None:
+            slot[1].synchronize()
+        slot[0].copy_(host)
+        dev = self.exact("dev_" + name, host.shape, host.dtype)
+        dev.copy_(slot[0], non_blocking=True)
+        slot[1] = torch.cuda.Event()
+        slot[1].record(torch.cuda.current_stream(self.device))
+        return dev
 
 
 class DeviceAugmenter:
@@ -282,57 +313,33 @@ class DeviceAugmenter:
     def __init__(self, device, size: int = 224, mean: Sequence[float] = IMAGENET_MEAN, std: Sequence[float] = IMAGENET_STD):
         self.device, self.size, self.mean, self.std = torch.device(device), int(size), tuple(mean), tuple(std)
         self._coeffs = {}
-        self._bufs = {}
+        self._scratch = _Scratch(self.device)
 
-    def _buf(self, name, shape, dtype):
-        t = self._bufs.get(name)
-        if t is None or t.shape != torch.Size(shape) or t.dtype != dtype:
-            t = self._bufs[name] = torch.empty(shape, dtype=dtype, device=self.device)
-        return t
-
-    def _upload(self, name, arr):
-        """numpy -> device through a pinned staging tensor kept per name (non-blocking; rewritten only after a host sync of the
-        previous copy's event)."""
-        return _upload_pinned(self._bufs, self.device, name, arr)
-
-    def _grow(self, name, nbytes: int) -> torch.Tensor:
-        """A uint8 device scratch buffer of at least `nbytes`, reallocated only when a batch needs more than it holds (the size of a
-        ragged batch's workspace follows its largest frame)."""
-        t = self._bufs.get(name)
-        if t is None or t.numel() < nbytes:
-            t = self._bufs[name] = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=self.device)
-        return t
-
-    def _ragged_crop(self, frames: RaggedFrames, boxes, bicubic: bool, name: str) -> torch.Tensor:
-        """pm_aug_resized_crop_ragged_u8: boxes (top, left, h, w) int32 [B, 4], each inside its own frame."""
-        import numpy as np
-        B, S = len(frames), self.size
-        hw = frames.sizes
-        boxes = np.ascontiguousarray(boxes, dtype=np.int32)
-        if boxes.shape != (B, 4) or (boxes[:, 2:] <= 0).any() or (boxes[:, :2] < 0).any() or \
-                (boxes[:, 0] + boxes[:, 2] > hw[:, 0]).any() or (boxes[:, 1] + boxes[:, 3] > hw[:, 1]).any():
-            raise ValueError("crop boxes must be (top, left, h, w) inside their own frame, one per sample")
-        Hmax, Wmax = int(hw[:, 0].max()), int(hw[:, 1].max())
+    def _resized_crop(self, frames, boxes: np.ndarray, bicubic: bool, name: str) -> torch.Tensor:
+        """pm_aug_resized_crop_u8 / pm_aug_resized_crop_ragged_u8: frames uint8 [B, Hs, Ws, 3] or a RaggedFrames, on the device;
+        boxes as _check_boxes returns them.  The workspace follows the largest frame seen; `name` keeps the box upload and the
+        output of the Resize apart from those of the RandomResizedCrop."""
+        B, S, sc = len(frames), self.size, self._scratch
         lib = _lib.load()
-        ws = self._grow("rrc_ws", int(lib.pm_aug_resized_crop_workspace_bytes(B, Hmax, Wmax, S)))
-        box_d = self._upload(name + "_box", boxes)
-        out = self._buf(name + "_out", (B, S, S, 3), torch.uint8)
-        _lib.check(lib.pm_aug_resized_crop_ragged_u8(frames.data.data_ptr(), frames.offset.data_ptr(), frames.hw.data_ptr(),
-                                                     box_d.data_ptr(), out.data_ptr(), 1 if bicubic else 0, B, Hmax, Wmax, S,
-                                                     ws.data_ptr(), ws.numel(), torch.cuda.current_stream(self.device).cuda_stream),
-                   "pm_aug_resized_crop_ragged_u8")
+        if isinstance(frames, RaggedFrames):
+            fn, src = lib.pm_aug_resized_crop_ragged_u8, (frames.data.data_ptr(), frames.offset.data_ptr(), frames.hw.data_ptr())
+            Hmax, Wmax = (int(v) for v in frames.sizes.max(0))
+        else:
+            fn, src = lib.pm_aug_resized_crop_u8, (frames.data_ptr(),)
+            Hmax, Wmax = frames.shape[1:3]
+        ws = sc.grow("crop_ws", int(lib.pm_aug_resized_crop_workspace_bytes(B, Hmax, Wmax, S)), torch.uint8)
+        box_d = sc.upload(name + "_box", boxes)
+        out = sc.exact(name + "_out", (B, S, S, 3), torch.uint8)
+        _lib.check(fn(*src, box_d.data_ptr(), out.data_ptr(), 1 if bicubic else 0, B, Hmax, Wmax, S, ws.data_ptr(), ws.numel(),
+                      torch.cuda.current_stream(self.device).cuda_stream), fn.__name__)
         return out
 
     def resize(self, frames) -> torch.Tensor:
         """uint8 [B, Hs, Ws, 3] -> uint8 [B, size, size, 3] (T.Resize((size, size)) on PIL images).  A device-resident RaggedFrames
         goes through the ragged resized crop with the whole frame as the box and the bilinear filter (the same taps)."""
         if isinstance(frames, RaggedFrames):
-            import numpy as np
             _check_ragged_on_device(frames, "DeviceAugmenter")
-            hw = frames.sizes
-            boxes = np.zeros((len(frames), 4), dtype=np.int32)
-            boxes[:, 2:] = hw
-            return self._ragged_crop(frames, boxes, False, "rs")
+            return self._resized_crop(frames, _whole_frame_boxes(frames.sizes), False, "rs")
         B, Hs, Ws, _ = frames.shape
         S = self.size
         if (Hs, Ws) == (S, S):
@@ -344,8 +351,8 @@ class DeviceAugmenter:
             by, ty, ky = _resample_coeffs(Hs, S)
             c = self._coeffs[key] = tuple(torch.from_numpy(a).to(self.device) for a in (bx, tx, by, ty)) + (kx, ky)
         bx, tx, by, ty, kx, ky = c
-        tmp = self._buf("rs_tmp", (B, Hs, S, 3), torch.uint8)
-        out = self._buf("rs_out", (B, S, S, 3), torch.uint8)
+        tmp = self._scratch.exact("rs_tmp", (B, Hs, S, 3), torch.uint8)
+        out = self._scratch.exact("rs_out", (B, S, S, 3), torch.uint8)
         lib = _lib.load()
         _lib.check(lib.pm_aug_resize_u8(frames.data_ptr(), tmp.data_ptr(), out.data_ptr(), bx.data_ptr(), tx.data_ptr(), kx,
                                         by.data_ptr(), ty.data_ptr(), ky, B, Hs, Ws, S, S,
@@ -357,31 +364,15 @@ class DeviceAugmenter:
         """uint8 [B, Hs, Ws, 3] or a device-resident RaggedFrames -> uint8 [B, size, size, 3]: RandomResizedCrop(size,
         scale=(0.2, 1.0), interpolation=bicubic) of the MAE pre-train transform (main_pretrain.py:157), one crop box per sample
         (drawn here unless given, for a ragged batch from each frame's own size)."""
-        import numpy as np
         if isinstance(frames, RaggedFrames):
             _check_ragged_on_device(frames, "DeviceAugmenter")
-            if boxes is None:
-                boxes = draw_rrc_boxes(len(frames), frames.sizes[:, 0], frames.sizes[:, 1], generator)
-            return self._ragged_crop(frames, boxes, bicubic, "rrc")
-        if frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[-1] != 3 or not frames.is_contiguous() or not frames.is_cuda:
-            raise ValueError("frames must be a contiguous uint8 [B, H, W, 3] tensor on the GPU")
-        B, Hs, Ws, _ = frames.shape
-        S = self.size
+            hw = frames.sizes
+        else:
+            _check_u8_frames(frames, "DeviceAugmenter.random_resized_crop", host_error=ValueError)
+            hw = np.broadcast_to(frames.shape[1:3], (len(frames), 2))
         if boxes is None:
-            boxes = draw_rrc_boxes(B, Hs, Ws, generator)
-        boxes = np.ascontiguousarray(boxes, dtype=np.int32)
-        if boxes.shape != (B, 4) or (boxes[:, 2:] <= 0).any() or (boxes[:, :2] < 0).any() or \
-                (boxes[:, 0] + boxes[:, 2] > Hs).any() or (boxes[:, 1] + boxes[:, 3] > Ws).any():
-            raise ValueError("crop boxes must be (top, left, h, w) inside the frame, one per sample")
-        lib = _lib.load()
-        need = int(lib.pm_aug_resized_crop_workspace_bytes(B, Hs, Ws, S))
-        ws = self._buf("rrc_ws", (need,), torch.uint8)
-        box_d = self._upload("rrc_box", boxes)
-        out = self._buf("rrc_out", (B, S, S, 3), torch.uint8)
-        _lib.check(lib.pm_aug_resized_crop_u8(frames.data_ptr(), box_d.data_ptr(), out.data_ptr(), 1 if bicubic else 0, B, Hs, Ws, S,
-                                              ws.data_ptr(), ws.numel(), torch.cuda.current_stream(self.device).cuda_stream),
-                   "pm_aug_resized_crop_u8")
-        return out
+            boxes = draw_rrc_boxes(len(frames), hw[:, 0], hw[:, 1], generator)
+        return self._resized_crop(frames, _check_boxes(boxes, hw), bicubic, "rrc")
 
     def mae_transform(self, frames, boxes=None, hflip=None, generator: Optional[torch.Generator] = None,
                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -396,7 +387,7 @@ class DeviceAugmenter:
         [B, size, size, 3] (the crop may come from elsewhere, e.g. DeviceJpegDecoder.resized_crop)."""
         if hflip is None:
             hflip = (torch.rand(len(x), generator=generator) < 0.5)
-        flips = self._upload("mae_flips", torch.as_tensor(hflip).to(torch.uint8).numpy())
+        flips = self._scratch.upload("mae_flips", torch.as_tensor(hflip).to(torch.uint8).numpy())
         return preprocess_u8(x, flips, self.mean, self.std, out=out)
 
     def __call__(self, frames, params: Optional[dict] = None, generator: Optional[torch.Generator] = None,
@@ -404,16 +395,13 @@ class DeviceAugmenter:
         """frames uint8 [B, H, W, 3] or a RaggedFrames, on the device.  Returns f32 [B, 3, size, size] (normalised) or, with
         to_f32=False, the augmented uint8 frames [B, size, size, 3] (written into `out` when given).  After the Resize every frame
         is size x size, so a ragged batch continues down the uniform chain."""
-        import numpy as np
         if isinstance(frames, RaggedFrames):
             _check_ragged_on_device(frames, "DeviceAugmenter")
         else:
-            if frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
-                raise ValueError("frames must be a contiguous uint8 [B, H, W, 3] tensor")
-            if not frames.is_cuda:
-                raise _lib.PolypMaeError("DeviceAugmenter runs on the GPU only (no CPU fallback)")
+            _check_u8_frames(frames, "DeviceAugmenter")
         lib = _lib.load()
         st = torch.cuda.current_stream(self.device).cuda_stream
+        up, buf = self._scratch.upload, self._scratch.exact
         x = self.resize(frames)
         B, H, W, _ = x.shape
         p = params if params is not None else draw_train_params(B, generator)
@@ -422,21 +410,21 @@ class DeviceAugmenter:
         jit[:, :4] = np.asarray(p["order"], dtype=np.int32)
         jit[:, 4:7] = np.stack([np.asarray(p[k], dtype=np.float32) for k in ("brightness", "contrast", "saturation")], 1).view(np.int32)
         jit[:, 7] = [int(np.int64(float(h) * 255)) & 0xFF for h in p["hue"]]   # np.uint8(hue_factor * 255): C cast, wraps
-        jit_d = self._upload("jit", jit)
-        lsum = self._buf("lsum", (B,), torch.int64)
-        a = self._buf("aug_a", (B, H, W, 3), torch.uint8)
+        jit_d = up("jit", jit)
+        lsum = buf("lsum", (B,), torch.int64)
+        a = buf("aug_a", (B, H, W, 3), torch.uint8)
         _lib.check(lib.pm_aug_color_jitter_u8(x.data_ptr(), a.data_ptr(), jit_d.data_ptr(), lsum.data_ptr(), B, H, W, st),
                    "pm_aug_color_jitter_u8")
         # -- GaussianBlur((25, 25))
-        taps_d = self._upload("taps", _gaussian_taps(self.KSIZE, p["sigma"]))
-        tmp = self._buf("blur_tmp", (B, H, W, 3), torch.float32)
-        b = self._buf("aug_b", (B, H, W, 3), torch.uint8)
+        taps_d = up("taps", _gaussian_taps(self.KSIZE, p["sigma"]))
+        tmp = buf("blur_tmp", (B, H, W, 3), torch.float32)
+        b = buf("aug_b", (B, H, W, 3), torch.uint8)
         _lib.check(lib.pm_aug_gaussian_blur_u8(a.data_ptr(), tmp.data_ptr(), b.data_ptr(), taps_d.data_ptr(), self.KSIZE, B, H, W,
                                                st), "pm_aug_gaussian_blur_u8")
         # -- flips + rotation (+ ToTensor + Normalize)
         geom = np.array([_rotation_geom(float(p["angle"][i]), W, H, int(bool(p["hflip"][i])) | (int(bool(p["vflip"][i])) << 1))
                          for i in range(B)], dtype=np.int32)
-        geom_d = self._upload("geom", geom)
+        geom_d = up("geom", geom)
         want = (B, 3, H, W) if to_f32 else (B, H, W, 3)
         if out is None:
             out = torch.empty(want, dtype=torch.float32 if to_f32 else torch.uint8, device=self.device)
@@ -490,7 +478,6 @@ def _row_seed(row, key: bytes) -> int:
 def occlusion_rect(area_fraction: float, seed: int, width: int, height: int):
     """transforms.py:99-120: the black rectangle of an "occ" row as (x0, y0, x1, y1), corners inclusive as ImageDraw.rectangle draws
     them, or None.  The draws come from Python's own random.Random(seed), in the reference's order."""
-    import math
     import random
     a = max(0.0, min(float(area_fraction), 1.0))
     if a <= 0:
@@ -556,8 +543,6 @@ def perturbation_plan(row, key: bytes = DEFAULT_HMAC_KEY):
 def pil_box_blur_params(sigma: float, passes: int = 3):
     """(radius, ww, fw) of Pillow's ImagingGaussianBlur for ImageFilter.GaussianBlur(radius=sigma) (BoxBlur.c: _gaussian_blur_radius, then
     ImagingHorizontalBoxBlur's fixed-point weights), in the float32 / UINT32 arithmetic of the C code.  radius = -1: nothing to blur."""
-    import math
-    import numpy as np
     f32 = np.float32
     s = f32(sigma)
     s2 = f32(s * s / f32(passes))
@@ -585,7 +570,8 @@ class DevicePerturber:
 
     def __init__(self, device, key: bytes = DEFAULT_HMAC_KEY, jpeg_fn=None):
         self.device, self.key, self.jpeg_fn = torch.device(device), key, jpeg_fn
-        self._aug = DeviceAugmenter(device)   # (its staging / scratch helpers)
+        self._scratch = _Scratch(self.device)
+        self._aug: Optional[DeviceAugmenter] = None   # (eval_transform's Resize)
         self._decoder: Optional["DeviceJpegDecoder"] = None   # (batches(): kept across batches once a JpegBatch arrives)
 
     def eval_transform(self, frames: torch.Tensor, rows=None, size: int = 224, mean: Sequence[float] = IMAGENET_MEAN,
@@ -594,7 +580,7 @@ class DevicePerturber:
         [B, Hs, Ws, 3] of one frame size, or a device-resident RaggedFrames of mixed sizes (transforms.py:234-256):
         Resize((size, size)) -> [the rows' perturbations] -> ToTensor -> Normalize, f32 [B, 3, size, size] out; three to ten
         launches, nothing leaves the device.  `out`: the f32 tensor to write (as preprocess_u8 takes it)."""
-        if self._aug.size != size:
+        if self._aug is None or self._aug.size != size:
             self._aug = DeviceAugmenter(self.device, size=size)
         x = self._aug.resize(frames)
         if rows is not None:
@@ -622,18 +608,14 @@ class DevicePerturber:
 
     def __call__(self, frames: torch.Tensor, rows) -> torch.Tensor:
         """frames uint8 [B, H, W, 3] on the device, rows: one metadata mapping (or None) per frame.  Returns a new uint8 tensor."""
-        import numpy as np
-        if frames.dtype != torch.uint8 or frames.ndim != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
-            raise ValueError("frames must be a contiguous uint8 [B, H, W, 3] tensor")
-        if not frames.is_cuda:
-            raise _lib.PolypMaeError("DevicePerturber runs on the GPU only (no CPU fallback)")
+        _check_u8_frames(frames, "DevicePerturber")
         B, H, W, _ = frames.shape
         if len(rows) != B:
             raise ValueError("one row per frame")
         plans = [perturbation_plan(r, self.key) for r in rows]
         lib = _lib.load()
         st = torch.cuda.current_stream(self.device).cuda_stream
-        up, buf = self._aug._upload, self._aug._buf
+        up, buf = self._scratch.upload, self._scratch.exact
         out = frames.clone()
         kinds = {p[0] for p in plans}
         if "jpeg" in kinds:
@@ -706,17 +688,11 @@ class DeviceJpegDecoder:
             raise ValueError("sync_rounds must be in 0..8")
         self.device = torch.device(device)
         self.mode, self.sync_rounds = mode, int(sync_rounds)
-        self._bufs = {}
-
-    def _grow(self, name, n: int, dtype) -> torch.Tensor:
-        t = self._bufs.get(name)
-        if t is None or t.numel() < n:
-            t = self._bufs[name] = torch.empty(max(int(n), 1), dtype=dtype, device=self.device)
-        return t
+        self._scratch = _Scratch(self.device)
 
     def stats(self) -> dict:
         """The counters of the last mode="parallel" call (synchronises with the device)."""
-        t = self._bufs.get("stats")
+        t = self._scratch.bufs.get("stats")
         if t is None:
             raise _lib.PolypMaeError("DeviceJpegDecoder.stats(): no mode='parallel' call has been made")
         return dict(zip(self.STATS, t[:len(self.STATS)].tolist()))
@@ -733,23 +709,39 @@ class DeviceJpegDecoder:
         if not batch.is_cuda:
             raise _lib.PolypMaeError("DeviceJpegDecoder runs on the GPU only (no CPU fallback): move the JpegBatch to the device first")
 
+    def _tables(self, batch) -> Tuple[tuple, torch.Tensor, torch.Tensor]:
+        """What every decode entry takes first -- entropy, intervals, frames, huff and quant, each with its count -- and the
+        grow-only coefficient and plane buffers."""
+        t, n, ptr = batch.t, batch.meta["blocks"] * 64, self._ptr
+        lead = (ptr(t["entropy"]), t["entropy"].numel(), ptr(t["intervals"]), t["intervals"].shape[0], ptr(t["frames"]),
+                t["frames"].shape[0], ptr(t["huff"]), t["huff"].shape[0], ptr(t["quant"]), t["quant"].shape[0])
+        return lead, self._scratch.grow("coef", n, torch.int16), self._scratch.grow("planes", n, torch.uint8)
+
+    def _parallel_ws(self, batch) -> tuple:
+        """What the parallel entries take last: subseq with its count, sync_rounds, the grow-only workspace with its size, `stats`."""
+        t = batch.t
+        need = ctypes.c_size_t(0)
+        _lib.check(_lib.load().pm_jpeg_decode_workspace(t["intervals"].shape[0], t["subseq"].numel(), ctypes.byref(need)),
+                   "pm_jpeg_decode_workspace")
+        ws = self._scratch.grow("workspace", need.value, torch.uint8)
+        stats = self._scratch.grow("stats", 8, torch.int32)
+        return self._ptr(t["subseq"]), t["subseq"].numel(), self.sync_rounds, ws.data_ptr(), ws.numel(), stats.data_ptr()
+
     def resized_crop(self, batch, boxes, size: int, bicubic: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Decode straight into the resized crop: uint8 [B, size, size, 3] = DeviceAugmenter(size)._ragged_crop(self(batch), boxes,
+        """Decode straight into the resized crop: uint8 [B, size, size, 3] = DeviceAugmenter(size)._resized_crop(self(batch), boxes,
         bicubic) byte for byte, without the full-size RGB frames in between (no buffer of meta["nbytes"] is allocated).  The
         entropy stage and the inverse DCT are those of mode="parallel" (pm_jpeg_decode_planes); the crop's horizontal pass then
         reads the component planes -- or a host-decoded frame's bytes in `fallback` -- where they lie (pm_jpeg_resized_crop_u8).
         boxes: (top, left, h, w) int [B, 4], each inside its own frame (batch.meta["hw"])."""
-        import numpy as np
         self._check_batch(batch)
-        m, t = batch.meta, batch.t
+        m, t, sc, ptr = batch.meta, batch.t, self._scratch, self._ptr
         B, S = len(batch), int(size)
         hw = m["hw"]
-        boxes = np.ascontiguousarray(boxes, dtype=np.int32)
-        if S <= 0 or boxes.shape != (B, 4) or (boxes[:, 2:] <= 0).any() or (boxes[:, :2] < 0).any() or \
-                (boxes[:, 0] + boxes[:, 2] > hw[:, 0]).any() or (boxes[:, 1] + boxes[:, 3] > hw[:, 1]).any():
-            raise ValueError("crop boxes must be (top, left, h, w) inside their own frame, one per sample")
+        if S <= 0:
+            raise ValueError("size must be positive")
+        boxes = _check_boxes(boxes, hw)
         if out is None:   # (grow-only, as the other buffers: a ragged last batch is a view of it)
-            out = self._grow("crop", B * S * S * 3, torch.uint8)[:B * S * S * 3].view(B, S, S, 3)
+            out = sc.grow("crop", B * S * S * 3, torch.uint8)[:B * S * S * 3].view(B, S, S, 3)
         elif tuple(out.shape) != (B, S, S, 3) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != t["hw"].device:
             raise ValueError("`out` must be a contiguous uint8 [B, size, size, 3] tensor on the batch's device")
         # per sample: the frame row it is, or -1 - k for row k of the fallback table (both tables are in frame order)
@@ -758,26 +750,16 @@ class DeviceJpegDecoder:
         on_host[m["fallback"]] = True
         source[~on_host] = np.arange(B - int(on_host.sum()), dtype=np.int32)
         source[on_host] = -1 - np.arange(int(on_host.sum()), dtype=np.int32)
-        box_d = _upload_pinned(self._bufs, self.device, "crop_box", boxes)
-        src_d = _upload_pinned(self._bufs, self.device, "crop_source", source)
-        coef = self._grow("coef", m["blocks"] * 64, torch.int16)
-        planes = self._grow("planes", m["blocks"] * 64, torch.uint8)
-        ptr = self._ptr
+        box_d, src_d = sc.upload("crop_box", boxes), sc.upload("crop_source", source)
         lib = _lib.load()
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        n_sub = t["subseq"].numel()
+        lead, coef, planes = self._tables(batch)
+        _lib.check(lib.pm_jpeg_decode_planes(*lead, coef.data_ptr(), planes.data_ptr(), m["blocks"], *self._parallel_ws(batch), stream),
+                   "pm_jpeg_decode_planes")
+        Hmax, Wmax = (int(v) for v in hw.max(0))
         need = ctypes.c_size_t(0)
-        _lib.check(lib.pm_jpeg_decode_workspace(t["intervals"].shape[0], n_sub, ctypes.byref(need)), "pm_jpeg_decode_workspace")
-        ws = self._grow("workspace", need.value, torch.uint8)
-        stats = self._grow("stats", 8, torch.int32)
-        _lib.check(lib.pm_jpeg_decode_planes(ptr(t["entropy"]), t["entropy"].numel(), ptr(t["intervals"]), t["intervals"].shape[0],
-                                             ptr(t["frames"]), t["frames"].shape[0], ptr(t["huff"]), t["huff"].shape[0],
-                                             ptr(t["quant"]), t["quant"].shape[0], coef.data_ptr(), planes.data_ptr(), m["blocks"],
-                                             ptr(t["subseq"]), n_sub, self.sync_rounds, ws.data_ptr(), ws.numel(), stats.data_ptr(),
-                                             stream), "pm_jpeg_decode_planes")
-        Hmax, Wmax = int(hw[:, 0].max()), int(hw[:, 1].max())
         _lib.check(lib.pm_jpeg_resized_crop_workspace(B, Hmax, Wmax, S, ctypes.byref(need)), "pm_jpeg_resized_crop_workspace")
-        cws = self._grow("crop_ws", need.value, torch.uint8)
+        cws = sc.grow("crop_ws", need.value, torch.uint8)
         _lib.check(lib.pm_jpeg_resized_crop_u8(planes.data_ptr(), m["blocks"], ptr(t["frames"]), t["frames"].shape[0], ptr(t["fallback"]),
                                                t["fallback"].numel(), ptr(t["fallback_table"]), t["fallback_table"].shape[0],
                                                src_d.data_ptr(), t["hw"].data_ptr(), box_d.data_ptr(), out.data_ptr(),
@@ -787,27 +769,17 @@ class DeviceJpegDecoder:
 
     def __call__(self, batch) -> RaggedFrames:
         self._check_batch(batch)
-        m, t = batch.meta, batch.t
-        coef = self._grow("coef", m["blocks"] * 64, torch.int16)
-        planes = self._grow("planes", m["blocks"] * 64, torch.uint8)
-        out = self._grow("out", m["nbytes"], torch.uint8)
-        ptr = self._ptr
+        m, t, ptr = batch.meta, batch.t, self._ptr
+        lead, coef, planes = self._tables(batch)
+        out = self._scratch.grow("out", m["nbytes"], torch.uint8)
+        args = lead + (ptr(t["fallback"]), t["fallback"].numel(), ptr(t["fallback_table"]), t["fallback_table"].shape[0],
+                       coef.data_ptr(), planes.data_ptr(), m["blocks"], m["pixels"], out.data_ptr(), m["nbytes"])
         lib = _lib.load()
-        args = (ptr(t["entropy"]), t["entropy"].numel(), ptr(t["intervals"]), t["intervals"].shape[0], ptr(t["frames"]),
-                t["frames"].shape[0], ptr(t["huff"]), t["huff"].shape[0], ptr(t["quant"]), t["quant"].shape[0], ptr(t["fallback"]),
-                t["fallback"].numel(), ptr(t["fallback_table"]), t["fallback_table"].shape[0], coef.data_ptr(), planes.data_ptr(),
-                m["blocks"], m["pixels"], out.data_ptr(), m["nbytes"])
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if self.mode == "interval":
             _lib.check(lib.pm_jpeg_decode(*args, stream), "pm_jpeg_decode")
         else:
-            n_sub = t["subseq"].numel()
-            need = ctypes.c_size_t(0)
-            _lib.check(lib.pm_jpeg_decode_workspace(t["intervals"].shape[0], n_sub, ctypes.byref(need)), "pm_jpeg_decode_workspace")
-            ws = self._grow("workspace", need.value, torch.uint8)
-            stats = self._grow("stats", 8, torch.int32)
-            _lib.check(lib.pm_jpeg_decode_parallel(*args, ptr(t["subseq"]), n_sub, self.sync_rounds, ws.data_ptr(), ws.numel(),
-                                                   stats.data_ptr(), stream), "pm_jpeg_decode_parallel")
+            _lib.check(lib.pm_jpeg_decode_parallel(*args, *self._parallel_ws(batch), stream), "pm_jpeg_decode_parallel")
         return RaggedFrames(out[:m["nbytes"]], t["offset"], t["hw"], _host=(m["offset"], m["hw"]))
 
 
@@ -840,12 +812,12 @@ class DevicePrefetcher:
         Frames of mixed decoded sizes -- an image folder such as Hyperkvasir-unlabelled -- arrive as a RaggedFrames (see
         `ragged_collate`): one host-to-device copy of the packed bytes plus the two small offset / size tables, then the per-sample
         resized crop (pm_aug_resized_crop_ragged_u8: the Resize of "train" is a crop with the whole frame as its box) brings every
-        frame to S x S on the device, and the rest of the chain is the uniform one.  The pinned and device staging buffers of a
-        ragged batch are sized in bytes, kept per slot and only ever grow; a batch that arrives pinned (DataLoader(pin_memory=True))
-        is copied from where it lies.  A batch of compressed files (jpeg.JpegBatch, `folder_loader(..., decode="device")`) is
-        staged the same way, one copy per array, and decoded on the copy stream (DeviceJpegDecoder) into the RaggedFrames the
-        ragged path then takes.  Uniform [B, H, W, 3] batches keep their own path (and, without `augment`, the fused
-        flips + ToTensor + Normalize of pm_preprocess_u8 only).
+        frame to S x S on the device, and the rest of the chain is the uniform one.  A batch of compressed files (jpeg.JpegBatch,
+        `folder_loader(..., decode="device")`) is decoded on the copy stream (DeviceJpegDecoder) into the RaggedFrames the ragged
+        path then takes.  Every kind of batch is staged the same way (`_stage_tensors`), one copy per tensor: the pinned and device
+        staging buffers are kept per slot and per name and only ever grow, and a batch that arrives pinned
+        (DataLoader(pin_memory=True)) is copied from where it lies.  Without `augment`, uniform [B, H, W, 3] batches get the fused
+        flips + ToTensor + Normalize of pm_preprocess_u8 only.
         stream: where the copies and the transform run -- "own": a stream of the prefetcher (a fourth busy stream beside the
         engine's three: one hardware queue each, fastest on a single GPU); "side": the engine's weight-gradient stream (idle
         during the forward pass, when the next batch is staged) -- for data-parallel ranks, where RCCL's stream is the fourth busy
@@ -864,13 +836,9 @@ class DevicePrefetcher:
         self.loader, self.device = loader, torch.device(device)
         self.mean, self.std, self.flip_p, self.generator = mean, std, float(flip_p), generator
         self.augment = augment
-        self._pinned = [None, None]
-        self._flip_pin = [None, None]   # per slot: pinned flip flags
-        self._dev = [None, None]        # per slot: (uint8 frames, float32 images) on the device
-        self._ragged_pin = [None, None]  # per slot, ragged batches: pinned (bytes, offset, hw), grow-only
-        self._ragged_dev = [None, None]  # per slot, ragged batches: device (bytes, offset, hw), grow-only
-        self._jpeg_pin = [None, None]    # per slot, compressed batches: pinned arrays by name, grow-only
-        self._jpeg_dev = [None, None]    # per slot, compressed batches: device arrays by name, grow-only
+        self._pin = [{}, {}]        # per slot: pinned staging tensors by name, flat and grow-only
+        self._dev = [{}, {}]        # per slot: device staging tensors by name, flat and grow-only
+        self._out = [None, None]    # per slot: the float32 images
         self._decoder: Optional[DeviceJpegDecoder] = None
         self._consumed = [None, None]   # per slot: event recorded on the consumer's stream after it used the batch
         self._slot_copied = [None, None]  # per slot: event after the slot's host-to-device copies were enqueued
@@ -879,68 +847,38 @@ class DevicePrefetcher:
     def __len__(self):
         return len(self.loader)
 
-    @staticmethod
-    def _grown(t: Optional[torch.Tensor], n: int, dtype, device=None) -> torch.Tensor:
-        """`t` if it holds n elements, else a new buffer of n on `device` (None: pinned host memory) -- grow-only staging."""
-        if t is None or t.numel() < n:
-            t = torch.empty(n, dtype=dtype, device=device, pin_memory=device is None)
-        return t
+    def _stage_tensors(self, slot: int, named: dict, pinned: bool) -> dict:
+        """One host-to-device copy per tensor into this slot's grow-only device buffer of that name -- through the slot's grow-only
+        pinned buffer of that name unless the batch arrived pinned (then it is copied from where it lies) -- and views of the
+        device copies in the tensors' own shapes.  A name that held another dtype gets a new buffer.  Called on the copy stream."""
+        def front(bufs: dict, name: str, like: torch.Tensor, device) -> torch.Tensor:   # (device None: pinned host memory)
+            b, n = bufs.get(name), like.numel()
+            if b is None or b.numel() < n or b.dtype != like.dtype:
+                b = bufs[name] = torch.empty(max(n, 1), dtype=like.dtype, device=device, pin_memory=device is None)
+            return b[:n].view(like.shape)
 
-    def _stage_ragged(self, slot: int, frames: RaggedFrames) -> RaggedFrames:
-        """One host-to-device copy of the packed bytes + the two tables into this slot's grow-only device buffers (through its
-        grow-only pinned buffers unless the batch is pinned already).  Called on the copy stream."""
-        B, nbytes = len(frames), frames.data.numel()
-        if frames.is_pinned():
-            src = (frames.data, frames.offset, frames.hw.view(-1))
-        else:
-            pin = self._ragged_pin[slot] or (None, None, None)
-            pin = tuple(self._grown(t, n, dt) for t, n, dt in zip(pin, (nbytes, B, 2 * B), (torch.uint8, torch.int64, torch.int32)))
-            self._ragged_pin[slot] = pin
-            src = (pin[0][:nbytes], pin[1][:B], pin[2][:2 * B])
-            src[0].copy_(frames.data)
-            src[1].copy_(frames.offset)
-            src[2].copy_(frames.hw.view(-1))
-        dev = self._ragged_dev[slot] or (None, None, None)
-        dev = tuple(self._grown(t, n, dt, device=self.device)
-                    for t, n, dt in zip(dev, (nbytes, B, 2 * B), (torch.uint8, torch.int64, torch.int32)))
-        self._ragged_dev[slot] = dev
-        for d, h in zip(dev, src):
-            d[:h.numel()].copy_(h, non_blocking=True)
-        return RaggedFrames(dev[0][:nbytes], dev[1][:B], dev[2][:2 * B].view(B, 2), _host=frames._host)
-
-    def _stage_jpeg(self, slot: int, batch):
-        """A jpeg.JpegBatch: one host-to-device copy per array into this slot's grow-only buffers (as _stage_ragged), then the
-        decode (DeviceJpegDecoder) on the copy stream -- or, with fused_decode, the decode into the first stage of the transform,
-        which returns the uint8 [B, S, S, 3] batch.  Called on the copy stream."""
-        from .jpeg import JpegBatch
-        pin_bufs = self._jpeg_pin[slot] = self._jpeg_pin[slot] or {}
-        dev_bufs = self._jpeg_dev[slot] = self._jpeg_dev[slot] or {}
-        pinned = batch.is_pinned()
         staged = {}
-        for name, t in batch.t.items():
-            n = t.numel()
-            src = t.reshape(-1)
+        for name, t in named.items():
             if not pinned:
-                pin_bufs[name] = self._grown(pin_bufs.get(name), max(n, 1), t.dtype)
-                src = pin_bufs[name][:n]
-                src.copy_(t.reshape(-1))
-            dev_bufs[name] = self._grown(dev_bufs.get(name), max(n, 1), t.dtype, device=self.device)
-            d = dev_bufs[name][:n]
-            d.copy_(src, non_blocking=True)
-            staged[name] = d.view(t.shape)
+                host = front(self._pin[slot], name, t, None)
+                host.copy_(t)
+                t = host
+            staged[name] = front(self._dev[slot], name, t, self.device)
+            staged[name].copy_(t, non_blocking=True)
+        return staged
+
+    def _decode(self, batch):
+        """A staged jpeg.JpegBatch -> the decoded RaggedFrames or, with fused_decode, the uint8 [B, S, S, 3] batch after the first
+        stage of the transform, which the decoder then does itself.  Called on the copy stream."""
         if self._decoder is None:
             self._decoder = DeviceJpegDecoder(self.device)
-        staged = JpegBatch(staged, batch.meta)
         if not self.fused_decode:
-            return self._decoder(staged)
-        import numpy as np
+            return self._decoder(batch)
         hw = batch.meta["hw"]
         if self.transform == "mae":   # (the draws of DeviceAugmenter.random_resized_crop)
-            return self._decoder.resized_crop(staged, draw_rrc_boxes(len(batch), hw[:, 0], hw[:, 1], self.generator),
+            return self._decoder.resized_crop(batch, draw_rrc_boxes(len(batch), hw[:, 0], hw[:, 1], self.generator),
                                               self.augment.size, True)
-        boxes = np.zeros((len(batch), 4), dtype=np.int32)   # (DeviceAugmenter.resize: the whole frame, bilinear)
-        boxes[:, 2:] = hw
-        return self._decoder.resized_crop(staged, boxes, self.augment.size, False)
+        return self._decoder.resized_crop(batch, _whole_frame_boxes(hw), self.augment.size, False)   # (DeviceAugmenter.resize)
 
     def _transform(self, x, rest: Tuple, out: torch.Tensor, cropped: bool = False) -> torch.Tensor:
         """The slot's transform on the copy stream.  x: decoded frames (uniform or ragged) or, cropped=True, the uint8 [B, S, S, 3]
@@ -950,9 +888,10 @@ class DevicePrefetcher:
                 return self.augment.mae_tail(x, generator=self.generator, out=out)
             return self.augment.mae_transform(x, generator=self.generator, out=out)
         if self.transform == "eval":
-            if self.perturb is not None:
-                return self.perturb.eval_transform(x, rest[-1], size=self.augment.size, mean=self.mean, std=self.std, out=out)
-            return preprocess_u8(self.augment.resize(x), None, self.mean, self.std, out=out)
+            x = self.augment.resize(x)
+            if self.perturb is not None and rest[-1] is not None:
+                x = self.perturb(x, rest[-1])
+            return preprocess_u8(x, None, self.mean, self.std, out=out)
         return self.augment(x, generator=self.generator, out=out)
 
     def _rest(self, rest: Tuple) -> Tuple:
@@ -963,63 +902,42 @@ class DevicePrefetcher:
     def _stage(self, slot: int, batch) -> Tuple:
         from .jpeg import JpegBatch
         frames, rest = batch[0], tuple(batch[1:])
-        if isinstance(frames, (RaggedFrames, JpegBatch)):
+        compressed, ragged = isinstance(frames, JpegBatch), isinstance(frames, RaggedFrames)
+        if compressed or ragged:
             if self.augment is None:
                 raise ValueError("a RaggedFrames or JpegBatch batch needs a DeviceAugmenter (augment=...) to bring its frames to one size")
-            S = self.augment.size
-            bufs = self._dev[slot]
-            if bufs is None or bufs[1].shape != (len(frames), 3, S, S):
-                with torch.cuda.stream(self._stream):
-                    bufs = (None, torch.empty((len(frames), 3, S, S), dtype=torch.float32, device=self.device))
-                self._dev[slot] = bufs
-            with torch.cuda.stream(self._stream):
-                if self._consumed[slot] is not None:
-                    self._stream.wait_event(self._consumed[slot])
-                x = self._stage_ragged(slot, frames) if isinstance(frames, RaggedFrames) else self._stage_jpeg(slot, frames)
-                imgs = self._transform(x, rest, bufs[1], cropped=self.fused_decode and isinstance(frames, JpegBatch))
-                rest_dev = self._rest(rest)
-                ev = torch.cuda.Event()
-                ev.record(self._stream)
-                self._slot_copied[slot] = ev
-            return imgs, rest_dev, ev
-        if frames.dtype != torch.uint8:
-            raise ValueError("DevicePrefetcher expects uint8 HWC frames from the loader")
-        if frames.is_pinned():  # e.g. DataLoader(pin_memory=True): no staging copy
-            pin = frames
+            named = frames.t if compressed else {"data": frames.data, "offset": frames.offset, "hw": frames.hw}
         else:
-            pin = self._pinned[slot]
-            if pin is None or pin.shape != frames.shape:
-                pin = torch.empty(frames.shape, dtype=torch.uint8).pin_memory()
-                self._pinned[slot] = pin
-            pin.copy_(frames)
-        flips = None
+            if frames.dtype != torch.uint8:
+                raise ValueError("DevicePrefetcher expects uint8 HWC frames from the loader")
+            named = {"frames": frames}
+        B = len(frames)
+        shape = (B, 3, self.augment.size, self.augment.size) if self.augment is not None else (B, 3) + tuple(frames.shape[1:3])
+        f8 = None
         if self.flip_p > 0 and self.augment is None:
-            r = torch.rand(2, frames.shape[0], generator=self.generator)
+            r = torch.rand(2, B, generator=self.generator)
             f8 = ((r[0] < self.flip_p).to(torch.uint8) | ((r[1] < self.flip_p).to(torch.uint8) << 1))
-            # pinned too: a pageable host-to-device copy is synchronous and would stall the enqueue of the step
-            flips = self._flip_pin[slot]
-            if flips is None or flips.numel() != f8.numel():
-                flips = torch.empty(f8.numel(), dtype=torch.uint8).pin_memory()
-                self._flip_pin[slot] = flips
-            flips.copy_(f8)
-        # device buffers are owned per slot and reused (no allocator traffic on the copy stream): the copy stream first
-        # waits until the consumer's work on the batch that last used this slot has been enqueued AND executed
-        bufs = self._dev[slot]
-        if bufs is None or bufs[0] is None or bufs[0].shape != frames.shape:
-            B, H, W, _ = frames.shape
-            S = self.augment.size if self.augment is not None else None
-            bufs = (torch.empty(frames.shape, dtype=torch.uint8, device=self.device),
-                    torch.empty((B, 3, S, S) if S else (B, 3, H, W), dtype=torch.float32, device=self.device))
-            self._dev[slot] = bufs
+        # the buffers are owned per slot and reused (no allocator traffic on the copy stream in the steady state): the copy stream
+        # first waits until the consumer's work on the batch that last used this slot has been enqueued AND executed
+        out = self._out[slot]
+        if out is None or out.shape != shape:   # (allocated outside the copy stream: it is the consumer's stream that reads it last)
+            out = self._out[slot] = torch.empty(shape, dtype=torch.float32, device=self.device)
         with torch.cuda.stream(self._stream):
             if self._consumed[slot] is not None:
                 self._stream.wait_event(self._consumed[slot])
-            bufs[0].copy_(pin, non_blocking=True)
-            if self.augment is not None:
-                imgs = self._transform(bufs[0], rest, bufs[1])
+            x = self._stage_tensors(slot, named, frames.is_pinned())   # (DataLoader(pin_memory=True): no staging copy)
+            if compressed:
+                x = self._decode(JpegBatch(x, frames.meta))
+            elif ragged:
+                x = RaggedFrames(x["data"], x["offset"], x["hw"], _host=frames._host)
             else:
-                fl = flips.to(self.device, non_blocking=True) if flips is not None else None
-                imgs = preprocess_u8(bufs[0], fl, self.mean, self.std, out=bufs[1])
+                x = x["frames"]
+            if self.augment is not None:
+                imgs = self._transform(x, rest, out, cropped=compressed and self.fused_decode)
+            else:   # (the flags go through pinned memory too: a pageable host-to-device copy is synchronous and would stall the
+                # enqueue of the step)
+                fl = self._stage_tensors(slot, {"flips": f8}, False)["flips"] if f8 is not None else None
+                imgs = preprocess_u8(x, fl, self.mean, self.std, out=out)
             rest_dev = self._rest(rest)
             ev = torch.cuda.Event()
             ev.record(self._stream)

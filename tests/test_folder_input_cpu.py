@@ -135,3 +135,47 @@ def test_ragged_augmenter_refuses_host_frames():
                  lambda: aug(rf), lambda: DevicePerturber("cpu").eval_transform(rf, size=16)):
         with pytest.raises(_lib.PolypMaeError):
             call()
+
+
+@pytest.mark.parametrize("uniform", [False, True])
+def test_check_boxes_accepts_full_frames_and_refuses_each_violation(uniform):
+    """The one crop-box check: per-frame sizes, and a uniform batch's one size broadcast to [B, 2]."""
+    from ssl4polyp_amd.data import _check_boxes, _whole_frame_boxes
+    hw = np.broadcast_to((5, 7), (3, 2)) if uniform else np.array([(5, 7), (4, 4), (9, 2)], dtype=np.int64)
+    full = _whole_frame_boxes(hw)
+    assert full.tolist() == [[0, 0, h, w] for h, w in hw.tolist()]
+    for given in (full, full.astype(np.int64), full.tolist(), np.asfortranarray(full)):
+        got = _check_boxes(given, hw)
+        assert got.dtype == np.int32 and got.flags["C_CONTIGUOUS"] and got.shape == (3, 4) and np.array_equal(got, full)
+    H, W = (int(v) for v in hw[1])
+    for bad in ((0, 0, 0, W),            # h = 0
+                (0, -1, H, 1),           # left = -1
+                (1, 0, H, W),            # top + h = H + 1
+                (0, 1, H, W)):           # left + w = W + 1
+        boxes = full.copy()
+        boxes[1] = bad
+        with pytest.raises(ValueError):
+            _check_boxes(boxes, hw)
+    for wrong_shape in (full[:2], full[:, :3], full.reshape(-1)):
+        with pytest.raises(ValueError):
+            _check_boxes(wrong_shape, hw)
+
+
+def test_scratch_exact_and_grow_on_the_host():
+    """_Scratch without a GPU (upload needs one): grow never shrinks, exact follows shape and dtype."""
+    from ssl4polyp_amd.data import _Scratch
+    sc = _Scratch("cpu")
+    a = sc.grow("ws", 100, torch.uint8)
+    assert a.ndim == 1 and a.numel() >= 100 and a.dtype == torch.uint8 and a.device.type == "cpu"
+    assert sc.grow("ws", 10, torch.uint8).data_ptr() == a.data_ptr() and sc.grow("ws", 10, torch.uint8).numel() == a.numel()
+    assert sc.grow("ws", 100, torch.uint8) is a
+    b = sc.grow("ws", 101, torch.uint8)
+    assert b.numel() >= 101 and b is not a and sc.bufs["ws"] is b
+    assert sc.grow("empty", 0, torch.int16).numel() >= 1   # (a pointer the C entries accept)
+    x = sc.exact("x", (2, 3), torch.uint8)
+    assert x.shape == (2, 3) and sc.exact("x", (2, 3), torch.uint8) is x
+    y = sc.exact("x", (3, 2), torch.uint8)
+    assert y is not x and y.shape == (3, 2)
+    z = sc.exact("x", (3, 2), torch.int32)
+    assert z is not y and z.dtype == torch.int32 and sc.bufs["x"] is z
+    assert sc.exact("other", (3, 2), torch.int32) is not z

@@ -60,6 +60,24 @@ def test_device_prefetcher_order_values_and_flips():
         assert m(imgs).shape == (2, 2)
 
 
+def test_device_prefetcher_flip_flags_through_reused_slots():
+    """Four batches, so both slots stage their flip flags twice: every batch equals the oracle with the flips the same generator
+    calls draw on the host."""
+    from oracle.input_ref import to_tensor_normalize
+    from ssl4polyp_amd.data import DevicePrefetcher
+    g = torch.Generator().manual_seed(21)
+    batches = [(torch.randint(0, 256, (4, 8, 8, 3), dtype=torch.uint8, generator=g), torch.arange(4) + 10 * i) for i in range(4)]
+    g1, g2 = torch.Generator().manual_seed(4), torch.Generator().manual_seed(4)
+    seen, drawn = 0, set()
+    for i, (imgs, labels) in enumerate(DevicePrefetcher(batches, DEV, flip_p=0.5, generator=g1)):
+        r = torch.rand(2, 4, generator=g2)
+        flips = (r[0] < 0.5).to(torch.uint8) | ((r[1] < 0.5).to(torch.uint8) << 1)
+        assert torch.equal(imgs.cpu(), to_tensor_normalize(batches[i][0], flips)) and torch.equal(labels.cpu(), batches[i][1])
+        drawn.add(tuple(flips.tolist()))
+        seen += 1
+    assert seen == 4 and len(drawn) > 1   # (the batches do not all carry the same flags)
+
+
 def test_device_prefetcher_on_the_engines_side_stream_trains_the_same():
     """stream="side" (what a data-parallel rank uses: no fifth busy stream beside RCCL's): the staging thread enqueues the copies and
     the transform on the engine's weight-gradient stream while the main thread enqueues AdamW / weight gradients there -- same batches,

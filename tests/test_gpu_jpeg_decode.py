@@ -146,7 +146,7 @@ def test_corrupt_entropy_data_is_contained_and_deterministic():
     fresh = DeviceJpegDecoder(DEV)
     for name, n, dt in (("coef", jb.meta["blocks"] * 64, torch.int16), ("planes", jb.meta["blocks"] * 64, torch.uint8),
                         ("out", jb.meta["nbytes"], torch.uint8)):
-        fresh._bufs[name] = torch.randint(0, 100, (n,), device=DEV).to(dt)
+        fresh._scratch.bufs[name] = torch.randint(0, 100, (n,), device=DEV).to(dt)
     rf3, _ = _decode(files, fresh)
     assert torch.equal(first, rf3.data)
     for b in (0, 1, 3):

@@ -151,7 +151,7 @@ def test_damaged_streams_equal_the_interval_decoder():
     fresh = DeviceJpegDecoder(DEV, mode="parallel")
     for name, n, dt in (("coef", jb.meta["blocks"] * 64, torch.int16), ("planes", jb.meta["blocks"] * 64, torch.uint8),
                         ("out", jb.meta["nbytes"], torch.uint8), ("workspace", lib_need.value, torch.uint8)):
-        fresh._bufs[name] = torch.randint(0, 256, (n,), device=DEV).to(dt)
+        fresh._scratch.bufs[name] = torch.randint(0, 256, (n,), device=DEV).to(dt)
     rf3, _, _ = _decode(files, fresh)
     assert torch.equal(rf3.data, want)
     for b in (0, 2, 6):

@@ -55,7 +55,7 @@ def test_whole_frame_bilinear_equals_pillow_per_file(files, batch):
     for b, f in enumerate(files):
         want = pil_resized(f, S)
         assert np.array_equal(got[b], want), (b, int((got[b] != want).sum()))
-    assert "out" not in dec._bufs   # no full-size RGB buffer
+    assert "out" not in dec._scratch.bufs   # no full-size RGB buffer
     assert dec.stats()["subsequences"] == batch.meta["n_subseq"]
 
 
@@ -67,7 +67,7 @@ def test_per_frame_boxes_equal_pillow_and_the_sequential_way_out(files, batch):
     for bicubic in (True, False):
         got = dec.resized_crop(batch, boxes, S, bicubic)
         assert torch.equal(seq.resized_crop(batch, boxes, S, bicubic), got)
-        assert torch.equal(two_step._ragged_crop(DeviceJpegDecoder(DEV)(batch), boxes, bicubic, "t"), got)
+        assert torch.equal(two_step._resized_crop(DeviceJpegDecoder(DEV)(batch), boxes, bicubic, "t"), got)
         got = got.cpu().numpy()
         for b, f in enumerate(files):
             want = pil_resized(f, S, boxes[b], bicubic)
@@ -120,7 +120,7 @@ def test_c_entry_refuses_bad_arguments(files, batch):
     lib = _lib.load()
     dec = DeviceJpegDecoder(DEV)
     boxes = _whole(SIZES)
-    want = dec.resized_crop(batch, boxes, S, False).clone()   # (leaves the decoded planes in dec._bufs["planes"])
+    want = dec.resized_crop(batch, boxes, S, False).clone()   # (leaves the decoded planes in dec._scratch.bufs["planes"])
     B, t, m = 10, batch.t, batch.meta
     Hm, Wm = int(m["hw"][:, 0].max()), int(m["hw"][:, 1].max())
     need = ctypes.c_size_t(0)
@@ -135,7 +135,7 @@ def test_c_entry_refuses_bad_arguments(files, batch):
     source = torch.tensor([0, 1, 2, 3, 4, 5, 6, 7, -1, -2], dtype=torch.int32, device=DEV)
     box = torch.from_numpy(boxes).to(DEV)
     st = torch.cuda.current_stream(DEV).cuda_stream
-    planes = dec._bufs["planes"]
+    planes = dec._scratch.bufs["planes"]
 
     def call(**kw):
         g = lambda k, v: kw.get(k, v)
@@ -158,11 +158,11 @@ def test_c_entry_refuses_bad_arguments(files, batch):
     # the planes-only decode entry validates as pm_jpeg_decode_parallel does
     assert lib.pm_jpeg_decode_planes(t["entropy"].data_ptr(), t["entropy"].numel(), t["intervals"].data_ptr(), t["intervals"].shape[0],
                                      t["frames"].data_ptr(), 8, t["huff"].data_ptr(), t["huff"].shape[0], t["quant"].data_ptr(),
-                                     t["quant"].shape[0], dec._bufs["coef"].data_ptr(), planes.data_ptr(), m["blocks"],
+                                     t["quant"].shape[0], dec._scratch.bufs["coef"].data_ptr(), planes.data_ptr(), m["blocks"],
                                      t["subseq"].data_ptr(), t["subseq"].numel(), 9, ws.data_ptr(), ws.numel(), None, st) == _lib.PM_ESHAPE
     assert lib.pm_jpeg_decode_planes(t["entropy"].data_ptr(), t["entropy"].numel(), t["intervals"].data_ptr(), t["intervals"].shape[0],
                                      t["frames"].data_ptr(), 8, t["huff"].data_ptr(), t["huff"].shape[0], t["quant"].data_ptr(),
-                                     t["quant"].shape[0], dec._bufs["coef"].data_ptr(), planes.data_ptr(), m["blocks"],
+                                     t["quant"].shape[0], dec._scratch.bufs["coef"].data_ptr(), planes.data_ptr(), m["blocks"],
                                      t["subseq"].data_ptr(), t["subseq"].numel(), 2, ws.data_ptr(), 16, None, st) == _lib.PM_EINVAL
 
 
@@ -181,7 +181,7 @@ def test_prefetcher_fused_decode_yields_the_unfused_images(tmp_path, files):
             pf = DevicePrefetcher(ld, DEV, augment=DeviceAugmenter(DEV, size=S), transform=transform, fused_decode=fused,
                                   generator=torch.Generator().manual_seed(5))
             runs.append([x.clone() for x, _ in pf])
-            assert ("out" in pf._decoder._bufs) == (not fused)   # the fused run never allocates the full-size RGB output
+            assert ("out" in pf._decoder._scratch.bufs) == (not fused)   # the fused run never allocates the full-size RGB output
         assert [tuple(x.shape) for x in runs[0]] == [(4, 3, S, S), (4, 3, S, S), (2, 3, S, S)]
         assert all(torch.equal(a, b) for a, b in zip(*runs)), transform
     # "eval" is the plain transform: Pillow's resize of every file, ToTensor, Normalize

@@ -147,7 +147,7 @@ def test_prefetcher_over_an_image_folder_mae_transform(tmp_path):
     def run(seed):
         pf = DevicePrefetcher(ld, DEV, augment=DeviceAugmenter(DEV), transform="mae", generator=torch.Generator().manual_seed(seed))
         out = [(x.clone(), y.clone()) for x, y in pf]
-        assert pf._ragged_pin == [None, None]   # the loader pinned the batches: no second staging copy
+        assert pf._pin == [{}, {}]   # the loader pinned the batches: no second staging copy
         return out
     a, b = run(7), run(7)
     assert len(a) == len(order) // B == 3
@@ -176,14 +176,45 @@ def test_prefetcher_ragged_staging_buffers_only_grow():
     for i, (x, y) in enumerate(pf):
         assert x.shape == (2, 3, 224, 224) and torch.equal(y.cpu(), torch.arange(2) + i)
         if i == 1:   # both slots have staged a big batch
-            ptrs = [(pf._ragged_pin[s][0].data_ptr(), pf._ragged_dev[s][0].data_ptr()) for s in (0, 1)]
+            ptrs = [(pf._pin[s]["data"].data_ptr(), pf._dev[s]["data"].data_ptr()) for s in (0, 1)]
         n += 1
     assert n == 5
     nbig = batches[0][0].data.numel()
     for s in (0, 1):
-        assert (pf._ragged_pin[s][0].data_ptr(), pf._ragged_dev[s][0].data_ptr()) == ptrs[s]
-        assert pf._ragged_pin[s][0].numel() == pf._ragged_dev[s][0].numel() == nbig
-    assert pf.augment._bufs["rrc_ws"].numel() >= 1
+        assert (pf._pin[s]["data"].data_ptr(), pf._dev[s]["data"].data_ptr()) == ptrs[s]
+        assert pf._pin[s]["data"].numel() == pf._dev[s]["data"].numel() == nbig
+    assert pf.augment._scratch.bufs["crop_ws"].numel() >= 1
+
+
+def test_prefetcher_mixed_batch_kinds_share_slots():
+    """Uniform, ragged and compressed batches interleaved through one prefetcher, whose two slots keep their staging buffers by
+    name: two kinds carry arrays called `offset` and `hw`, the uniform frames share a name with the int32 `frames` table of a
+    compressed batch, batch sizes change between the visits of a slot and a smaller batch follows a larger one of its kind.
+    transform="eval" draws nothing, so every batch must come out as a fresh prefetcher yields it alone -- decoded in two steps
+    or fused."""
+    from pack_files import encode
+    from ssl4polyp_amd.data import DeviceAugmenter, DevicePrefetcher, RaggedFrames
+    from ssl4polyp_amd.jpeg import JpegBatch
+    jpg = lambda H, W, seed: encode(_frame(H, W, seed), quality=90)
+    ragged = lambda: RaggedFrames.from_frames([_frame(40, 56, 3), _frame(64, 48, 4)])
+    jb3 = JpegBatch.from_bytes([jpg(48, 64, 5), jpg(33, 47, 6), encode(_frame(30, 20, 7), "png")])
+    jb2 = JpegBatch.from_bytes([jpg(33, 47, 8), jpg(16, 24, 9)])
+    assert jb3.meta["fallback"] == [2] and jb2.meta["fallback"] == []
+    g = torch.Generator().manual_seed(12)
+    frames = [torch.randint(0, 256, (3, 48, 64, 3), dtype=torch.uint8, generator=g), ragged(), jb3,
+              torch.randint(0, 256, (2, 32, 32, 3), dtype=torch.uint8, generator=g), ragged(), jb2]
+    batches = [(f, torch.arange(len(f)) + i) for i, f in enumerate(frames)]
+
+    def run(loader, fused=False):
+        pf = DevicePrefetcher(loader, DEV, augment=DeviceAugmenter(DEV, size=32), transform="eval", fused_decode=fused)
+        return [(x.clone(), y.clone()) for x, y in pf]
+    alone = [run([b])[0] for b in batches]
+    for fused in (False, True):
+        mixed = run(batches, fused)
+        assert len(mixed) == 6
+        for i, ((x, y), (xa, ya)) in enumerate(zip(mixed, alone)):
+            assert x.shape == (len(frames[i]), 3, 32, 32) and torch.equal(x, xa), (fused, i)
+            assert torch.equal(y.cpu(), batches[i][1]) and torch.equal(ya.cpu(), batches[i][1]), (fused, i)
 
 
 def test_main_pretrain_from_an_image_folder(tmp_path):
