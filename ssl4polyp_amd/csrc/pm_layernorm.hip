@@ -5,6 +5,7 @@
 // per lane is a template parameter), f32 statistics, two-pass variance.
 // Algorithmic bytes per row: fwd 4D (x) + sizeof(act)*D (y); bwd sizeof(act)*D (dy) + 4D (x) + 4D (dres)
 // + 4D (dx) + sizeof(act)*D (dx_act).
+#include <stdlib.h>
 #include "pm_common.h"
 
 namespace {
@@ -66,127 +67,132 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
   }
 }
 
-template <typename TDy, typename TAct, int NV>
-__global__ __launch_bounds__(256) void ln_bwd_kernel(const TDy* __restrict__ dy, const float* __restrict__ x, long ldx,
-                                                     const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                     const float* __restrict__ rstd, const float* __restrict__ dres,
-                                                     long lddres, float* __restrict__ dx, long lddx,
-                                                     TAct* __restrict__ dx_act, float* __restrict__ dgamma,
-                                                     float* __restrict__ dbeta, float* __restrict__ dcolsum,
-                                                     float* __restrict__ partials, int M, int D) {
-  __shared__ float red[3][4][256 + 4];  // [vector][wave][lane*4 + e] per vec slot, reused per slot
+// Backward.  One wave64 per row, rows gw, gw + W, gw + 2W, ... for wave gw of W = 4 * gridDim.x: which wave handles which row is a
+// pure function of (M, grid), so the column sums are run-to-run deterministic.  One row is under arithmetic at a time while the
+// next row's loads are in flight: the wave issues row r + W (x, dy, dres, mean, rstd) before the reductions and stores of row r,
+// and dy stays in its 16-bit form until it is used.  What does not change from row to row lives in LDS, not in registers: gamma
+// (read at each use) and the wave's three column accumulators (read-modify-write of the wave's own 16-byte-per-lane slots, no
+// bank conflicts; 18 LDS instructions of 1 KB per row against 12 KB of HBM traffic).  That brings D <= 768 to at most 118 VGPRs
+// and 39 KB of LDS per workgroup, i.e. 4 waves per SIMD, where two full f32 working sets and the accumulators took 182 VGPRs
+// (2 waves); D = 1024 holds 3 and D = 1280 holds 2 (242 and 266 registers, 2 and 1 before).
+// `dres` may alias `dx` row for row (so neither is `__restrict__`): a prefetched row is never the row being stored, and the loads
+// of a row precede its own store by data dependence.  kRes: the launch has a residual (`dres` != NULL).  The launch bound is the
+// minimum number of waves per SIMD the register allocator must leave room for.
+template <typename TDy, typename TAct, int NV, bool kRes>
+__global__ __launch_bounds__(256, NV <= 3 ? 4 : 1) void ln_bwd_kernel(const TDy* __restrict__ dy, const float* __restrict__ x, long ldx,
+                                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                                      const float* __restrict__ rstd, const float* dres, long lddres,
+                                                                      float* dx, long lddx, TAct* __restrict__ dx_act,
+                                                                      float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                      float* __restrict__ dcolsum, float* __restrict__ partials,
+                                                                      int M, int D) {
+  __shared__ f32x4 gam[NV * 64];
+  __shared__ f32x4 acc[3][4][NV * 64];  // [dgamma | dbeta | dcolsum][wave][column / 4]: each wave's column sums, touched by it alone
   constexpr int kMaxVec = NV;  // f32x4 slots per lane for this D (shadows the file-scope bound): D <= 256 * NV
+  typedef TDy __attribute__((ext_vector_type(4))) Dy4;  // dy as loaded: 8 bytes per slot for the 16-bit types
   const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: row addresses and mean / rstd stay scalar
   const int nvec = D >> 2;
-  f32x4 g[kMaxVec];
-  f32x4 acc_g[kMaxVec], acc_b[kMaxVec], acc_c[kMaxVec];
+  const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+  for (int c = threadIdx.x; c < kMaxVec * 64; c += 256) gam[c] = (c < nvec) ? *reinterpret_cast<const f32x4*>(gamma + 4 * c) : z;
 #pragma unroll
   for (int i = 0; i < kMaxVec; ++i) {
-    const int c = lane + 64 * i;
-    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    g[i] = (c < nvec) ? *reinterpret_cast<const f32x4*>(gamma + 4 * c) : z;
-    acc_g[i] = z;
-    acc_b[i] = z;
-    acc_c[i] = z;
+    acc[0][wave][lane + 64 * i] = z;
+    acc[1][wave][lane + 64 * i] = z;
+    acc[2][wave][lane + 64 * i] = z;
   }
+  __syncthreads();
   const float invD = 1.0f / (float)D;
-  // Two rows per wave per iteration: their loads and the two shuffle-reduction chains are independent, which is the
-  // instruction-level parallelism this latency-bound loop was missing (one wave otherwise serialises
-  // load -> 2 x 6 shuffles -> store per row).
   const long stride = (long)gridDim.x * 4;
-  for (long row0 = (long)blockIdx.x * 4 + wave; row0 < M; row0 += 2 * stride) {
-    long rows[2] = {row0, row0 + stride};
-    const bool valid[2] = {true, rows[1] < M};
-    if (!valid[1]) rows[1] = row0;  // harmless duplicate loads; contributions and stores are suppressed below
-    float mu[2], rs[2], s1[2] = {0.f, 0.f}, s2[2] = {0.f, 0.f};
-    f32x4 xh[2][kMaxVec], dv[2][kMaxVec], dr[2][kMaxVec];
+  long row = (long)blockIdx.x * 4 + wave;
+  // the row in flight
+  f32x4 nx[kMaxVec], ndr[kMaxVec];
+  Dy4 ndy[kMaxVec];
+  float nmu = 0.f, nrs = 0.f;
+  auto fetch = [&](long r) {
+    nmu = mean[r];
+    nrs = rstd[r];
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      mu[u] = mean[rows[u]];
-      rs[u] = rstd[rows[u]];
-#pragma unroll
-      for (int i = 0; i < kMaxVec; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nvec) {
-          xh[u][i] = *reinterpret_cast<const f32x4*>(x + rows[u] * ldx + 4 * c);
-          dv[u][i] = load4<TDy>(dy + rows[u] * (long)D + 4 * c);
-          if (dres) dr[u][i] = *reinterpret_cast<const f32x4*>(dres + rows[u] * lddres + 4 * c);
-        }
+    for (int i = 0; i < kMaxVec; ++i) {
+      const int c = lane + 64 * i;
+      if (i < kMaxVec - 1 || c < nvec) {  // only the last slot can be ragged: D > 256 * (NV - 1)
+        nx[i] = *reinterpret_cast<const f32x4*>(x + r * ldx + 4 * c);
+        ndy[i] = *reinterpret_cast<const Dy4*>(dy + r * (long)D + 4 * c);
+        if (kRes) ndr[i] = *reinterpret_cast<const f32x4*>(dres + r * lddres + 4 * c);
       }
     }
+  };
+  if (row < M) fetch(row);  // a wave without a row loads nothing
+  while (row < M) {
+    const float mu = nmu, rs = nrs;
+    f32x4 xh[kMaxVec], dr[kMaxVec];
+    Dy4 dv[kMaxVec];
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const float live = valid[u] ? 1.0f : 0.0f;
+    for (int i = 0; i < kMaxVec; ++i) {
+      const int c = lane + 64 * i;
+      if (i < kMaxVec - 1 || c < nvec) {  // only the last slot can be ragged: D > 256 * (NV - 1)
 #pragma unroll
-      for (int i = 0; i < kMaxVec; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nvec) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            xh[u][i][e] = (xh[u][i][e] - mu[u]) * rs[u];
-            const float gg = dv[u][i][e] * g[i][e];
-            s1[u] += gg;
-            s2[u] += gg * xh[u][i][e];
-            acc_g[i][e] += live * dv[u][i][e] * xh[u][i][e];
-            acc_b[i][e] += live * dv[u][i][e];
-          }
-        }
+        for (int e = 0; e < 4; ++e) xh[i][e] = (nx[i][e] - mu) * rs;
+        dv[i] = ndy[i];
+        if (kRes) dr[i] = ndr[i];
       }
     }
-    float c1[2], c2[2];
+    const long next = row + stride;
+    if (next < M) fetch(next);  // under this row's reductions and stores
+    float s1 = 0.f, s2 = 0.f;
 #pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      c1[u] = s1[u];
-      c2[u] = s2[u];
-    }
+    for (int i = 0; i < kMaxVec; ++i) {
+      const int c = lane + 64 * i;
+      if (i < kMaxVec - 1 || c < nvec) {  // only the last slot can be ragged: D > 256 * (NV - 1)
+        const f32x4 g = gam[c];
+        f32x4 ag = acc[0][wave][c], ab = acc[1][wave][c];
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {  // the four reductions interleaved
-      c1[0] += __shfl_xor(c1[0], o, 64);
-      c1[1] += __shfl_xor(c1[1], o, 64);
-      c2[0] += __shfl_xor(c2[0], o, 64);
-      c2[1] += __shfl_xor(c2[1], o, 64);
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (!valid[u]) continue;
-      const float k1 = c1[u] * invD, k2 = c2[u] * invD;
-#pragma unroll
-      for (int i = 0; i < kMaxVec; ++i) {
-        const int c = lane + 64 * i;
-        if (c < nvec) {
-          f32x4 o;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = rs[u] * (dv[u][i][e] * g[i][e] - k1 - xh[u][i][e] * k2);
-          if (dres) o += dr[u][i];
-          *reinterpret_cast<f32x4*>(dx + rows[u] * lddx + 4 * c) = o;
-          if (dx_act) store4<TAct>(dx_act + rows[u] * (long)D + 4 * c, o);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) acc_c[i][e] += o[e];
+        for (int e = 0; e < 4; ++e) {
+          const float d = (float)dv[i][e];
+          const float gg = d * g[e];
+          s1 += gg;
+          s2 += gg * xh[i][e];
+          ag[e] = __builtin_fmaf(d, xh[i][e], ag[e]);  // fused in every slot (left to contraction, the guarded slot got mul + add)
+          ab[e] += d;
         }
+        acc[0][wave][c] = ag;
+        acc[1][wave][c] = ab;
       }
+      __builtin_amdgcn_sched_barrier(0);  // one slot's gamma and f32 dy live at a time
     }
+    float c1 = s1, c2 = s2;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {  // the two reductions interleaved
+      c1 += __shfl_xor(c1, o, 64);
+      c2 += __shfl_xor(c2, o, 64);
+    }
+    const float k1 = c1 * invD, k2 = c2 * invD;
+#pragma unroll
+    for (int i = 0; i < kMaxVec; ++i) {
+      const int c = lane + 64 * i;
+      if (i < kMaxVec - 1 || c < nvec) {  // only the last slot can be ragged: D > 256 * (NV - 1)
+        const f32x4 g = gam[c];
+        f32x4 o;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] = rs * ((float)dv[i][e] * g[e] - k1 - xh[i][e] * k2);
+        if (kRes) o += dr[i];
+        *reinterpret_cast<f32x4*>(dx + row * lddx + 4 * c) = o;
+        if (dx_act) store4<TAct>(dx_act + row * (long)D + 4 * c, o);
+        acc[2][wave][c] += o;
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    row = next;
   }
-  // cross-wave reduction of the column partials, then one atomic per column per block
+  // cross-wave reduction of the column partials, then one partial row (or one atomic per column) per block
+  __syncthreads();
 #pragma unroll
   for (int i = 0; i < kMaxVec; ++i) {
     const int c = lane + 64 * i;
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      red[0][wave][lane * 4 + e] = acc_g[i][e];
-      red[1][wave][lane * 4 + e] = acc_b[i][e];
-      red[2][wave][lane * 4 + e] = acc_c[i][e];
-    }
-    __syncthreads();
-    if (wave < 3 && c < nvec) {
+    if (wave < 3 && (i < kMaxVec - 1 || c < nvec)) {
       float* dst = wave == 0 ? dgamma : (wave == 1 ? dbeta : dcolsum);
       if (dst) {
-        f32x4 t;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          t[e] = (red[wave][0][lane * 4 + e] + red[wave][1][lane * 4 + e]) +
-                 (red[wave][2][lane * 4 + e] + red[wave][3][lane * 4 + e]);
+        const f32x4 t = (acc[wave][0][c] + acc[wave][1][c]) + (acc[wave][2][c] + acc[wave][3][c]);
         if (partials) {  // two-stage: plain store of this block's partial row, summed by ln_bwd_reduce_kernel
           *reinterpret_cast<f32x4*>(partials + ((long)blockIdx.x * 3 + wave) * D + 4 * c) = t;
         } else {         // no workspace: one atomic per column per block (contended when the grid is large)
@@ -221,11 +227,17 @@ __global__ __launch_bounds__(1024) void ln_bwd_reduce_kernel(const float* __rest
   }
 }
 
-inline int ln_grid(int M) {
-  int g = (M + 3) / 4;
-  return g < 1 ? 1 : (g > 1024 ? 1024 : g);
+// A/B switch, read once: PM_LN_BWD_BLOCKS = most workgroups of one ln_bwd_kernel launch (64 .. 1024, default kLnBwdBlocks); the
+// workspace the caller passes bounds it further.  Another bound is another (still deterministic) association of the column sums.
+constexpr int kLnBwdBlocks = 1024;
+int ln_bwd_max_blocks() {
+  static const int v = [] {
+    const char* e = getenv("PM_LN_BWD_BLOCKS");
+    const int n = e && e[0] ? atoi(e) : kLnBwdBlocks;
+    return n < 64 ? 64 : (n > 1024 ? 1024 : n);
+  }();
+  return v;
 }
-
 }  // namespace
 
 extern "C" int pm_layernorm_fwd(const float* x, long ldx, const float* gamma, const float* beta, void* y, int out_dtype,
@@ -249,23 +261,28 @@ extern "C" int pm_layernorm_bwd(const void* dy, int dy_dtype, const float* x, lo
   if (!dy || !x || !gamma || !mean || !rstd || !dx) return PM_EINVAL;
   if (M <= 0 || D <= 0 || D > kMaxD || (D & 3) || (ldx & 3) || (lddx & 3) || (dres && (lddres & 3))) return PM_ESHAPE;
   if (dx_act && act_dtype != dy_dtype) return PM_EINVAL;
-  int grid = (M + 3) / 4;
+  int cap = 256;  // atomics fallback: keep the number of contending blocks low
   float* partials = nullptr;
   const bool want_sums = dgamma || dbeta || dcolsum;
   if (want_sums && workspace && ws_bytes >= (size_t)64 * 3 * D * sizeof(float)) {
-    int cap = (int)(ws_bytes / ((size_t)3 * D * sizeof(float)));
-    if (cap > 1024) cap = 1024;
-    if (grid > cap) grid = cap;
+    const size_t fit = ws_bytes / ((size_t)3 * D * sizeof(float));
+    cap = ln_bwd_max_blocks();
+    if ((size_t)cap > fit) cap = (int)fit;
     partials = reinterpret_cast<float*>(workspace);
-  } else if (grid > 256) {
-    grid = 256;  // atomics fallback: keep the number of contending blocks low
+  } else if (!want_sums) {
+    cap = ln_bwd_max_blocks();
   }
-  if (grid < 1) grid = 1;
+  // the parent kernel's grid and row assignment (wave gw of 4 * grid takes rows gw, gw + 4 * grid, ...): with the fixed order inside
+  // a wave, a workgroup and ln_bwd_reduce_kernel, the column sums come out bit for bit as before the rows went in flight
+  const int grid = (M + 3) / 4 < cap ? (M + 3) / 4 : cap;
   hipStream_t s = pm_stream(stream);
   const int nv = (D + 255) / 256;  // f32x4 slots per lane: 3 for D = 768, 2 for 512
 #define PM_LN_BWD(TD, NV)                                                                                               \
-  hipLaunchKernelGGL((ln_bwd_kernel<TD, TD, NV>), dim3(grid), dim3(256), 0, s, (const TD*)dy, x, ldx, gamma, mean, rstd, \
-                     dres, lddres, dx, lddx, (TD*)dx_act, dgamma, dbeta, dcolsum, partials, M, D)
+  do {                                                                                                                   \
+    auto kern = dres ? ln_bwd_kernel<TD, TD, NV, true> : ln_bwd_kernel<TD, TD, NV, false>;                               \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, s, (const TD*)dy, x, ldx, gamma, mean, rstd, dres, lddres, dx, lddx, \
+                       (TD*)dx_act, dgamma, dbeta, dcolsum, partials, M, D);                                             \
+  } while (0)
   PM_DISPATCH_ACT(dy_dtype, T, {
     if (nv == 1) PM_LN_BWD(T, 1); else if (nv == 2) PM_LN_BWD(T, 2); else if (nv == 3) PM_LN_BWD(T, 3);
     else if (nv == 4) PM_LN_BWD(T, 4); else PM_LN_BWD(T, 5);
