@@ -87,8 +87,13 @@ int pm_gemm_ws(const void* A, long lda, int a_kmajor, const void* B, long ldb, i
  *   max_blocks: workgroups a split-K weight-gradient GEMM (both operands k-major) spreads over; 0 = 256 = the whole
  *               chip (fastest alone).  A caller that runs weight gradients on a second stream beside the dgrad chain
  *               passes ~128 so that the chain keeps half of the CUs (the training engine does: +4.5 % step rate).
- *   variant:    0 = the dispatcher's heuristics; otherwise forces one kernel variant (tuning scripts and tests; the
- *               values are listed in pm_gemm.hip and are not stable across ABI versions). */
+ *   variant:    the one per-call override of the kernel choice (tests, tuning scripts); it names shipped kernels only.
+ *               Bits 0-5: 0 = the dispatcher's heuristics; 1 = the 128x128 kernels; 8, 9, 10, 24, 25, 26 = that ring-kernel
+ *               configuration for a problem that fits the ring kernel (16-bit operands, A k-normal, K % 32 == 0,
+ *               M >= 1024) -- this also switches the few-tiles rule off.  Bits 6-7: tile of a ring weight gradient (both
+ *               operands k-major), 0 = heuristics, 1 = 256x128, 2 = 256x256.  Any other value, or a ring configuration
+ *               that is not built for the call's B layout (9, 10, 25, 26 exist for k-normal B only), returns PM_EINVAL.
+ *               The values are not stable across ABI versions. */
 typedef struct pm_gemm_opts {
   int max_blocks;
   int variant;
@@ -96,6 +101,25 @@ typedef struct pm_gemm_opts {
 int pm_gemm_ex(const void* A, long lda, int a_kmajor, const void* B, long ldb, int b_kmajor, int in_dtype,
                const float* bias, void* C, long ldc, int c_dtype, int epilogue, void* aux, const float* resid,
                int M, int N, int K, void* workspace, size_t ws_bytes, const pm_gemm_opts* opts, void* stream);
+
+/* The dispatcher's plan for a GEMM WITHOUT launching: returns the status pm_gemm_ex would return for these layouts, types,
+ * shapes and options (PM_OK, PM_ESHAPE, PM_EALIGN, PM_EINVAL; pointers and leading dimensions are not seen, so their
+ * checks are not made) and, when PM_OK, fills *info.  has_bias: bias != NULL; ldc_is_n: ldc == N; ws_bytes: the scratch
+ * the call would pass (0 = none).  A host engine or a test uses it to know which kernel a Linear runs on. */
+#define PM_GEMM_GENERIC 0    /* 128x128, register-staged, any K % chunk == 0 */
+#define PM_GEMM_LDS128 1     /* 128x128, LDS-DMA, optional split-K */
+#define PM_GEMM_RING 2       /* large-tile ring kernel (forward / dgrad) */
+#define PM_GEMM_RING_WGRAD 3 /* large-tile ring kernel, both operands k-major, split-K */
+typedef struct pm_gemm_plan_info {
+  int family;        /* PM_GEMM_* */
+  int cfg;           /* ring configuration (pm_gemm_opts.variant bits 0-5), 0 for the other families */
+  int tile_m, tile_n;
+  int split_k;       /* k-slices (1 = none); > 1: f32 slabs in the workspace and a reduce launch */
+  int band;          /* PM_GEMM_RING: tile columns per band of the tile order (0 = row by row) */
+  size_t ws_bytes;   /* scratch the plan uses */
+} pm_gemm_plan_info;
+int pm_gemm_plan(int a_kmajor, int b_kmajor, int in_dtype, int has_bias, int c_dtype, int ldc_is_n, int epilogue, int M, int N,
+                 int K, size_t ws_bytes, const pm_gemm_opts* opts, pm_gemm_plan_info* info);
 
 /* Every weight gradient of one transformer block in ONE launch (autograd of timm Block's four Linears: attn.qkv,
  * attn.proj, mlp.fc1, mlp.fc2 -- models_mae.py:39-41,53-55 through engine_pretrain.py:65 / tc.py:4533):

@@ -17,7 +17,7 @@
 //   -> forward: X k-normal, W k-normal;  dgrad: dY k-normal, W (as stored [out][in]) k-major;
 //      wgrad: dY k-major (M side = out features), X k-major (N side = in features).
 //
-// Three kernels:
+// Three GEMM kernels:
 //   gemm_v3_kernel (below, "large-tile path"): the bf16 workhorse of the training step -- 256x256 / 192x256 / 256x128
 //     block tiles, 8 waves, 4-slot LDS-DMA ring, ping-pong or software-pipelined k-loop, batched-load / 16-B-store
 //     epilogues; forward, dgrad and split-K wgrad of every ViT-B shape go through it.
@@ -30,10 +30,18 @@
 //     Epilogue: each wave stages its 64x64 accumulators through LDS and leaves as whole 16-B vectors along n
 //     (bias / GELU / dGELU / residual applied on the way out) -> fully coalesced stores.
 //   gemm_generic_kernel (any K % chunk == 0): register-staged, fully predicated loads (tiny / odd shapes).
+// wgrad_group_kernel runs the ring kernel's tile body over the weight gradients of a whole transformer block in one launch.
+//
+// Host side: plan_gemm is a pure function of a call's layouts, types, epilogue, shapes, scratch size and pm_gemm_opts; it
+// returns the refusal or the kernel family, ring configuration, tile, split-K and tile order (pm_gemm_plan exposes it, so "which
+// kernel runs for this Linear" is checked on the CPU: tests/golden/gemm_plan.json).  gemm_dispatch validates the pointers, plans
+// and launches what the plan says; pm_gemm_workspace_bytes is the same plan with unlimited scratch.  The ring configurations are
+// one table (kRingCfgs) read by the plan and by the launcher: only what the heuristics can choose is instantiated, and
+// pm_gemm_opts.variant, the one per-call override, can name nothing else.  No environment variable is read here; the thresholds
+// are named constants beside their rules.  The variants that were measured and removed: docs/EXPERIMENT_LOG.md.
 // Roofline: MFMA-bound; algorithmic FLOPs 2*M*N*K.
 #include "pm_common.h"
 #include <type_traits>
-#include <stdio.h>
 
 namespace {
 
@@ -61,9 +69,8 @@ struct GemmArgs {
   int ksteps_split;  // k-steps per split
   float* xsum;         // grouped wgrad: xsum[m] += sum_k X(m, k) (= the bias gradient: column sums of dY), or NULL
   int xsum_store;      // xsum[m] = ... instead of += (partial row sums of a k-slice, reduced later)
-  int epi_hoist;       // gemm_glds_kernel: the sixteen epilogue loads of a wave tile in one batch (0: one load -> store chain per vector)
   int col_major;       // tile index -> (tm, tn): 0 row by row, 1 column by column (grouped wgrad: see wgrad_group_kernel), >= 2: row by
-                       // row inside bands of that many tile columns (wide-N GEMMs: see gemm_dispatch)
+                       // row inside bands of that many tile columns (wide-N GEMMs: see plan_gemm)
 #ifdef PM_GEMM_STAMP
   unsigned long long* stamps;  // diagnostic build only: per-wave cycle sums of the k-loop segments
 #endif
@@ -204,28 +211,6 @@ __device__ __forceinline__ void mma_kstep(const char* bx, const char* bw, int wm
 #pragma unroll
       for (int j = 0; j < 2; ++j) acc[i][j] = mfma16B<T>(fw[i], fx[j], acc[i][j]);
   }
-}
-
-// The 32x32x16 MFMA of the ring kernels' k-loops.  Diagnostic build -DPM_MFMA16_TIMING (scratch/mfma16_timing.sh): the same
-// operand registers feed TWO v_mfma_f32_16x16x32_bf16 (same FLOPs, same pipe cycles: 2 x 16 = 32) on two quarters of the
-// accumulator -- the results are WRONG (the fragment maps differ), the build only answers "what clock does the chip hold on
-// this k-loop with the other MFMA shape" (MI355X_MICROARCH.md, DVFS give-back item 7).  Never shipped.
-template <typename E>
-__device__ __forceinline__ void ring_mfma(const Frag16& a, const Frag16& b, f32x16& acc, int kk) {
-#ifdef PM_MFMA16_TIMING
-  f32x4 lo = {acc[8 * kk], acc[8 * kk + 1], acc[8 * kk + 2], acc[8 * kk + 3]};
-  f32x4 hi = {acc[8 * kk + 4], acc[8 * kk + 5], acc[8 * kk + 6], acc[8 * kk + 7]};
-  lo = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.h, lo, 0, 0, 0);
-  hi = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.h, b.h, hi, 0, 0, 0);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    acc[8 * kk + e] = lo[e];
-    acc[8 * kk + 4 + e] = hi[e];
-  }
-#else
-  (void)kk;
-  acc = mfma16B<E>(a, b, acc);
-#endif
 }
 
 // XCD-aware tile order: the 8 XCDs take blocks round-robin; give each XCD a contiguous run of tiles so
@@ -406,7 +391,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_glds_kernel(GemmArgs a) {
   const int epi = split ? PM_EPI_STORE : a.epilogue;
   float* slab = split ? reinterpret_cast<float*>(a.C) + (long)blockIdx.y * a.M * a.ldc : nullptr;
   const int mw = m0 + wm * 64, nw = n0 + wn * 64;
-  if (!split && a.epi_hoist && (sizeof(T) == 2 || a.c_dtype == PM_F32)) {  // (f32 operands with a 16-bit C: the per-vector path below)
+  if (!split && (sizeof(T) == 2 || a.c_dtype == PM_F32)) {  // (f32 operands with a 16-bit C: the per-vector path below)
     // every load the epilogue needs for the wave's 64 x 64 tile (f32 residual / C, or the saved pre-activation) is issued before the
     // first store: one exposed trip to memory per tile instead of sixteen load -> store chains (the compiler cannot hoist a load over
     // a store that may alias it).  Clamped addresses for rows / columns beyond M / N, the stores are gated.
@@ -533,41 +518,34 @@ __global__ __launch_bounds__(kThreads, 2) void gemm_generic_kernel(GemmArgs a) {
 // (or 256x128) outputs = 128 FLOP/B, a k-step is 32 elements (64-B rows: 4 chunks, XOR-swizzled by (row>>2)&3),
 // and 4 ring slots keep 3 stages (96 KiB / CU) in flight behind a COUNTED s_waitcnt vmcnt(N) and a raw
 // s_barrier (one per k-step): the DMA of stages t+1, t+2 overlaps the MFMAs of stage t.
-// Wave layout WM x WN; per-wave tile (BM/WM) x (BN/WN) = 128x64 (256^2) or 64x64 (256x128):
-// 12 / 8 ds_read_b128 per 16 / 8 MFMAs per k-step.
-constexpr int V3_STAGES = 4;
+// 8 waves in WM x WN = 2 x 4 (256-wide tiles) or 4 x 2 (128-wide); per-wave tile (BM/WM) x (BN/WN) = 128x64, 96x64 (192-row
+// tiles) or 64x64 (256x128): 12 / 8 ds_read_b128 per 16 / 8 MFMAs per k-step.
+constexpr int V3_STAGES = 4;                 // ring slots
 constexpr int V3_KE = 32;                    // bf16 elements of k per stage
 constexpr int V3_STAGE_WAVE = 64 * STAGE_ROW;  // epilogue staging per wave (64 rows x 64 f32, padded)
 
-// One 1-KiB LDS-DMA piece j of a k-normal tile (16 rows x 64 B; the lane's SOURCE chunk is the inverse swizzle of its slot).
-// XOR applied to the 16-B chunk index of row `row` of a k-normal stage image (64-B rows).  S16 = false: the 32x32x16 operand
-// read (lane = row l & 31, k-half l >> 5); S16 = true: the 16x16x32 operand read (lane = row l & 15, chunk l >> 4), for which
-// rows 4q .. 4q+3 take XOR {0, 0, 3, 3}[q]: every 16-lane group of the ds_read_b128 then covers all 16 bank slots once.
-template <bool S16> __device__ __forceinline__ int v3_swz_kn(int row) {
-  const int q = (row >> 2) & 3;
-  if constexpr (S16) return (q >> 1) * 3;
-  else return q;
-}
+constexpr int V3_WAVES = 8;                  // waves per workgroup: two per SIMD
 
-template <bool S16 = false>
+// One 1-KiB LDS-DMA piece j of a k-normal tile (16 rows x 64 B; the lane's SOURCE chunk is the inverse swizzle of its slot:
+// 16-B chunk c of row r sits at c ^ ((r >> 2) & 3), conflict-free for the 32x32x16 operand read of v3_frag_kn).
 __device__ __forceinline__ void v3_piece_kn(char* tile, const __bf16* __restrict__ base, long ld, int r0, int R, int k0,
                                             int j, int lane) {
   const int row = 16 * j + (lane >> 2), cs = lane & 3;
-  const int c = cs ^ v3_swz_kn<S16>(row);
+  const int c = cs ^ ((row >> 2) & 3);
   int gr = r0 + row;
   gr = gr < R ? gr : R - 1;
   glds16(base + (long)gr * ld + k0 + c * 8, tile + 1024 * j);
 }
 
-template <int ROWS, int NW = 8, bool S16 = false>
+template <int ROWS>
 __device__ __forceinline__ void v3_stage_kn(char* tile, const __bf16* __restrict__ base, long ld, int r0, int R, int k0,
                                             int wave, int lane) {
-  constexpr int TI = ROWS * 64 / 1024;  // wave-instructions for the tile, dealt round-robin to the NW waves
+  constexpr int TI = ROWS * 64 / 1024;  // wave-instructions for the tile, dealt round-robin to the waves
 #pragma unroll
-  for (int i = 0; i < (TI + NW - 1) / NW; ++i) {
-    const int j = wave + NW * i;
+  for (int i = 0; i < (TI + V3_WAVES - 1) / V3_WAVES; ++i) {
+    const int j = wave + V3_WAVES * i;
     if (j >= TI) break;  // (192-row tiles: waves 4-7 issue one instruction less)
-    v3_piece_kn<S16>(tile, base, ld, r0, R, k0, j, lane);
+    v3_piece_kn(tile, base, ld, r0, R, k0, j, lane);
   }
 }
 
@@ -585,12 +563,12 @@ __device__ __forceinline__ void v3_piece_km(char* tile, const __bf16* __restrict
   glds16(base + (long)(k0 + krow) * ld + gc, tile + 1024 * j);
 }
 
-template <int COLS, int NW = 8>
+template <int COLS>
 __device__ __forceinline__ void v3_stage_km(char* tile, const __bf16* __restrict__ base, long ld, int r0, int R, int k0,
                                             int wave, int lane) {
-  constexpr int NI = 32 * COLS * 2 / 1024 / NW;
+  constexpr int NI = 32 * COLS * 2 / 1024 / V3_WAVES;
 #pragma unroll
-  for (int i = 0; i < NI; ++i) v3_piece_km<COLS>(tile, base, ld, r0, R, k0, wave + NW * i, lane);
+  for (int i = 0; i < NI; ++i) v3_piece_km<COLS>(tile, base, ld, r0, R, k0, wave + V3_WAVES * i, lane);
 }
 
 __device__ __forceinline__ Frag16 v3_frag_kn(const char* tile, int rb, int kk, int lane) {
@@ -598,15 +576,6 @@ __device__ __forceinline__ Frag16 v3_frag_kn(const char* tile, int rb, int kk, i
   const int c = 2 * kk + (lane >> 5);
   Frag16 f;
   f.u = *reinterpret_cast<const u32x4*>(tile + row * 64 + 16 * (c ^ ((row >> 2) & 3)));
-  return f;
-}
-
-// 16 rows x 32 k (one whole 64-B row segment per 4 lanes): the operand of v_mfma_f32_16x16x32_bf16 in ONE ds_read_b128
-__device__ __forceinline__ Frag16 v3_frag16_kn(const char* tile, int rb, int lane) {
-  const int row = rb + (lane & 15);
-  const int c = lane >> 4;
-  Frag16 f;
-  f.u = *reinterpret_cast<const u32x4*>(tile + row * 64 + 16 * (c ^ v3_swz_kn<true>(row)));
   return f;
 }
 
@@ -644,25 +613,19 @@ template <int N> __device__ __forceinline__ void wait_vmcnt() {
 // One block = one BM_ x BN_ output tile (`tile` = row-major tile index, `split_idx` = k-slice for split-K).  The body of
 // gemm_v3_kernel (one GEMM per launch) and of wgrad_group_kernel (the weight gradients of a whole transformer block in
 // one launch, full-K tiles).
-// M16: the k-loop issues v_mfma_f32_16x16x32_bf16 (16 x 16 output tiles, the whole 32-element k-step per instruction) instead of
-// 32x32x16: the same FLOPs per pipe cycle and the same LDS bytes per k-step, but the chip holds a higher clock on it
-// (MI355X_MICROARCH.md, DVFS give-back item 7; measured here with the operand registers of the 32x32x16 loop fed to the other
-// shape: qkv 55.5 -> 48.8 us, fc1+GELU 102 -> 96).  Built for the forward kernels whose both operands are k-normal, on the
-// ping-pong loop with the LDS-staged epilogue (the accumulator layout changes: lane = m % 16, registers = 4 consecutive n).
-template <int BM_, int BN_, int WM, int WN, bool WK, int STAGES, bool DIRECT, bool PP, bool XK, int NW, bool SWP,
-          bool XSUM = false, bool M16 = false, typename E = __bf16>
+// PP: the ping-pong k-loop; otherwise the software-pipelined one.  DIRECT: the epilogue leaves straight from the accumulator
+// registers; otherwise staged through LDS.  XK / WK: that operand is k-major.  XSUM: row sums of X beside the GEMM.
+template <int BM_, int BN_, bool WK, bool DIRECT, bool PP, bool XK, bool XSUM, typename E>
 __device__ __forceinline__ void gemm_v3_tile(GemmArgs& a, const int tile, const int split_idx) {
-  static_assert(!M16 || (PP && !DIRECT && !XK && !WK && !XSUM && !SWP && NW == 8), "16x16x32 variant: k-normal ping-pong, staged epilogue");
+  constexpr int STAGES = V3_STAGES, NW = V3_WAVES;
+  constexpr int WN = BN_ / 64, WM = NW / WN;       // wave grid
   constexpr int TM = BM_ / WM, TN = BN_ / WN;      // per-wave tile
   constexpr int MT = TM / 32, NTL = TN / 32;       // 32x32 accumulators per wave
   constexpr int XB = BM_ * 64, WB = BN_ * 64;      // bytes per stage per side
   constexpr int SB = XB + WB;
   constexpr int G = (SB / 1024 + NW - 1) / NW;     // LDS-DMA instructions per wave per stage (max over waves)
-  constexpr int D = STAGES - 1;                    // stages in flight
-  static_assert(WM * WN == NW && (NW == 8 || (NW == 4 && !PP)) && (WB % (1024 * NW)) == 0 &&
-                    ((XB % (1024 * NW)) == 0 || ((PP || SWP) && !XK && XB == 12288 && DIRECT)),
-                "NW waves (ping-pong: 8); whole wave-instructions per wave, except the 192-row k-normal X tile of the "
-                "ping-pong kernel");
+  static_assert((WB % (1024 * NW)) == 0 && ((XB % (1024 * NW)) == 0 || (!XK && XB == 12288 && DIRECT)),
+                "whole wave-instructions per wave, except the 192-row k-normal X tile");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -714,12 +677,6 @@ __device__ __forceinline__ void gemm_v3_tile(GemmArgs& a, const int tile, const 
     for (int j = 0; j < MT; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  constexpr int NT16 = M16 ? TN / 16 : 1, MT16 = M16 ? TM / 16 : 1;   // 16 x 16 accumulators per wave (M16 only)
-  f32x4 acc16[NT16][MT16];
-#pragma unroll
-  for (int i = 0; i < NT16; ++i)
-#pragma unroll
-    for (int j = 0; j < MT16; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // Row sums of the X operand beside the GEMM (grouped weight gradients: X = dY^T, so xsum = the Linear's bias gradient).
   // The 32x32x16 X fragment (lane l: row l&31, k-half l>>5) is fed as the B operand of a 16x16x32 MFMA, which reads it as
@@ -742,10 +699,10 @@ __device__ __forceinline__ void gemm_v3_tile(GemmArgs& a, const int tile, const 
 
   auto issue = [&](int t) {
     char* buf = smem + (t % STAGES) * SB;
-    if constexpr (XK) v3_stage_km<BM_, NW>(buf, X, a.ldx, m0, a.M, t * V3_KE, wave, lane);
-    else v3_stage_kn<BM_, NW, M16>(buf, X, a.ldx, m0, a.M, t * V3_KE, wave, lane);
-    if constexpr (WK) v3_stage_km<BN_, NW>(buf + XB, W, a.ldw, n0, a.N, t * V3_KE, wave, lane);
-    else v3_stage_kn<BN_, NW, M16>(buf + XB, W, a.ldw, n0, a.N, t * V3_KE, wave, lane);
+    if constexpr (XK) v3_stage_km<BM_>(buf, X, a.ldx, m0, a.M, t * V3_KE, wave, lane);
+    else v3_stage_kn<BM_>(buf, X, a.ldx, m0, a.M, t * V3_KE, wave, lane);
+    if constexpr (WK) v3_stage_km<BN_>(buf + XB, W, a.ldw, n0, a.N, t * V3_KE, wave, lane);
+    else v3_stage_kn<BN_>(buf + XB, W, a.ldw, n0, a.N, t * V3_KE, wave, lane);
   };
   auto read_frags = [&](int t, Frag16 (&fw)[2][NTL], Frag16 (&fx)[2][MT]) {
     const char* bx = smem + (t % STAGES) * SB;
@@ -772,7 +729,7 @@ __device__ __forceinline__ void gemm_v3_tile(GemmArgs& a, const int tile, const 
       for (int i = 0; i < NTL; ++i)
 #pragma unroll
         for (int j = 0; j < MT; ++j)
-          ring_mfma<E>(fw[kk][i], fx[kk][j], acc[i][j], kk);
+          acc[i][j] = mfma16B<E>(fw[kk][i], fx[kk][j], acc[i][j]);
     if constexpr (XSUM) {
       if (do_xsum) {
 #pragma unroll
@@ -785,18 +742,16 @@ __device__ __forceinline__ void gemm_v3_tile(GemmArgs& a, const int tile, const 
     __builtin_amdgcn_s_setprio(0);
   };
 
-  if constexpr (SWP) {
+  if constexpr (!PP) {
     // Software-pipelined loop, one barrier per k-step.  Iteration t runs the MFMAs of stage t on fragments that were
     // read from LDS during iteration t-1, and between those MFMAs issues (a) the fragment reads of stage t+1 into the
     // other register set and (b) this wave's LDS-DMA pieces of stage t+3 into the slot of stage t-1 (every wave
     // consumed its stage-(t-1) fragments before it reached this iteration's barrier).  LDS reads and DMA issue cost
     // far less in the shadow of the wave's own MFMAs than in a phase of their own (stamped: 12 ds_read_b128 276 cyc,
     // 4 pieces 416 cyc in the ping-pong read phase), and the SIMD's two waves cover each other's remaining stalls.
-    // Ring of STAGES slots: the pieces of stage t+STAGES-1 go into the slot of stage t-1; stages t+2 .. t+STAGES-2
-    // may still be in flight at the barrier of iteration t (STAGES = 3: none -- the block's twin on the CU covers it).
-    static_assert((STAGES == 4 || STAGES == 3) && !PP, "software-pipelined ring: 3 or 4 slots");
+    // Ring of 4 slots: the pieces of stage t+3 go into the slot of stage t-1; stage t+2 may still be in flight at the
+    // barrier of iteration t.
     constexpr int AHEAD = STAGES - 1;   // issue distance
-    constexpr int FLY = STAGES - 3;     // stages allowed in flight across the barrier
     constexpr int TIX = XB / 1024, TIW = WB / 1024;         // DMA pieces per side per stage
     constexpr int GX = (TIX + NW - 1) / NW, GW = TIW / NW;  // per wave (GX: max over waves)
     constexpr int NR = 2 * (NTL + MT), NMF = 2 * NTL * MT;  // fragment reads / MFMAs per k-step
@@ -847,7 +802,7 @@ __device__ __forceinline__ void gemm_v3_tile(GemmArgs& a, const int tile, const 
       constexpr bool FULL = decltype(full)::value;
       PM_STAMP(0);
       __builtin_amdgcn_sched_barrier(0);
-      if (FLY > 0 && (FULL || t + 2 < nk)) wait_stages(std::integral_constant<int, FLY>{});  // stage t+1 landed
+      if (FULL || t + 2 < nk) wait_stages(std::integral_constant<int, 1>{});  // stage t+1 landed, stage t+2 may fly
       else wait_vmcnt<0>();
       PM_STAMP(1);
       __builtin_amdgcn_s_barrier();
@@ -857,7 +812,7 @@ __device__ __forceinline__ void gemm_v3_tile(GemmArgs& a, const int tile, const 
 #pragma unroll
       for (int m = 0; m < NMF; ++m) {
         const int kk = m / (NTL * MT), i = (m / MT) % NTL, j = m % MT;
-        ring_mfma<E>(cw[kk][i], cx[kk][j], acc[i][j], kk);
+        acc[i][j] = mfma16B<E>(cw[kk][i], cx[kk][j], acc[i][j]);
         __builtin_amdgcn_sched_barrier(0);
         if (m < NR && rd) read_one(t + 1, m, nw, nx);
         if ((m % PER) == 1 && m / PER < G && ld) piece(t + AHEAD, m / PER);
@@ -884,7 +839,7 @@ __device__ __forceinline__ void gemm_v3_tile(GemmArgs& a, const int tile, const 
 #pragma unroll
     for (int t = 0; t < AHEAD; ++t)
       if (t < nk) issue(t);
-    if (nk > 2) wait_stages(std::integral_constant<int, (AHEAD > 2 ? 2 : 1)>{});
+    if (nk > 2) wait_stages(std::integral_constant<int, 2>{});
     else if (nk > 1) wait_stages(std::integral_constant<int, 1>{});
     else wait_vmcnt<0>();
     __builtin_amdgcn_s_barrier();
@@ -907,39 +862,18 @@ __device__ __forceinline__ void gemm_v3_tile(GemmArgs& a, const int tile, const 
       a.stamps[((long)blockIdx.x * NW + wave) * 16 + 7] = nk;
     }
 #endif
-  } else if constexpr (!PP) {
-#pragma unroll
-    for (int t = 0; t < D; ++t)
-      if (t < nk) issue(t);
-    for (int t = 0; t < nk; ++t) {
-      // stage t must have landed (this wave's share); later stages may stay in flight
-      const int ahead = nk - 1 - t;  // stages issued after t that exist
-      if (ahead >= D - 1) wait_vmcnt<G * (D - 1)>();
-      else if (ahead == 1) wait_vmcnt<G>();
-      else wait_vmcnt<0>();
-      __builtin_amdgcn_s_barrier();  // everyone's share of stage t landed; everyone finished reading stage t-1
-      // all fragment reads of the k-step first (their latency then overlaps the DMA issue below), then the DMA
-      // refill of the slot that stage t-1 occupied, then 2*MT*NTL back-to-back MFMAs
-      Frag16 fw[2][NTL], fx[2][MT];
-      read_frags(t, fw, fx);
-      __builtin_amdgcn_sched_barrier(0);
-      if (t + D < nk) issue(t + D);
-      __builtin_amdgcn_sched_barrier(0);
-      mma_all(fw, fx);
-    }
   } else {
     // Ping-pong: waves 0-3 and 4-7 (SIMD partners: wave w and w+4 share a SIMD) run the same two-phase loop
     //   R_t: 12 LDS fragment reads of stage t + LDS-DMA refill      M_t: 16 back-to-back MFMAs
     // one phase apart (waves 4-7 pass one extra barrier first), so on every SIMD one wave's MFMA phase runs
     // beside its partner's read / DMA-issue phase instead of both stalling on LDS latency together.
-    // Ring: DP = STAGES-2 stages in flight; R_t refills the slot of stage t-2, which both halves finished reading
+    // Ring: DP = 2 stages in flight; R_t refills the slot of stage t-2, which both halves finished reading
     // (and waited lgkmcnt(0) on) at least two barriers ago.  Stage readiness: every wave waits for its own DMA share
     // of stage t+1 before the barrier that opens its M_t -- for the lagging half that barrier is the one that opens
     // the leading half's R_{t+1}.
     // (Issuing the refill, or half of it, between the MFMAs of M_t instead was measured neutral to slightly worse:
     // the stamped read phase shrinks from 810 to 392 cycles but the MFMA phase grows from 575 to 730.)
     constexpr int DP = STAGES - 2;
-    static_assert(STAGES == 4, "ping-pong ring tuned for 4 slots");
     const int gq = wave >> 2;
 #pragma unroll
     for (int t = 0; t < DP; ++t)
@@ -965,17 +899,7 @@ __device__ __forceinline__ void gemm_v3_tile(GemmArgs& a, const int tile, const 
       __builtin_amdgcn_s_barrier();  // opens R_t
       PM_STAMP(1);
       Frag16 fw[2][NTL], fx[2][MT];
-      Frag16 gw[NT16], gx[MT16];
-      if constexpr (M16) {
-        const char* bx = smem + (t % STAGES) * SB;
-        const char* bw = bx + XB;
-#pragma unroll
-        for (int i = 0; i < NT16; ++i) gw[i] = v3_frag16_kn(bw, wn * TN + 16 * i, lane);
-#pragma unroll
-        for (int j = 0; j < MT16; ++j) gx[j] = v3_frag16_kn(bx, wm * TM + 16 * j, lane);
-      } else {
-        read_frags(t, fw, fx);
-      }
+      read_frags(t, fw, fx);
       __builtin_amdgcn_sched_barrier(0);
       PM_STAMP(2);
       if (t + DP < nk) issue(t + DP);
@@ -988,17 +912,7 @@ __device__ __forceinline__ void gemm_v3_tile(GemmArgs& a, const int tile, const 
       PM_STAMP(5);
       __builtin_amdgcn_s_barrier();  // opens M_t
       PM_STAMP(6);
-      if constexpr (M16) {
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < NT16; ++i)
-#pragma unroll
-          for (int j = 0; j < MT16; ++j)
-            acc16[i][j] = mfma16x16<E>(gw[i], gx[j], acc16[i][j]);
-        __builtin_amdgcn_s_setprio(0);
-      } else {
-        mma_all(fw, fx);
-      }
+      mma_all(fw, fx);
 #ifdef PM_GEMM_STAMP
       PM_STAMP(7);
 #pragma unroll
@@ -1137,27 +1051,17 @@ __device__ __forceinline__ void gemm_v3_tile(GemmArgs& a, const int tile, const 
   for (int mh = 0; mh < MT / 2; ++mh) {    // 64 rows of the wave tile per pass
 #pragma unroll
     for (int nh = 0; nh < NTL / 2; ++nh) {  // 64 columns per pass
-      if constexpr (M16) {
-        // 16 x 16 accumulators: lane l holds row m = l & 15, columns n = 4 (l >> 4) .. + 3 of its tile
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj)
+      for (int j = 0; j < 2; ++j) {
+        const int ml = j * 32 + (lane & 31);
 #pragma unroll
-          for (int ii = 0; ii < 4; ++ii)
-            *reinterpret_cast<f32x4*>(st + (16 * jj + (lane & 15)) * STAGE_ROW + (16 * ii + 4 * (lane >> 4)) * 4) =
-                acc16[M16 ? nh * 4 + ii : 0][M16 ? mh * 4 + jj : 0];
-      } else {
+        for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int ml = j * 32 + (lane & 31);
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              const f32x16& t16 = acc[nh * 2 + i][mh * 2 + j];
-              const f32x4 v = {t16[4 * g], t16[4 * g + 1], t16[4 * g + 2], t16[4 * g + 3]};
-              *reinterpret_cast<f32x4*>(st + ml * STAGE_ROW + (i * 32 + 8 * g + 4 * h) * 4) = v;
-            }
-        }
+          for (int g = 0; g < 4; ++g) {
+            const f32x16& t16 = acc[nh * 2 + i][mh * 2 + j];
+            const f32x4 v = {t16[4 * g], t16[4 * g + 1], t16[4 * g + 2], t16[4 * g + 3]};
+            *reinterpret_cast<f32x4*>(st + ml * STAGE_ROW + (i * 32 + 8 * g + 4 * h) * 4) = v;
+          }
       }
       __builtin_amdgcn_wave_barrier();
       const int mw = m0 + wm * TM + mh * 64, nw = n0 + wn * TN + nh * 64;
@@ -1218,10 +1122,9 @@ __device__ __forceinline__ void gemm_v3_tile(GemmArgs& a, const int tile, const 
 #endif
 }
 
-template <int BM_, int BN_, int WM, int WN, bool WK, int STAGES, int MINW, bool DIRECT, bool PP, bool XK = false, int NW = 8,
-          bool SWP = false, bool M16 = false, typename E = __bf16>
-__global__ __launch_bounds__(NW * 64, MINW) void gemm_v3_kernel(GemmArgs a) {
-  gemm_v3_tile<BM_, BN_, WM, WN, WK, STAGES, DIRECT, PP, XK, NW, SWP, false, M16, E>(a, xcd_remap(blockIdx.x, gridDim.x), blockIdx.y);
+template <int BM_, int BN_, bool WK, bool DIRECT, bool PP, bool XK, typename E>
+__global__ __launch_bounds__(V3_WAVES * 64, 2) void gemm_v3_kernel(GemmArgs a) {
+  gemm_v3_tile<BM_, BN_, WK, DIRECT, PP, XK, false, E>(a, xcd_remap(blockIdx.x, gridDim.x), blockIdx.y);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1253,19 +1156,24 @@ struct WgradGroupArgs {
   int n, K, total_tiles;
   int split;          // k-slices per tile (1: the tile's workgroup writes dW itself)
   int ksteps_split;
-  int auto_order;     // per-problem tile order: the shorter side fastest (0: row by row, the A/B baseline)
   long total_vec, bias_begin, bias_total;  // reduce launch: float4 items, then bias rows
-  int xcds;           // XCDs the work is confined to (8: all).  < 8: the grid is 8 / xcds times the work and the workgroups the
-                      // hardware deals to the other XCDs (workgroup id % 8 >= xcds) leave at once -- see pm_wgrad_group
 #ifdef PM_GEMM_STAMP
   unsigned long long* stamps;
 #endif
 };
 
-// one (k-slice, tile) work item of a grouped launch
-template <int BM_, int BN_, int WM, int WN, typename E, int NW>
-__device__ __forceinline__ void group_item(const WgradGroupArgs& g, const int w) {
-  {
+// 256 x BN_ tiles, 8 waves on the ping-pong loop (two waves per SIMD, 128 x 64 per wave at BN_ = 256), row sums of dY beside the GEMM.
+// (The software-pipelined loop needs 254 VGPRs without the row sums: with them it spills 73 and runs 1.5x slower;
+//  without them, bias gradients by separate column-sum passes, it equals this loop with the row sums inside.)
+template <int BN_, typename E>
+__global__ __launch_bounds__(V3_WAVES * 64, 2) void wgrad_group_kernel(WgradGroupArgs g) {
+  // gridDim.x workgroups (a multiple of 8, or the whole work list) walk the (k-slice, tile) items t = blockIdx.x,
+  // + gridDim.x, ...: the caller chooses how many CUs the weight-gradient stream takes from the dgrad chain beside it.
+  // xcd_remap gives every XCD a contiguous run of items; within a k-slice consecutive items are neighbouring tiles
+  // (same dY panel -> same private L2); with gridDim.x % 8 == 0 a workgroup stays on its XCD's run.
+  const int work = g.total_tiles * g.split;
+  for (int t = blockIdx.x; t < work; t += gridDim.x) {
+    const int w = xcd_remap(t, work);
     const int slice = w / g.total_tiles, tile = w - slice * g.total_tiles;
     int pi = 0;
 #pragma unroll
@@ -1276,12 +1184,12 @@ __device__ __forceinline__ void group_item(const WgradGroupArgs& g, const int w)
     a.X = pr.dY; a.W = pr.X; a.ldx = pr.lddy; a.ldw = pr.ldx; a.bias = nullptr; a.C = pr.dW; a.ldc = pr.lddw; a.aux = nullptr;
     a.resid = nullptr; a.M = pr.M; a.N = pr.N; a.K = g.K; a.epilogue = pr.accumulate ? PM_EPI_ACCUM : PM_EPI_STORE;
     a.c_dtype = PM_F32; a.tiles_m = pr.tiles_m; a.tiles_n = pr.tiles_n; a.split_k = 1; a.ksteps_split = 0;
-    a.xsum = pr.dbias; a.xsum_store = 0; a.epi_hoist = 0;
+    a.xsum = pr.dbias; a.xsum_store = 0;
     // Consecutive work items run on one XCD (xcd_remap) at the same pace, so what they share they fetch once into that XCD's
     // L2: a tile reads a dY panel [K x 256] and an X panel [K x 256] (6.4 MB each at K = 12 608).  Walk the SHORTER side of the
     // problem fastest, so that a run of ~13 tiles covers a compact rectangle: fc2's gradient is 3 x 12 tiles -- row by row a run
     // touches 2 + 12 panels, column by column 3 + 5 (PMC before: 557 MB fetched per ViT-B block against 335 MB algorithmic).
-    a.col_major = g.auto_order ? (pr.tiles_m < pr.tiles_n) : 0;
+    a.col_major = pr.tiles_m < pr.tiles_n;
     if (g.split > 1) {  // a k-slice: plain f32 partials into the slab (gemm_v3_tile offsets C by the slice), reduced afterwards
       a.C = pr.slab; a.ldc = pr.N; a.epilogue = PM_EPI_STORE; a.split_k = g.split; a.ksteps_split = g.ksteps_split;
       a.xsum = pr.dbias ? pr.bias_part + (long)slice * pr.M : nullptr; a.xsum_store = 1;
@@ -1289,41 +1197,8 @@ __device__ __forceinline__ void group_item(const WgradGroupArgs& g, const int w)
 #ifdef PM_GEMM_STAMP
     a.stamps = g.stamps;  // (rows of the block index: the caller hands a region of its own to the grouped launches)
 #endif
-    // (the software-pipelined loop needs 254 VGPRs without the row sums: with them it spills 73 and runs 1.5x slower;
-    //  without them, bias gradients by separate column-sum passes, it equals this loop with the row sums inside)
-    if constexpr (NW == 8)
-      gemm_v3_tile<BM_, BN_, WM, WN, true, 4, true, true, true, 8, false, true, false, E>(a, tile - pr.tile_begin, slice);
-    else
-      gemm_v3_tile<BM_, BN_, WM, WN, true, 4, true, false, true, NW, true, true, false, E>(a, tile - pr.tile_begin, slice);
+    gemm_v3_tile<256, BN_, true, true, true, true, true, E>(a, tile - pr.tile_begin, slice);
     __syncthreads();  // every wave is done with the LDS ring before the next tile's first stages are issued
-  }
-}
-
-// NW = 8: the ping-pong loop (two waves per SIMD, 128 x 64 per wave).  NW = 4 (experiment, PM_GROUP_KERNEL=4): ONE wave per SIMD,
-// 128 x 128 per wave on the software-pipelined loop -- 16 fragment reads per 32 MFMAs instead of 12 per 16, i.e. 2/3 of the LDS
-// fragment traffic that co-limits the 8-wave loop here (both operands arrive by transpose reads), at 512 VGPRs per wave.
-template <int BM_, int BN_, int WM, int WN, typename E = __bf16, int NW = 8>
-__global__ __launch_bounds__(NW * 64, NW == 8 ? 2 : 1) void wgrad_group_kernel(WgradGroupArgs g) {
-  // gridDim.x workgroups (a multiple of 8, or the whole work list) walk the (k-slice, tile) items t = blockIdx.x,
-  // + gridDim.x, ...: the caller chooses how many CUs the weight-gradient stream takes from the dgrad chain beside it.
-  // xcd_remap gives every XCD a contiguous run of items; within a k-slice consecutive items are neighbouring tiles
-  // (same dY panel -> same private L2); with gridDim.x % 8 == 0 a workgroup stays on its XCD's run.
-  const int work = g.total_tiles * g.split;
-  if (g.xcds < 8) {
-    // few tiles (the (proj, qkv) launch of a ViT-B block: 36): confined to g.xcds of the 8 XCDs, every XCD's run of consecutive
-    // tiles is 8 / xcds times longer, i.e. shares more dY / X panels in ONE L2 instead of fetching them into several
-    const int xcd = blockIdx.x & 7;
-    if (xcd >= g.xcds) return;
-    const int t = (blockIdx.x >> 3) * g.xcds + xcd;   // one work item per participating workgroup (grid sized for it)
-    if (t >= work) return;
-    const int q = work / g.xcds, r = work % g.xcds;
-    const int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (t / g.xcds);
-    group_item<BM_, BN_, WM, WN, E, NW>(g, w);
-    return;
-  }
-  for (int t = blockIdx.x; t < work; t += gridDim.x) {
-    const int w = xcd_remap(t, work);
-    group_item<BM_, BN_, WM, WN, E, NW>(g, w);   // (ends in a block barrier: the LDS ring is free for the next item)
   }
 }
 
@@ -1362,176 +1237,307 @@ __global__ __launch_bounds__(256) void wgrad_group_reduce_kernel(WgradGroupArgs 
   }
 }
 
-// forward GEMM on the 16x16x32 loop (both operands k-normal): 256 x 256 ping-pong, LDS-staged epilogue
-template <typename E>
-int launch_v3_m16(GemmArgs a, hipStream_t s) {
-  a.tiles_m = (a.M + 255) / 256;
-  a.tiles_n = (a.N + 255) / 256;
-  constexpr int ring = 4 * 512 * 64, stage = 8 * V3_STAGE_WAVE;
-  const size_t lds = ring > stage ? ring : stage;
-  auto kern = gemm_v3_kernel<256, 256, 2, 4, false, 4, 2, false, true, false, 8, false, true, E>;
-  PM_ALLOW_LDS(kern, lds);
-  hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n), dim3(512), lds, s, a);
-  return pm_check_launch();
-}
-
-template <typename E, int BM_, int BN_, int WM, int WN, int STAGES, int MINW, bool DIRECT, bool PP = false, int NW = 8, bool SWP = false>
-int launch_v3(GemmArgs a, int wk, hipStream_t s) {
-  a.tiles_m = (a.M + BM_ - 1) / BM_;
-  a.tiles_n = (a.N + BN_ - 1) / BN_;
-  constexpr int ring = STAGES * (BM_ + BN_) * 64;
-  constexpr int stage = DIRECT ? 0 : NW * V3_STAGE_WAVE;
-  const size_t lds = ring > stage ? ring : stage;
-  const dim3 grid(a.tiles_m * a.tiles_n), block(NW * 64);
-  if (wk) {
-    auto kern = gemm_v3_kernel<BM_, BN_, WM, WN, true, STAGES, MINW, DIRECT, PP, false, NW, SWP, false, E>;
-    PM_ALLOW_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, a);
-  } else {
-    auto kern = gemm_v3_kernel<BM_, BN_, WM, WN, false, STAGES, MINW, DIRECT, PP, false, NW, SWP, false, E>;
-    PM_ALLOW_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, a);
-  }
-  return pm_check_launch();
-}
-
-// wgrad shape (both operands k-major, K = #tokens): 256x128 ping-pong ring kernel, direct epilogue, split-K slabs
-template <typename E, int BM_, int BN_, int WM, int WN, bool SWP>
-int launch_v3_wgrad(GemmArgs a, hipStream_t s) {
-  a.tiles_m = (a.M + BM_ - 1) / BM_;
-  a.tiles_n = (a.N + BN_ - 1) / BN_;
-  constexpr int ring = 4 * (BM_ + BN_) * 64;
-  const dim3 grid(a.tiles_m * a.tiles_n, a.split_k), block(512);
-  auto kern = gemm_v3_kernel<BM_, BN_, WM, WN, true, 4, 2, true, !SWP, true, 8, SWP, false, E>;
-  PM_ALLOW_LDS(kern, ring);
-  hipLaunchKernelGGL(kern, grid, block, ring, s, a);
-  return pm_check_launch();
+// (xk, wk) -> the compile-time pair: f(XK, WK) with std::bool_constant arguments
+template <typename F>
+int with_layouts(int xk, int wk, F&& f) {
+  if (xk) return wk ? f(std::true_type{}, std::true_type{}) : f(std::true_type{}, std::false_type{});
+  return wk ? f(std::false_type{}, std::true_type{}) : f(std::false_type{}, std::false_type{});
 }
 
 template <typename T>
 int launch_generic(const GemmArgs& a, int xk, int wk, hipStream_t s) {
-  const dim3 grid(a.tiles_m * a.tiles_n), block(kThreads);
-  const size_t lds = 4 * TILE_BYTES;
-  if (!xk && !wk)
-    hipLaunchKernelGGL((gemm_generic_kernel<T, false, false>), grid, block, lds, s, a);
-  else if (!xk && wk)
-    hipLaunchKernelGGL((gemm_generic_kernel<T, false, true>), grid, block, lds, s, a);
-  else if (xk && wk)
-    hipLaunchKernelGGL((gemm_generic_kernel<T, true, true>), grid, block, lds, s, a);
-  else
-    hipLaunchKernelGGL((gemm_generic_kernel<T, true, false>), grid, block, lds, s, a);
-  return pm_check_launch();
+  return with_layouts(xk, wk, [&](auto XK, auto WK) {
+    hipLaunchKernelGGL((gemm_generic_kernel<T, decltype(XK)::value, decltype(WK)::value>), dim3(a.tiles_m * a.tiles_n),
+                       dim3(kThreads), 4 * TILE_BYTES, s, a);
+    return pm_check_launch();
+  });
 }
 
 template <typename T>
 int launch_glds(const GemmArgs& a, int xk, int wk, hipStream_t s) {
-  const dim3 grid(a.tiles_m * a.tiles_n, a.split_k), block(kThreads);
-  const size_t lds = GLDS_LDS_BYTES;
-  if (!xk && !wk) {
-    auto kern = gemm_glds_kernel<T, false, false>;
-    PM_ALLOW_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, a);
-  } else if (!xk && wk) {
-    auto kern = gemm_glds_kernel<T, false, true>;
-    PM_ALLOW_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, a);
-  } else if (xk && wk) {
-    auto kern = gemm_glds_kernel<T, true, true>;
-    PM_ALLOW_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, a);
-  } else {
-    auto kern = gemm_glds_kernel<T, true, false>;
-    PM_ALLOW_LDS(kern, lds);
-    hipLaunchKernelGGL(kern, grid, block, lds, s, a);
-  }
+  return with_layouts(xk, wk, [&](auto XK, auto WK) {
+    auto kern = gemm_glds_kernel<T, decltype(XK)::value, decltype(WK)::value>;
+    PM_ALLOW_LDS(kern, GLDS_LDS_BYTES);
+    hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n, a.split_k), dim3(kThreads), GLDS_LDS_BYTES, s, a);
+    return pm_check_launch();
+  });
+}
+
+// one ring kernel: grid = tiles x k-slices
+template <typename E, int BM_, int BN_, bool WK, bool DIRECT, bool PP, bool XK>
+int launch_v3(const GemmArgs& a, hipStream_t s) {
+  constexpr int ring = V3_STAGES * (BM_ + BN_) * 64;
+  constexpr int stage = DIRECT ? 0 : V3_WAVES * V3_STAGE_WAVE;
+  constexpr size_t lds = ring > stage ? ring : stage;
+  auto kern = gemm_v3_kernel<BM_, BN_, WK, DIRECT, PP, XK, E>;
+  PM_ALLOW_LDS(kern, lds);
+  hipLaunchKernelGGL(kern, dim3(a.tiles_m * a.tiles_n, a.split_k), dim3(V3_WAVES * 64), lds, s, a);
   return pm_check_launch();
 }
 
-// the ring-kernel variants the dispatcher chooses from (cfg: see gemm_dispatch), per 16-bit operand type
-template <typename E>
-int launch_v3_cfg(int cfg, const GemmArgs& a, int b_kmajor, hipStream_t s) {
-  switch (cfg) {
-    case 6: return launch_v3<E, 256, 256, 2, 4, 4, 2, true>(a, b_kmajor, s);          // plain ring loop, register epilogue
-    case 8: return launch_v3<E, 256, 256, 2, 4, 4, 2, false, true>(a, b_kmajor, s);   // ping-pong, LDS-staged epilogue
-    case 40: if (!b_kmajor) return launch_v3_m16<E>(a, s);                            // the same on v_mfma_f32_16x16x32_bf16
-             return launch_v3<E, 256, 256, 2, 4, 4, 2, false, true>(a, b_kmajor, s);
-    case 9: return launch_v3<E, 256, 256, 2, 4, 4, 2, true, true>(a, b_kmajor, s);    // ping-pong, register epilogue
-    case 10: return launch_v3<E, 192, 256, 2, 4, 4, 2, true, true>(a, b_kmajor, s);   // 192-row tiles: finer M granularity
-    // 128-row tiles (experiment 6, round 4: the half-batch proj / fc2 of the forward chains hold 99 tiles of 192 rows on 256 CUs)
-    case 12: return launch_v3<E, 128, 256, 2, 4, 4, 2, true, false, 8, true>(a, b_kmajor, s);
-    case 13: return launch_v3<E, 128, 256, 2, 4, 4, 2, true, true>(a, b_kmajor, s);
-    // software-pipelined loop (fragment reads and DMA issue between the wave's own MFMAs)
-    case 24: return launch_v3<E, 256, 256, 2, 4, 4, 2, false, false, 8, true>(a, b_kmajor, s);
-    case 25: return launch_v3<E, 256, 256, 2, 4, 4, 2, true, false, 8, true>(a, b_kmajor, s);
-    case 26: return launch_v3<E, 192, 256, 2, 4, 4, 2, true, false, 8, true>(a, b_kmajor, s);
-    // Measured and no longer instantiated (the template still admits them):
-    //   two 4-wave blocks per CU   launch_v3<E, 128, 256, 2, 2, 3, 2, false, false, 4, true>   slower on every shape
-    //   two 8-wave blocks per CU   launch_v3<E, 256, 128, 4, 2, 3, 4, true> / <128, 256, 2, 4, 3, 4, true>: <= 128 VGPRs, 100-150
-    //                              spills, 85 instead of 128 FLOP per LDS-fill byte: 1.7x slower
-    //   one wave per SIMD          launch_v3<E, 256, 256, 2, 2, 4, 1, true, false, 4, true>: 128x128 per wave, 512 VGPRs, 2/3 of the
-    //                              LDS reads per FLOP: equals the 8-wave loop on long-K dgrads (decoder dfc1 1.0 PFLOP/s both),
-    //                              loses 5-30 % wherever prologue / epilogue matter
-    default: return launch_v3<E, 256, 256, 2, 4, 4, 2, false>(a, b_kmajor, s);
-  }
-}
-
-// Split-K plan of a weight-gradient GEMM on the ring kernel (shared by the dispatcher and pm_gemm_workspace_bytes).
-// 256x256 tiles (twice the MFMAs per barrier) from 2x2 tiles up: ViT-B qkv / fc1 / fc2 gradients 74 us vs 83 with
-// 256x128; the MAE decoder's 512-wide gradients (K = 50 432 tokens) +2.8 % step rate; neutral for 768x768.
-// Variant bits 6-7: 1 = force 256x128, 2 = force 256x256, 3 = software-pipelined 256x256 (slower: tr reads).
-struct WgradPlan {
-  int wv;     // tile variant (1: 256x128, 2: 256x256, 3: software-pipelined 256x256)
-  int split;  // k-slices (each writes an f32 slab when > 1)
+// The ring kernels of the forward / dgrad GEMMs (X k-normal, BM x 256 tiles): every configuration the heuristics of plan_gemm
+// choose, with the W layouts they choose it for.  plan_gemm and the launcher both read this table; nothing else is instantiated
+// (what was measured and left the tree: docs/EXPERIMENT_LOG.md).
+struct RingCfg {
+  int cfg;         // pm_gemm_opts.variant bits 0-5
+  int bm;          // tile rows (192: finer M granularity)
+  bool direct;     // register epilogue (LDS-staged otherwise: whole 128-B row segments per store)
+  bool pp;         // ping-pong k-loop (software-pipelined otherwise: fragment reads and DMA issue between the wave's own MFMAs)
+  bool w_kmajor;   // also built for W k-major (dgrads); every entry is built for W k-normal
 };
-inline WgradPlan plan_wgrad(int M, int N, int K, int force_cfg, int wgrad_blocks, size_t ws_bytes) {
-  WgradPlan p;
-  p.wv = (force_cfg >> 6) & 3;
-  if (p.wv == 0) p.wv = ((M + 255) / 256) * ((N + 255) / 256) >= 4 ? 2 : 1;
-  const int bn3 = p.wv >= 2 ? 256 : 128;
-  const int t3 = ((M + 255) / 256) * ((N + bn3 - 1) / bn3);
-  const int nk3 = K / V3_KE;
-  int split = wgrad_blocks / t3;
-  if (split > nk3 / 16) split = nk3 / 16;
-  if (split > 16) split = 16;
-  if (split < 1) split = 1;
-  while (split > 1 && (size_t)split * M * N * sizeof(float) > ws_bytes) --split;
-  p.split = split;
-  return p;
-}
-inline bool is16(int dtype) { return dtype == PM_BF16 || dtype == PM_F16; }
-inline bool wgrad_ring_shape(int in_dtype, int a_kmajor, int b_kmajor, int M, int N, int K) {
-  return is16(in_dtype) && a_kmajor && b_kmajor && (K % V3_KE) == 0 && K >= 2048 && M >= 256 && N >= 128;
+constexpr RingCfg kRingCfgs[] = {
+    {8, 256, false, true, true},   {9, 256, true, true, false},   {10, 192, true, true, false},
+    {24, 256, false, false, true}, {25, 256, true, false, false}, {26, 192, true, false, false},
+};
+constexpr int kNumRingCfgs = sizeof(kRingCfgs) / sizeof(kRingCfgs[0]);
+inline const RingCfg* find_ring_cfg(int cfg, int w_kmajor) {
+  for (const RingCfg& c : kRingCfgs)
+    if (c.cfg == cfg && (!w_kmajor || c.w_kmajor)) return &c;
+  return nullptr;
 }
 
-int gemm_dispatch(const void* A, long lda, int a_kmajor, const void* B, long ldb, int b_kmajor, int in_dtype,
-                  const float* bias, void* C, long ldc, int c_dtype, int epilogue, void* aux, const float* resid, int M, int N,
-                  int K, void* workspace, size_t ws_bytes, const pm_gemm_opts* opts, void* stream);
-
-}  // namespace
-
-extern "C" size_t pm_gemm_workspace_bytes(int a_kmajor, int b_kmajor, int in_dtype, int M, int N, int K,
-                                          const pm_gemm_opts* opts) {
-  if (M <= 0 || N <= 0 || K <= 0 || !(a_kmajor && b_kmajor)) return 0;  // only the split-K weight gradients use scratch
-  int blocks = (opts && opts->max_blocks > 0) ? opts->max_blocks : 256;
-  blocks = blocks < 16 ? 16 : (blocks > 1024 ? 1024 : blocks);
-  const int variant = opts ? opts->variant : 0;
-  if (wgrad_ring_shape(in_dtype, a_kmajor, b_kmajor, M, N, K) && (variant & 63) != 1) {
-    const WgradPlan p = plan_wgrad(M, N, K, variant, blocks, (size_t)-1);
-    return p.split > 1 ? (size_t)p.split * M * N * sizeof(float) : 0;
+template <typename E, int I = 0>
+int launch_ring(int cfg, const GemmArgs& a, int w_kmajor, hipStream_t s) {
+  if constexpr (I == kNumRingCfgs) {
+    return PM_EINVAL;
+  } else {
+    constexpr RingCfg c = kRingCfgs[I];
+    if (c.cfg != cfg) return launch_ring<E, I + 1>(cfg, a, w_kmajor, s);
+    if constexpr (c.w_kmajor)
+      if (w_kmajor) return launch_v3<E, c.bm, 256, true, c.direct, c.pp, false>(a, s);
+    return w_kmajor ? PM_EINVAL : launch_v3<E, c.bm, 256, false, c.direct, c.pp, false>(a, s);
   }
-  // 128x128 split-K path: up to 16 slabs
-  const int ke = is16(in_dtype) ? 64 : 32;
-  if (K % ke) return 0;
-  const int nk = K / ke, tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-  if (tiles >= 256 || nk < 16) return 0;
-  int split = 512 / tiles;
-  if (split > nk / 8) split = nk / 8;
-  if (split > 16) split = 16;
-  return split > 1 ? (size_t)split * M * N * sizeof(float) : 0;
 }
 
 #ifdef PM_GEMM_STAMP
-namespace { unsigned long long* g_stamps = nullptr; }
+unsigned long long* g_stamps = nullptr;  // diagnostic build: set by pm_debug_gemm_stamps
+#endif
+inline bool is16(int dtype) { return dtype == PM_BF16 || dtype == PM_F16; }
+
+// out[m][n] = (accumulate ? out : 0) + the split-K slabs in the workspace
+int launch_splitk_reduce(const void* slabs, void* out, long ldc, int M, int N, int splits, bool accumulate, hipStream_t s) {
+  const long nvec = (long)M * (N >> 2);
+  int grid = (int)((nvec + 255) / 256);
+  if (grid > 2048) grid = 2048;
+  hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid), dim3(256), 0, s, (const float*)slabs, (float*)out, ldc, M, N, splits,
+                     accumulate ? 1 : 0);
+  return pm_check_launch();
+}
+
+// Everything the dispatcher decides for one call, as a function of the call's arguments only (no pointers, no state).
+struct GemmPlan {
+  int status;          // PM_OK, or the refusal of the arguments / shapes (the fields below are then meaningless)
+  int family;          // PM_GEMM_GENERIC / LDS128 / RING / RING_WGRAD
+  int cfg;             // PM_GEMM_RING: the entry of kRingCfgs
+  int tile_m, tile_n;
+  int split_k;         // k-slices (> 1: f32 slabs in the workspace, then splitk_reduce_kernel)
+  int ksteps_split;    // k-steps of the family's kernel per slice
+  int band;            // GemmArgs::col_major
+  size_t ws_bytes;     // scratch used
+};
+
+// Thresholds of the rules below, each measured (the comment at the rule says how).
+constexpr int kTallM = 20000;            // rows from which a problem counts as "tall"
+constexpr int kFewTiles = 128;           // fewer 256 x 256 tiles than this: the 128 x 128 kernel ...
+constexpr int kFewTilesMaxM = 4096;      // ... for a short chain ...
+constexpr int kFewTilesNarrowN = 512;    // ... or a narrow one
+constexpr int kTileBand = 6;             // tile columns per band of a wide problem's tile order
+constexpr int kWideN = 2048;             // act-typed forward outputs from this width take the LDS-staged epilogue
+
+// The ring configuration of a forward / dgrad GEMM.  Tuned on the ViT-B/16 shapes at M = 12 608.
+int choose_ring_cfg(int w_kmajor, int epilogue, int M, int N) {
+  // fc1 + GELU, and the dGELU dgrad (reads the saved pre-activation, writes an act-typed [M, 4D] tensor): ping-pong loop with the
+  // LDS-staged epilogue -- dGELU stand-alone 96.8 vs 95.1 us at ViT-B, 197 vs 220 us at the MAE decoder, and +0.6 % cls step rate
+  // in-step (whole 128-B row segments per store instead of 16-B pieces at a 6-KB stride)
+  if (epilogue == PM_EPI_GELU || epilogue == PM_EPI_DGELU) return 8;
+  // plain dgrads (dfc1 / dproj / dqkv; W read as stored by ds_read_b64_tr_b16): the software-pipelined loop wins since those reads
+  // stopped waiting for the whole DMA ring (PM_LDS_IMAGE): dfc1 66 -> 61 us, dqkv 51 -> 47, decoder dfc1 118 -> 107.  256-row
+  // tiles with the staged epilogue although the 192-row direct kernel is faster ALONE (59-62 vs 65 us): in the step the chain runs
+  // beside the grouped weight gradients, which hold 108 CUs -- 150 tiles of 256 rows + 108 = the chip, 198 tiles of 192 rows + 108
+  // oversubscribe it and the chain's third of a round queues behind the long weight-gradient workgroups (+1.0 % cls in four
+  // same-box pairs, MAE +0.2 %)
+  if (w_kmajor) return 24;
+  // wide act-typed forward outputs (qkv): ping-pong, LDS-staged epilogue
+  if (epilogue == PM_EPI_STORE && N >= kWideN) return 8;
+  // tall problems (MAE decoder: M = 50 432 -> 197 row tiles, 1.5 rounds of the chip): the epilogue is paid 197 x 2 times and the
+  // direct register epilogue's strided 16-B stores cost more than the staging pass: software-pipelined loop + staged epilogue for
+  // f32 outputs (proj 59 vs 66 us, fc2 145 vs 147), ping-pong + staged for the act-typed qkv (96 vs 102)
+  if (M >= kTallM) return epilogue == PM_EPI_STORE ? 8 : 24;
+  // otherwise the direct register epilogue; whole tiles per CU round: 192-row tiles when they need fewer (rounds x rows)
+  const long nt = (N + 255) / 256;
+  const long c256 = (((M + 255) / 256 * nt + 255) / 256) * 256, c192 = (((M + 191) / 192 * nt + 255) / 256) * 192;
+  const bool rows192 = c192 < c256;
+  // f32 residual outputs: the software-pipelined loop wins (fc2 80 -> 70 us); narrow act-typed / accumulated ones: ping-pong
+  if (epilogue == PM_EPI_RESIDUAL) return rows192 ? 26 : 25;
+  return rows192 ? 10 : 9;
+}
+
+GemmPlan plan_gemm(int a_kmajor, int b_kmajor, int in_dtype, bool has_bias, int c_dtype, bool ldc_is_n, int epilogue, int M, int N,
+                   int K, bool has_ws, size_t ws_bytes, const pm_gemm_opts* opts) {
+  GemmPlan p{PM_OK, PM_GEMM_GENERIC, 0, BM, BN, 1, 0, 0, 0};
+  auto refuse = [&p](int status) { p.status = status; return p; };
+  // per-call options (no process-wide state): the kernel override (bits 0-5: 0 / 1 / a ring cfg; bits 6-7: the weight-gradient
+  // tile) and the number of workgroups a split-K weight gradient may spread over
+  const int variant = opts ? opts->variant : 0;
+  const int force = variant & 63, force_wgrad = (variant >> 6) & 3;
+  if ((variant & ~255) || force_wgrad == 3 || (force > 1 && !find_ring_cfg(force, 0))) return refuse(PM_EINVAL);
+  int wgrad_blocks = (opts && opts->max_blocks > 0) ? opts->max_blocks : 256;
+  if (wgrad_blocks < 16) wgrad_blocks = 16;
+  if (wgrad_blocks > 1024) wgrad_blocks = 1024;
+  if (M <= 0 || N <= 0 || K <= 0) return refuse(PM_ESHAPE);
+  if (!is16(in_dtype) && in_dtype != PM_F32) return refuse(PM_EINVAL);
+  if (!is16(c_dtype) && c_dtype != PM_F32) return refuse(PM_EINVAL);
+  if (is16(in_dtype) && is16(c_dtype) && c_dtype != in_dtype) return refuse(PM_EINVAL);  // a 16-bit C has the operands' type
+  const int epc = is16(in_dtype) ? 8 : 4;
+  // 16-byte global chunks: the contiguous dimension of each operand must be a chunk multiple
+  if (!a_kmajor && (K % epc)) return refuse(PM_EALIGN);
+  if (a_kmajor && (M % epc)) return refuse(PM_EALIGN);
+  if (!b_kmajor && (K % epc)) return refuse(PM_EALIGN);
+  if (b_kmajor && (N % epc)) return refuse(PM_EALIGN);
+  if (N & 3) return refuse(PM_EALIGN);
+  if (epilogue < PM_EPI_STORE || epilogue > PM_EPI_ACCUM) return refuse(PM_EINVAL);
+  if (epilogue == PM_EPI_RESIDUAL && c_dtype != PM_F32) return refuse(PM_EINVAL);
+  if (epilogue == PM_EPI_ACCUM && c_dtype != PM_F32) return refuse(PM_EINVAL);
+  const int ke = is16(in_dtype) ? 64 : 32;
+  if (K % ke) return p;  // the generic kernel
+  // Few tiles (scratch/bench_gemm_smallm.py, profiles/r4_exp3_gemm_smallm*.txt): a problem with fewer than ~half as many
+  // 256 x 256 tiles as the chip has CUs runs ONE partial round of long workgroups on the ring kernel -- its time is a tile's
+  // latency whatever M is (proj at M = 1 600 ... 6 304: 25-28 us) -- while the 128 x 128 LDS-DMA kernel spreads the same work over
+  // 4x the workgroups, two per CU: M = 3 200 (MAE encoder at bs = 64/GPU) qkv 25.3 -> 21.2 us, proj 27.1 -> 18.7, fc2 57.4 -> 43.9,
+  // dfc1 55.0 -> 37.4, dqkv 43.3 -> 29.3; the half-batch forward chains of the fine-tune (M = 6 304) proj 28.1 -> 26.0, fc2 58.7 ->
+  // 54.0; the 512-wide MAE decoder at M = 12 608: dfc1 44.1 -> 38.5, dqkv 35.6 -> 30.7.  The crossover sits between 117 tiles
+  // (128 x 128 wins) and 150 (the ring wins) on all 56 measured (shape, epilogue) points: fewer than 128 tiles -> 128 x 128.
+  // ... in the step the rule holds only where the WHOLE chain is small (profiles/r4_exp4_few_tiles.txt): sent to the
+  // 128 x 128 kernel, the half-batch proj / fc2 of the fine-tune forward (M = 6 304) cost the step 4 % (MAE bs = 256: 1.6 %) although
+  // they are faster alone -- two 66-KB workgroups on a CU keep the other chain's 128-KB ring workgroups off it -- while MAE at
+  // bs = 64/GPU gains 4.5-6 %.  Hence the cap on M.
+  // ... or narrow (N <= 512: the MAE decoder's proj / fc2 / dgrads at bs = 64/GPU, M = 6 304 / 12 608 -- 50 / 100 tiles; the same
+  // experiment: +0.7 % on top; a 512-wide problem never belongs to the fine-tune's or the bs = 256 encoder's half-batch chains).
+  // A forced ring cfg switches the rule off.
+  const long tiles256 = (long)((M + 255) / 256) * ((N + 255) / 256);
+  const bool few_tiles = force == 0 && tiles256 < kFewTiles && (M <= kFewTilesMaxM || N <= kFewTilesNarrowN);
+  // large-tile ring kernel: 16-bit operands, X k-normal (forward and dgrad GEMMs), big M
+  if (is16(in_dtype) && !a_kmajor && (K % V3_KE) == 0 && M >= 1024 && force != 1 && !few_tiles) {
+    const RingCfg* c = find_ring_cfg(force ? force : choose_ring_cfg(b_kmajor, epilogue, M, N), b_kmajor);
+    if (!c) return refuse(PM_EINVAL);  // (a forced cfg that is not built for this W layout)
+    p.family = PM_GEMM_RING;
+    p.cfg = c->cfg;
+    p.tile_m = c->bm;
+    p.tile_n = 256;
+    // Tile order of a wide problem.  xcd_remap hands each XCD a contiguous run of tiles; row by row, a run of ~75 tiles of the dGELU
+    // dgrad (50 x 12 tiles) walks all 12 W panels (4.7 MB: more than the XCD's 4 MB L2, beside a 77-MB stream of saved
+    // pre-activations) six times -- PMC: 205.8 MB fetched per launch against ~135 MB if every XCD read W once.  In bands of 6 tile
+    // columns a run is ~12 row blocks x 6 panels: the band's W (2.4 MB) stays in the L2 while the row blocks stream through once.
+    // Measured (profiles/r4_exp11_tile_bands.txt): dGELU dgrad 205.7 -> 172.7 MB fetched, fc1 + GELU 67.5 -> 57.7 MB; stand-alone
+    // fc1 + GELU 99.5 -> 95.9 us; in the step +0.6 ... +1.2 % (cls), +0.7 % (MAE bs = 256), two same-box rounds each.
+    if ((N + 255) / 256 > kTileBand) p.band = kTileBand;
+    return p;
+  }
+  // split-K: only for f32 plain-store / accumulate outputs without bias (the wgrad shapes: K = #tokens, few tiles)
+  const bool splittable = has_ws && !has_bias && c_dtype == PM_F32 && (epilogue == PM_EPI_STORE || epilogue == PM_EPI_ACCUM) &&
+                          ldc_is_n;
+  // large-K weight gradient (both operands k-major) on the ping-pong ring kernel, split so that tiles x splits ~ one block per CU
+  if (splittable && is16(in_dtype) && a_kmajor && b_kmajor && (K % V3_KE) == 0 && K >= 2048 && M >= 256 && N >= 128 && force != 1) {
+    // 256x256 tiles (twice the MFMAs per barrier) from 2x2 tiles up: ViT-B qkv / fc1 / fc2 gradients 74 us vs 83 with
+    // 256x128; the MAE decoder's 512-wide gradients (K = 50 432 tokens) +2.8 % step rate; neutral for 768x768.
+    const bool wide = force_wgrad ? force_wgrad == 2 : ((M + 255) / 256) * ((N + 255) / 256) >= 4;
+    p.family = PM_GEMM_RING_WGRAD;
+    p.tile_m = 256;
+    p.tile_n = wide ? 256 : 128;
+    const int tiles = ((M + 255) / 256) * ((N + p.tile_n - 1) / p.tile_n);
+    const int nk = K / V3_KE;
+    int split = wgrad_blocks / tiles;
+    if (split > nk / 16) split = nk / 16;
+    if (split > 16) split = 16;
+    if (split < 1) split = 1;
+    while (split > 1 && (size_t)split * M * N * sizeof(float) > ws_bytes) --split;
+    p.ksteps_split = (nk + split - 1) / split;
+    p.split_k = (nk + p.ksteps_split - 1) / p.ksteps_split;  // no empty slice
+    if (split > 1) p.ws_bytes = (size_t)split * M * N * sizeof(float);
+    return p;
+  }
+  p.family = PM_GEMM_LDS128;
+  const int nk = K / ke, tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+  p.ksteps_split = nk;
+  if (splittable && tiles < 256 && nk >= 16) {
+    int split = 512 / tiles;                      // fill the 2-blocks-per-CU machine once
+    if (split > nk / 8) split = nk / 8;           // >= 8 k-steps per split
+    if (split > 16) split = 16;
+    const size_t need = (size_t)split * M * N * sizeof(float);
+    if (split > 1 && need <= ws_bytes) {
+      p.ksteps_split = (nk + split - 1) / split;
+      p.split_k = (nk + p.ksteps_split - 1) / p.ksteps_split;  // no empty split
+      p.ws_bytes = need;
+    }
+  }
+  return p;
+}
+
+// validate the pointers, plan, launch what the plan says
+int gemm_dispatch(const void* A, long lda, int a_kmajor, const void* B, long ldb, int b_kmajor, int in_dtype,
+                  const float* bias, void* C, long ldc, int c_dtype, int epilogue, void* aux, const float* resid, int M, int N,
+                  int K, void* workspace, size_t ws_bytes, const pm_gemm_opts* opts, void* stream) {
+  if (!A || !B || !C) return PM_EINVAL;
+  const GemmPlan p = plan_gemm(a_kmajor, b_kmajor, in_dtype, bias != nullptr, c_dtype, ldc == N, epilogue, M, N, K,
+                               workspace != nullptr, workspace ? ws_bytes : 0, opts);
+  if (p.status) return p.status;
+  const int epc = is16(in_dtype) ? 8 : 4;
+  if ((lda % epc) || (ldb % epc) || (ldc & 3)) return PM_EALIGN;  // leading dimensions: whole 16-byte chunks
+  if (((uintptr_t)A & 15) || ((uintptr_t)B & 15) || ((uintptr_t)C & 15)) return PM_EALIGN;
+  if (epilogue == PM_EPI_DGELU && !aux) return PM_EINVAL;   // (GELU without aux: the pre-activation is not kept -- forward-only use)
+  if (epilogue == PM_EPI_RESIDUAL && !resid) return PM_EINVAL;
+  GemmArgs a;
+  a.X = A; a.W = B; a.ldx = lda; a.ldw = ldb; a.bias = bias; a.C = C; a.ldc = ldc; a.aux = aux; a.resid = resid;
+  a.M = M; a.N = N; a.K = K; a.epilogue = epilogue; a.c_dtype = c_dtype;
+  a.tiles_m = (M + p.tile_m - 1) / p.tile_m;
+  a.tiles_n = (N + p.tile_n - 1) / p.tile_n;
+  a.split_k = p.split_k;
+  a.ksteps_split = p.ksteps_split;
+  a.xsum = nullptr;
+  a.xsum_store = 0;
+  a.col_major = p.band;
+#ifdef PM_GEMM_STAMP
+  a.stamps = g_stamps;
+#endif
+  if (p.split_k > 1) {  // the kernel writes f32 partial slabs, the reduce launch applies STORE / ACCUM
+    a.C = workspace;
+    a.epilogue = PM_EPI_STORE;
+  }
+  hipStream_t s = pm_stream(stream);
+  int st = PM_EINVAL;
+  switch (p.family) {
+    case PM_GEMM_GENERIC: PM_DISPATCH_ACT(in_dtype, T, st = launch_generic<T>(a, a_kmajor, b_kmajor, s)); break;
+    case PM_GEMM_LDS128: PM_DISPATCH_ACT(in_dtype, T, st = launch_glds<T>(a, a_kmajor, b_kmajor, s)); break;
+    case PM_GEMM_RING: PM_DISPATCH_16(in_dtype, E, st = launch_ring<E>(p.cfg, a, b_kmajor, s)); break;
+    case PM_GEMM_RING_WGRAD:  // direct epilogue, ping-pong loop
+      PM_DISPATCH_16(in_dtype, E, st = p.tile_n == 128 ? launch_v3<E, 256, 128, true, true, true, true>(a, s)
+                                                       : launch_v3<E, 256, 256, true, true, true, true>(a, s));
+      break;
+  }
+  if (st || p.split_k == 1) return st;
+  return launch_splitk_reduce(workspace, C, ldc, M, N, p.split_k, epilogue == PM_EPI_ACCUM, s);
+}
+
+}  // namespace
+
+extern "C" int pm_gemm_plan(int a_kmajor, int b_kmajor, int in_dtype, int has_bias, int c_dtype, int ldc_is_n, int epilogue, int M,
+                            int N, int K, size_t ws_bytes, const pm_gemm_opts* opts, pm_gemm_plan_info* info) {
+  const GemmPlan p = plan_gemm(a_kmajor, b_kmajor, in_dtype, has_bias != 0, c_dtype, ldc_is_n != 0, epilogue, M, N, K, ws_bytes > 0,
+                               ws_bytes, opts);
+  if (p.status == PM_OK && info)
+    *info = pm_gemm_plan_info{p.family, p.cfg, p.tile_m, p.tile_n, p.split_k, p.band, p.ws_bytes};
+  return p.status;
+}
+
+// the split-K slabs of a weight gradient (both operands k-major; f32 dW, no bias) when the caller can give any amount
+extern "C" size_t pm_gemm_workspace_bytes(int a_kmajor, int b_kmajor, int in_dtype, int M, int N, int K,
+                                          const pm_gemm_opts* opts) {
+  if (!(a_kmajor && b_kmajor)) return 0;  // only the split-K weight gradients use scratch
+  const GemmPlan p = plan_gemm(a_kmajor, b_kmajor, in_dtype, false, PM_F32, true, PM_EPI_STORE, M, N, K, true, (size_t)-1, opts);
+  return p.status == PM_OK ? p.ws_bytes : 0;
+}
+
+#ifdef PM_GEMM_STAMP
 extern "C" void pm_debug_gemm_stamps(void* p) { g_stamps = reinterpret_cast<unsigned long long*>(p); }
 #endif
 
@@ -1548,226 +1554,6 @@ extern "C" int pm_gemm_ws(const void* A, long lda, int a_kmajor, const void* B, 
   return gemm_dispatch(A, lda, a_kmajor, B, ldb, b_kmajor, in_dtype, bias, C, ldc, c_dtype, epilogue, aux, resid, M, N, K,
                        workspace, ws_bytes, nullptr, stream);
 }
-
-namespace {
-
-// tuning hook, read once: PM_CFG_CLASS="<nt_store>,<nt_gelu>,<nt_residual>,<nn_store>,<nn_dgelu>" forces a ring-kernel variant per
-// (operand layout, epilogue) class for in-step A/B runs (0 = the heuristics); unset in production
-const int* cfg_class_override() {
-  static int v[5] = {0, 0, 0, 0, 0};
-  static const bool init = [] {
-    const char* e = getenv("PM_CFG_CLASS");
-    if (e) sscanf(e, "%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4]);
-    return true;
-  }();
-  (void)init;
-  return v;
-}
-int tall_m() {  // tuning hook, read once: row count from which a problem counts as "tall" (see gemm_dispatch)
-  static const int v = [] { const char* e = getenv("PM_TALL_M"); return e && e[0] ? atoi(e) : 20000; }();
-  return v;
-}
-int few_tiles_threshold() {  // tuning hook, read once: PM_FEW_TILES=0 keeps every M >= 1024 problem on the ring kernel (round-3 dispatch)
-  static const int v = [] { const char* e = getenv("PM_FEW_TILES"); return e && e[0] ? atoi(e) : 128; }();
-  return v;
-}
-// A/B switch, read once on the host and carried in GemmArgs: PM_EPI_HOIST=0 restores the 128 x 128 kernel's per-vector epilogue
-int epi_hoist_host() {
-  static const int v = [] { const char* e = getenv("PM_EPI_HOIST"); return e && e[0] ? atoi(e) : 1; }();
-  return v;
-}
-int tile_band() {  // tuning hook, read once: forward / dgrad tiles walk bands of PM_TILE_BAND tile columns (default 6; 0: row by row)
-  static const int v = [] { const char* e = getenv("PM_TILE_BAND"); return e && e[0] ? atoi(e) : 6; }();
-  return v;
-}
-int few_tiles_narrow_n() {  // tuning hook, read once: widest N for which the few-tiles rule ignores the cap on M
-  static const int v = [] { const char* e = getenv("PM_FEW_TILES_NARROW_N"); return e && e[0] ? atoi(e) : 512; }();
-  return v;
-}
-int few_tiles_max_m() {  // tuning hook, read once: largest M the few-tiles rule applies to
-  static const int v = [] { const char* e = getenv("PM_FEW_TILES_MAXM"); return e && e[0] ? atoi(e) : 4096; }();
-  return v;
-}
-bool dgrad_pp() {  // A/B switch, read once: dgrads on the ping-pong loop
-  static const bool v = [] { const char* e = getenv("PM_DGRAD_PP"); return e && e[0] == '1'; }();
-  return v;
-}
-
-int gemm_dispatch(const void* A, long lda, int a_kmajor, const void* B, long ldb, int b_kmajor, int in_dtype,
-                  const float* bias, void* C, long ldc, int c_dtype, int epilogue, void* aux, const float* resid, int M, int N,
-                  int K, void* workspace, size_t ws_bytes, const pm_gemm_opts* opts, void* stream) {
-  // per-call options (no process-wide state): kernel variant override (tuning scripts, tests) and the number of
-  // workgroups a split-K weight gradient may spread over
-  const int force_cfg = opts ? opts->variant : 0;
-  int wgrad_blocks = (opts && opts->max_blocks > 0) ? opts->max_blocks : 256;
-  if (wgrad_blocks < 16) wgrad_blocks = 16;
-  if (wgrad_blocks > 1024) wgrad_blocks = 1024;
-  if (!A || !B || !C) return PM_EINVAL;
-  if (M <= 0 || N <= 0 || K <= 0) return PM_ESHAPE;
-  if (!is16(in_dtype) && in_dtype != PM_F32) return PM_EINVAL;
-  if (!is16(c_dtype) && c_dtype != PM_F32) return PM_EINVAL;
-  if (is16(in_dtype) && is16(c_dtype) && c_dtype != in_dtype) return PM_EINVAL;  // a 16-bit C has the operands' type
-  const int epc = is16(in_dtype) ? 8 : 4;
-  // 16-byte global chunks: the contiguous dimension of each operand and its leading dimension must be chunk multiples
-  if ((lda % epc) || (ldb % epc)) return PM_EALIGN;
-  if (!a_kmajor && (K % epc)) return PM_EALIGN;
-  if (a_kmajor && (M % epc)) return PM_EALIGN;
-  if (!b_kmajor && (K % epc)) return PM_EALIGN;
-  if (b_kmajor && (N % epc)) return PM_EALIGN;
-  if ((N & 3) || (ldc & 3)) return PM_EALIGN;
-  if (((uintptr_t)A & 15) || ((uintptr_t)B & 15) || ((uintptr_t)C & 15)) return PM_EALIGN;
-  if (epilogue < PM_EPI_STORE || epilogue > PM_EPI_ACCUM) return PM_EINVAL;
-  if (epilogue == PM_EPI_DGELU && !aux) return PM_EINVAL;   // (GELU without aux: the pre-activation is not kept -- forward-only use)
-  if (epilogue == PM_EPI_RESIDUAL && (!resid || c_dtype != PM_F32)) return PM_EINVAL;
-  if (epilogue == PM_EPI_ACCUM && c_dtype != PM_F32) return PM_EINVAL;
-  GemmArgs a;
-  a.X = A; a.W = B; a.ldx = lda; a.ldw = ldb; a.bias = bias; a.C = C; a.ldc = ldc; a.aux = aux; a.resid = resid;
-  a.M = M; a.N = N; a.K = K; a.epilogue = epilogue; a.c_dtype = c_dtype;
-  a.tiles_m = (M + BM - 1) / BM;
-  a.tiles_n = (N + BN - 1) / BN;
-  a.split_k = 1;
-  a.xsum = nullptr;
-  a.xsum_store = 0;
-  // Tile order of a wide problem (experiment 11, round 4).  xcd_remap hands each XCD a contiguous run of tiles; row by row, a run of
-  // ~75 tiles of the dGELU dgrad (50 x 12 tiles) walks all 12 W panels (4.7 MB: more than the XCD's 4 MB L2, beside a 77-MB stream of
-  // saved pre-activations) six times -- PMC: 205.8 MB fetched per launch against ~135 MB if every XCD read W once.  In bands of 6 tile
-  // columns a run is ~12 row blocks x 6 panels: the band's W (2.4 MB) stays in the L2 while the row blocks stream through once.
-  // Measured (profiles/r4_exp11_tile_bands.txt): dGELU dgrad 205.7 -> 172.7 MB fetched, fc1 + GELU 67.5 -> 57.7 MB; stand-alone fc1 + GELU
-  // 99.5 -> 95.9 us; in the step +0.6 ... +1.2 % (cls), +0.7 % (MAE bs = 256), two same-box rounds each.
-  a.epi_hoist = epi_hoist_host();
-  a.col_major = 0;
-  {
-    const int band = tile_band();
-    const int tn256 = (N + 255) / 256;
-    if (band >= 2 && tn256 > band && !a_kmajor) a.col_major = band;
-  }
-#ifdef PM_GEMM_STAMP
-  a.stamps = g_stamps;
-#endif
-  hipStream_t s = pm_stream(stream);
-  const int ke = is16(in_dtype) ? 64 : 32;
-  const bool fast = (K % ke) == 0;
-  if (!fast) {
-    a.ksteps_split = 0;
-    PM_DISPATCH_ACT(in_dtype, T, return launch_generic<T>(a, a_kmajor, b_kmajor, s));
-    return PM_EINVAL;
-  }
-  // Few tiles (round 4, scratch/bench_gemm_smallm.py, profiles/r4_exp3_gemm_smallm*.txt): a problem with fewer than ~half as many
-  // 256 x 256 tiles as the chip has CUs runs ONE partial round of long workgroups on the ring kernel -- its time is a tile's
-  // latency whatever M is (proj at M = 1 600 ... 6 304: 25-28 us) -- while the 128 x 128 LDS-DMA kernel spreads the same work over
-  // 4x the workgroups, two per CU: M = 3 200 (MAE encoder at bs = 64/GPU) qkv 25.3 -> 21.2 us, proj 27.1 -> 18.7, fc2 57.4 -> 43.9,
-  // dfc1 55.0 -> 37.4, dqkv 43.3 -> 29.3; the half-batch forward chains of the fine-tune (M = 6 304) proj 28.1 -> 26.0, fc2 58.7 ->
-  // 54.0; the 512-wide MAE decoder at M = 12 608: dfc1 44.1 -> 38.5, dqkv 35.6 -> 30.7.  The crossover sits between 117 tiles
-  // (128 x 128 wins) and 150 (the ring wins) on all 56 measured (shape, epilogue) points: fewer than 128 tiles -> 128 x 128.
-  const long tiles256 = (long)((M + 255) / 256) * ((N + 255) / 256);
-  // ... in the step the rule holds only where the WHOLE chain is small (experiment 4, profiles/r4_exp4_few_tiles.txt): sent to the
-  // 128 x 128 kernel, the half-batch proj / fc2 of the fine-tune forward (M = 6 304) cost the step 4 % (MAE bs = 256: 1.6 %) although
-  // they are faster alone -- two 66-KB workgroups on a CU keep the other chain's 128-KB ring workgroups off it -- while MAE at
-  // bs = 64/GPU gains 4.5-6 %.  Hence the cap on M.
-  // ... or narrow (N <= 512: the MAE decoder's proj / fc2 / dgrads at bs = 64/GPU, M = 6 304 / 12 608 -- 50 / 100 tiles; the same
-  // experiment: +0.7 % on top; a 512-wide problem never belongs to the fine-tune's or the bs = 256 encoder's half-batch chains).
-  const bool few_tiles = (force_cfg & 63) == 0 && tiles256 < few_tiles_threshold() &&
-                         (M <= few_tiles_max_m() || N <= few_tiles_narrow_n());
-  // large-tile ring kernel: bf16, X k-normal (forward and dgrad GEMMs), big M
-  if (is16(in_dtype) && !a_kmajor && (K % V3_KE) == 0 && M >= 1024 && (force_cfg & 63) != 1 && !few_tiles) {
-    // Tile / pipeline choice, tuned on the ViT-B/16 shapes at M = 12608 (scratch/bench_gemm6.py).
-    // pm_debug_gemm_config(cfg) forces one of the variants below (0 = the heuristics).
-    int cfg = force_cfg & 63;
-    if (cfg == 0) {
-      // 256x256 ping-pong everywhere; LDS-staged epilogue for the wide act-typed outputs (qkv, fc1+GELU: whole
-      // 128-B row segments per store), direct register epilogue for f32 residual outputs and the dgrads
-      const bool wide_act = epilogue == PM_EPI_GELU || (epilogue == PM_EPI_STORE && !b_kmajor && N >= 2048);
-      cfg = wide_act ? 8 : 9;
-      if (cfg == 9) {  // whole tiles per CU round: 192-row tiles when they need fewer (rounds x rows)
-        const long nt = (N + 255) / 256;
-        const long c256 = (((M + 255) / 256 * nt + 255) / 256) * 256, c192 = (((M + 191) / 192 * nt + 255) / 256) * 192;
-        if (c192 < c256) cfg = 10;
-        // f32 residual outputs of the forward (k-normal W): the software-pipelined loop wins (fc2 80 -> 70 us);
-        // so it does for every dgrad (W read as stored by ds_read_b64_tr_b16) since those reads stopped waiting for the
-        // whole DMA ring (PM_LDS_IMAGE): dfc1 66 -> 61 us, dqkv 51 -> 47, dfc2 101 -> 96, decoder dfc1 118 -> 107
-        if ((epilogue == PM_EPI_RESIDUAL && !b_kmajor) || (b_kmajor && !dgrad_pp())) cfg = cfg == 10 ? 26 : 25;
-        // round 3 (scratch/archive_r3/r3_exp1.sh, r3_exp3.sh):
-        //  * the dGELU dgrad (reads the saved pre-activation, writes an act-typed [M, 4D] tensor) goes to the ping-pong loop
-        //    with the LDS-staged epilogue: stand-alone 96.8 vs 95.1 us at ViT-B, 197 vs 220 us at the MAE decoder, and
-        //    +0.6 % cls step rate in-step (whole 128-B row segments per store instead of 16-B pieces at a 6-KB stride)
-        //  * tall problems (MAE decoder: M = 50 432 -> 197 row tiles, 1.5 rounds of the chip): the epilogue is paid 197 x 2
-        //    times and the direct register epilogue's strided 16-B stores cost more than the staging pass: software-pipelined
-        //    loop + staged epilogue (cfg 24) for f32-residual and dgrad outputs (proj 59 vs 66 us, fc2 145 vs 147, dqkv 80 vs
-        //    83, dproj 37.5 vs 38.5), ping-pong + staged (cfg 8) for the act-typed qkv (96 vs 102)
-        //  * plain dgrads (dfc1 / dproj / dqkv: N = 768): 256-row tiles with the staged epilogue (cfg 24) although the 192-row
-        //    direct kernel is faster ALONE (59-62 vs 65 us): in the step the chain runs beside the grouped weight gradients,
-        //    which hold 108 CUs -- 150 tiles of 256 rows + 108 = the chip, 198 tiles of 192 rows + 108 oversubscribe it and the
-        //    chain's third of a round queues behind the long weight-gradient workgroups (scratch/archive_r3/r3_exp8.sh, r3_exp9.sh:
-        //    +1.0 % cls in four same-box pairs, MAE +0.2 %)
-        if (epilogue == PM_EPI_DGELU && !dgrad_pp()) cfg = 8;
-        else if (b_kmajor && !dgrad_pp()) cfg = 24;
-        else if (M >= tall_m()) cfg = (epilogue == PM_EPI_STORE && !b_kmajor) ? 8 : 24;
-      }
-      const int cls = !b_kmajor ? (epilogue == PM_EPI_GELU ? 1 : epilogue == PM_EPI_RESIDUAL ? 2 : 0) : (epilogue == PM_EPI_DGELU ? 4 : 3);
-      if (cfg_class_override()[cls]) cfg = cfg_class_override()[cls];
-    }
-    PM_DISPATCH_16(in_dtype, E, return launch_v3_cfg<E>(cfg, a, b_kmajor, s));
-  }
-  const int nk = K / ke;
-  a.ksteps_split = nk;
-  // split-K: only for f32 plain-store / accumulate outputs without bias (the wgrad shapes: K = #tokens, few tiles)
-  const int tiles = a.tiles_m * a.tiles_n;
-  const bool splittable = workspace && !bias && c_dtype == PM_F32 && (epilogue == PM_EPI_STORE || epilogue == PM_EPI_ACCUM) &&
-                          ldc == N;
-  // large-K wgrad on the ping-pong ring kernel: 256x128 tiles, split so that tiles x splits ~ one block per CU
-  if (splittable && wgrad_ring_shape(in_dtype, a_kmajor, b_kmajor, M, N, K) && (force_cfg & 63) != 1) {
-    // 256x256 tiles (twice the MFMAs per barrier) from 2x2 tiles up: ViT-B qkv / fc1 / fc2 gradients 74 us vs 83 with
-    // 256x128; the MAE decoder's 512-wide gradients (K = 50 432 tokens) +2.8 % step rate; neutral for 768x768.
-    // Tuning hook bits 6-7: 1 = force 256x128, 2 = force 256x256, 3 = software-pipelined 256x256 (slower: tr reads).
-    const WgradPlan plan = plan_wgrad(M, N, K, force_cfg, wgrad_blocks, ws_bytes);
-    const int wv = plan.wv, nk3 = K / V3_KE, split = plan.split;
-    GemmArgs w = a;
-    w.ksteps_split = (nk3 + split - 1) / split;
-    w.split_k = (nk3 + w.ksteps_split - 1) / w.ksteps_split;
-    void* out = a.C;
-    if (w.split_k > 1) {
-      w.C = workspace;
-      w.epilogue = PM_EPI_STORE;
-    }
-    int st = PM_EINVAL;
-    PM_DISPATCH_16(in_dtype, E, st = wv == 1   ? launch_v3_wgrad<E, 256, 128, 4, 2, false>(w, s)
-                                     : wv == 2 ? launch_v3_wgrad<E, 256, 256, 2, 4, false>(w, s)
-                                               : launch_v3_wgrad<E, 256, 256, 2, 4, true>(w, s));
-    if (st || w.split_k == 1) return st;
-    const long nvec = (long)M * (N >> 2);
-    int grid = (int)((nvec + 255) / 256);
-    if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid), dim3(256), 0, s, (const float*)workspace, (float*)out, ldc, M, N,
-                       w.split_k, epilogue == PM_EPI_ACCUM ? 1 : 0);
-    return pm_check_launch();
-  }
-  if (splittable && tiles < 256 && nk >= 16) {
-    int split = 512 / tiles;                      // fill the 2-blocks-per-CU machine once
-    if (split > nk / 8) split = nk / 8;           // >= 8 k-steps per split
-    if (split > 16) split = 16;
-    const size_t need = (size_t)split * M * N * sizeof(float);
-    if (split > 1 && need <= ws_bytes) {
-      a.split_k = split;
-      a.ksteps_split = (nk + split - 1) / split;
-      a.split_k = (nk + a.ksteps_split - 1) / a.ksteps_split;  // no empty split
-      void* out = a.C;
-      a.C = workspace;
-      int st = PM_EINVAL;
-      PM_DISPATCH_ACT(in_dtype, T, st = launch_glds<T>(a, a_kmajor, b_kmajor, s));
-      if (st) return st;
-      const long nvec = (long)M * (N >> 2);
-      int grid = (int)((nvec + 255) / 256);
-      if (grid > 2048) grid = 2048;
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(grid), dim3(256), 0, s, (const float*)workspace, (float*)out, ldc, M, N,
-                         a.split_k, epilogue == PM_EPI_ACCUM ? 1 : 0);
-      return pm_check_launch();
-    }
-  }
-  PM_DISPATCH_ACT(in_dtype, T, return launch_glds<T>(a, a_kmajor, b_kmajor, s));
-  return PM_EINVAL;
-}
-
-}  // namespace
 
 extern "C" int pm_gemm_colsum(const void* A, long lda, int a_kmajor, const void* B, long ldb, int b_kmajor, int in_dtype,
                               const float* bias, void* C, long ldc, int c_dtype, int epilogue, void* aux,
@@ -1789,40 +1575,8 @@ extern "C" int pm_gemm(const void* A, long lda, int a_kmajor, const void* B, lon
 
 namespace {
 
-// A/B switch, read once: PM_GROUP_ORDER=0 walks every problem's tiles row by row (round-2 behaviour)
-int group_order_auto() {
-  static const int v = [] { const char* e = getenv("PM_GROUP_ORDER"); return (e && e[0] == '0') ? 0 : 1; }();
-  return v;
-}
-
-// tuning hook, read once: work items (tiles x k-slices) a group with few tiles is cut into (default 224 of the 256 CUs)
-int group_split_target() {
-  static const int v = [] { const char* e = getenv("PM_GROUP_SPLIT_TARGET"); return e && e[0] ? atoi(e) : 224; }();
-  return v;
-}
-
-// tuning hooks, read once: a whole-K group of at most PM_GROUP_CONFINE_WORK tiles (default 0 = off) runs on PM_GROUP_CONFINE_XCDS XCDs
-int group_confine_xcds() {
-  static const int v = [] { const char* e = getenv("PM_GROUP_CONFINE_XCDS"); const int x = e && e[0] ? atoi(e) : 4; return x < 1 ? 1 : (x > 8 ? 8 : x); }();
-  return v;
-}
-int group_confine_max_work() {
-  static const int v = [] { const char* e = getenv("PM_GROUP_CONFINE_WORK"); return e && e[0] ? atoi(e) : 0; }();
-  return v;
-}
-
-// experiment hook, read once: PM_GROUP_KERNEL=4 -> the 4-wave (one wave per SIMD, 128 x 128 per wave) software-pipelined body
-int group_kernel_waves() {
-  static const int v = [] { const char* e = getenv("PM_GROUP_KERNEL"); return e && e[0] ? atoi(e) : 8; }();
-  return v;
-}
-
-// experiment hook, read once: PM_GROUP_FORCE_SPLIT=2|3 cuts the tiles of a LARGE group (ViT-B block: 108 tiles) into k-slices too,
-// so that a launch limited to fewer workgroups than tiles (max_blocks) walks equal shares (scratch/archive_r3/r3_exp17.sh)
-int group_force_split() {
-  static const int v = [] { const char* e = getenv("PM_GROUP_FORCE_SPLIT"); return e && e[0] ? atoi(e) : 0; }();
-  return v;
-}
+// work items (tiles x k-slices) a group with few tiles is cut into: 224 of the 256 CUs
+constexpr int kGroupSplitTarget = 224;
 
 struct GroupPlan {
   int status;        // PM_OK or the refusal
@@ -1851,8 +1605,8 @@ GroupPlan plan_group(const pm_wgrad_item* items, int n, int K, int in_dtype) {
   // block: 48 tiles, K = 50 432 tokens): each tile is cut into k-slices so that tiles x slices ~ the chip (48 x 4 = 192 work
   // items of 394 k-steps), f32 partials in the caller's workspace, ONE reduce launch for the whole group.
   const int nk = K / V3_KE;
-  if (t256 < 64 || group_force_split() > 1) {
-    int split = t256 < 64 ? (int)(group_split_target() / t256) : group_force_split();
+  if (t256 < 64) {
+    int split = (int)(kGroupSplitTarget / t256);
     if (split > 8) split = 8;
     if (split > nk / 128) split = nk / 128;  // >= 128 k-steps per slice: prologue / epilogue stay small
     if (split > 1) {
@@ -1907,7 +1661,6 @@ extern "C" int pm_wgrad_group(const pm_wgrad_item* items, int n, int K, int in_d
   const int bn = pl.bn;
   WgradGroupArgs g;
   g.n = n; g.K = K; g.split = pl.split; g.ksteps_split = pl.ksteps_split;
-  g.auto_order = group_order_auto();
 #ifdef PM_GEMM_STAMP
   g.stamps = g_stamps ? g_stamps + 4096L * 8 * 16 : nullptr;  // rows [4096, 4608) x 8 waves of the caller's stamp buffer
 #endif
@@ -1942,34 +1695,21 @@ extern "C" int pm_wgrad_group(const pm_wgrad_item* items, int n, int K, int in_d
       if (items[i].dbias) g.bias_total += items[i].n_out;
   const int work = total * pl.split;
   int grid = work;
-  g.xcds = 8;
   if (max_blocks > 0 && max_blocks < work) {
     grid = (max_blocks / 8) * 8;  // whole XCD rounds: a workgroup keeps walking its own XCD's run of items
     if (grid < 8) grid = 8;
     if (grid > work) grid = work;
-  } else if (pl.split == 1 && work <= group_confine_max_work() && group_confine_xcds() < 8) {
-    // A small whole-K group (the (proj, qkv) launch of a ViT-B block: 36 tiles) on all 8 XCDs gives each L2 a run of 4-5 tiles:
-    // few tiles share a dY / X panel in one L2, the panels are fetched by several (PMC: 258.8 MB against 125.7 MB algorithmic).
-    // Confined to 4 XCDs the runs are 9 tiles long.  The hardware deals workgroups to the XCDs round-robin by id, so the grid is
-    // 8 / xcds times the work and the workgroups that land on the other XCDs return at once.
-    g.xcds = group_confine_xcds();
-    grid = (work + g.xcds - 1) / g.xcds * 8;
   }
   hipStream_t s = pm_stream(stream);
   PM_DISPATCH_16(in_dtype, E, {
-    if (bn == 256 && group_kernel_waves() == 4) {
-      auto kern = wgrad_group_kernel<256, 256, 2, 2, E, 4>;
-      constexpr int ring = 4 * (256 + 256) * 64;
-      PM_ALLOW_LDS(kern, ring);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), ring, s, g);
-    } else if (bn == 256) {
-      auto kern = wgrad_group_kernel<256, 256, 2, 4, E>;
-      constexpr int ring = 4 * (256 + 256) * 64;
+    if (bn == 256) {
+      auto kern = wgrad_group_kernel<256, E>;
+      constexpr int ring = V3_STAGES * (256 + 256) * 64;
       PM_ALLOW_LDS(kern, ring);
       hipLaunchKernelGGL(kern, dim3(grid), dim3(512), ring, s, g);
     } else {
-      auto kern = wgrad_group_kernel<256, 128, 4, 2, E>;
-      constexpr int ring = 4 * (256 + 128) * 64;
+      auto kern = wgrad_group_kernel<128, E>;
+      constexpr int ring = V3_STAGES * (256 + 128) * 64;
       PM_ALLOW_LDS(kern, ring);
       hipLaunchKernelGGL(kern, dim3(grid), dim3(512), ring, s, g);
     }

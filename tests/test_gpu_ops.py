@@ -188,7 +188,11 @@ def test_linear_helpers_match_autograd(prec):
     (768, 3072, 8192, "tn", "accum"), (520, 136, 4096, "tn", "store")])
 @pytest.mark.parametrize("prec", ["bf16", "fp16"])
 def test_gemm_large_tile_paths(M, N, K, layout, epi, prec):
-    """Shapes that dispatch to the 256-wide ping-pong ring kernels (forward / dgrad / split-K wgrad), tails included."""
+    """Forward / dgrad / split-K wgrad shapes at a ragged M = 4000, as the dispatcher sends them (pm_gemm_plan, checked on the CPU in
+    tests/test_host_cpu.py): (4000, 2304, 768) nt store and (4000, 3072, 768) nn dgelu run on ring cfg 8;
+    (4000, 768, 3072) nt resid, (4000, 768, 2304) nn store (48 tiles of 256 x 256) and (4000, 1536, 512) nt gelu (96 tiles) go to
+    the 128 x 128 LDS-DMA kernel by the few-tiles rule (fewer than 128 tiles, M <= 4096); the three k-major-A shapes run the split-K ring weight-gradient kernels, (520, 136) on 256 x 128
+    tiles and the other two on 256 x 256.  Every ring configuration is forced in test_gemm_ring_variants."""
     from ssl4polyp_amd._lib import EPI_ACCUM, EPI_DGELU, EPI_GELU, EPI_RESIDUAL, EPI_STORE
     k = _k(prec)
     bf = k.act_dtype
@@ -225,6 +229,78 @@ def test_gemm_large_tile_paths(M, N, K, layout, epi, prec):
         p32 = pre.float().requires_grad_(True)
         F.gelu(p32).backward(acc)
         assert rel(C.float(), p32.grad) < t16
+
+
+# every shipped ring configuration on the (W layout, epilogue) pairs the heuristics send to it
+RING_PAIRS = {
+    8: [("nt", "store"), ("nt", "gelu"), ("nn", "dgelu")],
+    9: [("nt", "store"), ("nt", "accum")],
+    10: [("nt", "store"), ("nt", "accum")],
+    24: [("nt", "resid"), ("nt", "store"), ("nt", "accum"), ("nn", "store")],
+    25: [("nt", "resid")],
+    26: [("nt", "resid")],
+}
+RING_PAIRS[1] = sorted({p for v in RING_PAIRS.values() for p in v})  # the 128 x 128 kernels on the same cases
+# M = 1031: a ragged last tile of 7 rows at 256 and of 71 rows at 192 (12 DMA pieces over 8 waves); N = 264: two tile columns, the
+# last 8 wide; K = 32 ... 160: 1, 2, 3, 5 k-steps = every prologue / tail branch of both k-loops; the wide shape: 8 tile columns
+# = a full band of 6 and a narrow one of 2, 9 k-steps
+RING_SHAPES = [(1031, 264, 32), (1031, 264, 64), (1031, 264, 96), (1031, 264, 160), (1031, 1800, 288)]
+_ring_inputs = {}
+
+
+def _ring_case(prec, M, N, K):
+    """Operands and float32 references of one shape, computed once and shared by every variant (never written to)."""
+    key = (prec, M, N, K)
+    if key not in _ring_inputs:
+        dt = _k(prec).act_dtype
+        A, B = rnd(M, K, seed=90, scale=0.5).to(dt), rnd(N, K, seed=91, scale=0.5).to(dt)
+        bias, base, pre = rnd(N, seed=92), rnd(M, N, seed=93), rnd(M, N, seed=94).to(dt)
+        acc = A.float() @ B.float().t()
+        p32 = pre.float().requires_grad_(True)
+        F.gelu(p32).backward(acc)
+        _ring_inputs[key] = dict(A=A, B=B, Bt=B.t().contiguous(), bias=bias, base=base, pre=pre, acc=acc, dgelu=p32.grad)
+    return _ring_inputs[key]
+
+
+@pytest.mark.parametrize("variant", [8, 9, 10, 24, 25, 26, 1])
+@pytest.mark.parametrize("prec", ["bf16", "fp16"])
+def test_gemm_ring_variants(prec, variant):
+    """Each shipped ring kernel, forced through gemm_variant, against float32 A @ B.T of the rounded operands; C carries a guard
+    row behind row M that must keep its fill value."""
+    from ssl4polyp_amd._lib import EPI_ACCUM, EPI_DGELU, EPI_GELU, EPI_RESIDUAL, EPI_STORE
+    k = _k(prec)
+    k.gemm_variant = variant
+    dt, t16, fill = k.act_dtype, ptol(prec, 1e-2, 0), 7.0
+    for M, N, K in RING_SHAPES:
+        c = _ring_case(prec, M, N, K)
+        tol = 3e-5 * math.sqrt(K / 32)
+        for layout, epi in RING_PAIRS[variant]:
+            b_mat, ldb, bkm = (c["B"], K, 0) if layout == "nt" else (c["Bt"], N, 1)
+            bias = c["bias"] if layout == "nt" and epi != "accum" else None
+            want = c["acc"] + (bias if bias is not None else 0)
+            C = torch.full((M + 1, N), fill, device=DEV, dtype=dt if epi in ("store", "gelu", "dgelu") else torch.float32)
+            what = f"variant {variant} {prec} {(M, N, K)} {layout} {epi}"
+            if epi == "store":
+                k.gemm(c["A"], K, 0, b_mat, ldb, bkm, bias, C, N, EPI_STORE, M, N, K)
+                err, bound = rel(C[:M].float(), want), t16
+            elif epi == "accum":
+                C[:M] = c["base"]
+                k.gemm(c["A"], K, 0, b_mat, ldb, bkm, None, C, N, EPI_ACCUM, M, N, K)
+                err, bound = rel(C[:M], c["base"] + want), tol
+            elif epi == "resid":
+                k.gemm(c["A"], K, 0, b_mat, ldb, bkm, bias, C, N, EPI_RESIDUAL, M, N, K, resid=c["base"])
+                err, bound = rel(C[:M], c["base"] + want), tol
+            elif epi == "gelu":
+                aux = torch.full((M + 1, N), fill, device=DEV, dtype=dt)
+                k.gemm(c["A"], K, 0, b_mat, ldb, bkm, bias, C, N, EPI_GELU, M, N, K, aux=aux)
+                err, bound = max(rel(aux[:M].float(), want), rel(C[:M].float(), F.gelu(aux[:M].float()))), t16
+                assert bool((aux[M] == fill).all()), what + ": aux guard row written"
+            else:
+                k.gemm(c["A"], K, 0, b_mat, ldb, bkm, None, C, N, EPI_DGELU, M, N, K, aux=c["pre"])
+                err, bound = rel(C[:M].float(), c["dgelu"]), t16
+            print(f"{what}: err {err:.3e} bound {bound:.3e}")
+            assert err < bound, what
+            assert bool((C[M] == fill).all()), what + ": guard row written"
 
 
 @pytest.mark.parametrize("M,N,K,layout,epi", [

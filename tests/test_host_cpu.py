@@ -37,7 +37,7 @@ def test_library_exports_every_declared_symbol(built):
     assert set(_lib.SIGNATURES) | {"pm_strerror", "pm_abi_version", "pm_gemm_workspace_bytes", "pm_workspace_bytes",
                                    "pm_wgrad_group_workspace_bytes", "pm_aug_resized_crop_workspace_bytes"} == set(names)
     handle = _lib.load()
-    assert handle.pm_abi_version() == _lib.ABI_VERSION == 14
+    assert handle.pm_abi_version() == _lib.ABI_VERSION == 15
     # nothing undeclared leaves the library: every exported pm_* symbol is in the header (diagnostic hooks included)
     import subprocess
     out = subprocess.run(["nm", "-D", "--defined-only", built], capture_output=True, text=True).stdout
@@ -62,6 +62,83 @@ def test_library_exports_every_declared_symbol(built):
     assert handle.pm_wgrad_group_workspace_bytes(group(dec, (1, 3)), 4, 50432, _lib.PM_BF16) == \
         4 * 4 * sum(o * i for o, i in dec) + 4 * 4 * (2048 + 1536)
     assert handle.pm_wgrad_group_workspace_bytes(group(dec, ()), 4, 2112, _lib.PM_BF16) == 0
+
+
+def _gemm_plan(handle, a_kmajor, b_kmajor, in_dtype, has_bias, c_dtype, epilogue, M, N, K, max_blocks=0, variant=0, ws_bytes=0):
+    """pm_gemm_plan -> (status, (family, cfg, tile_m, tile_n, split_k, band, ws_bytes))."""
+    from ssl4polyp_amd import _lib
+    opts, info = _lib.GemmOpts(max_blocks, variant), _lib.GemmPlanInfo()
+    st = handle.pm_gemm_plan(a_kmajor, b_kmajor, in_dtype, has_bias, c_dtype, 1, epilogue, M, N, K, ws_bytes, ctypes.byref(opts),
+                             ctypes.byref(info))
+    return st, (info.family, info.cfg, info.tile_m, info.tile_n, info.split_k, info.band, info.ws_bytes)
+
+
+def test_gemm_dispatch_table(built):
+    """Which kernel every GEMM of the shipped workloads runs on (pm_gemm_plan), against tests/golden/gemm_plan.json: the table the
+    dispatcher gave when its rules were gathered into plan_gemm, before the unreachable variants were deleted.  Rows: the four
+    forward GEMMs, the four dgrads and the four split-K weight gradients (max_blocks = 128, unlimited scratch) of ViT-B/16
+    fine-tuning at bs = 64 (bf16 and f32), MAE ViT-B at bs = 256 and bs = 64 (encoder and 512-wide decoder), ViT-L/16 and ViT-H/14."""
+    import json
+    from ssl4polyp_amd import _lib
+    handle = _lib.load()
+    BF16, F32 = _lib.PM_BF16, _lib.PM_F32
+    rows = json.load(open(os.path.join(REPO, "tests", "golden", "gemm_plan.json")))
+    assert len(rows) == 136
+    by_name = {}
+    for r in rows:
+        ws = (1 << 62) if r["unlimited_ws"] else 0
+        st, plan = _gemm_plan(handle, r["a_kmajor"], r["b_kmajor"], r["in_dtype"], r["has_bias"], r["c_dtype"], r["epilogue"],
+                              r["M"], r["N"], r["K"], r["max_blocks"], 0, ws)
+        want = tuple(r["plan"][f] for f in ("family", "cfg", "tile_m", "tile_n", "split_k", "band", "ws_bytes"))
+        assert st == 0 and plan == want, (r["name"], st, plan, want)
+        by_name[r["name"]] = plan
+        if r["unlimited_ws"]:  # the workspace query is the same plan
+            opts = _lib.GemmOpts(r["max_blocks"], 0)
+            assert handle.pm_gemm_workspace_bytes(1, 1, r["in_dtype"], r["M"], r["N"], r["K"], ctypes.byref(opts)) == plan[6], r["name"]
+        else:
+            assert handle.pm_gemm_workspace_bytes(r["a_kmajor"], r["b_kmajor"], r["in_dtype"], r["M"], r["N"], r["K"], None) == plan[6] == 0
+    # rows derived by hand from the rules: (family, cfg, tile_m, tile_n), band where stated
+    RING, LDS128 = _lib.GEMM_RING, _lib.GEMM_LDS128
+    for name, want in {
+            "vitb_cls_bs64.qkv.M6304": (RING, 8, 256, 256, 1, 6), "vitb_cls_bs64.proj.M6304": (RING, 26, 192, 256),
+            "vitb_cls_bs64.fc2.M6304": (RING, 26, 192, 256), "vitb_cls_bs64.fc1_gelu.M6304": (RING, 8, 256, 256),
+            "vitb_cls_bs64.dfc2_dgelu.M12608": (RING, 8, 256, 256, 1, 6), "vitb_cls_bs64.dfc1.M12608": (RING, 24, 256, 256),
+            "vitb_cls_bs64.dproj.M12608": (RING, 24, 256, 256), "vitb_cls_bs64.dqkv.M12608": (RING, 24, 256, 256),
+            "mae_vitb_bs64_enc.qkv.M3200": (LDS128, 0, 128, 128), "mae_vitb_bs64_enc.fc1_gelu.M3200": (RING, 8, 256, 256),
+            "mae_vitb_bs64_dec.qkv.M12608": (RING, 10, 192, 256), "mae_vitb_bs64_dec.proj.M12608": (LDS128, 0, 128, 128),
+            "mae_vitb_bs256_dec.proj.M50432": (RING, 24, 256, 256), "mae_vitb_bs256_dec.fc2.M50432": (RING, 24, 256, 256)}.items():
+        assert by_name[name][:len(want)] == want, (name, by_name[name])
+    # the shapes of test_gemm_large_tile_paths (tests/test_gpu_ops.py): at M = 4000 the few-tiles rule sends N = 768 to the
+    # 128 x 128 kernel, N = 2304 stays on ring cfg 8
+    E = _lib
+    assert _gemm_plan(handle, 0, 0, BF16, 1, F32, E.EPI_RESIDUAL, 4000, 768, 3072)[1][:2] == (LDS128, 0)
+    assert _gemm_plan(handle, 0, 0, BF16, 1, BF16, E.EPI_STORE, 4000, 2304, 768)[1][:4] == (RING, 8, 256, 256)
+    assert _gemm_plan(handle, 0, 0, BF16, 1, BF16, E.EPI_GELU, 4000, 1536, 512)[1][:2] == (LDS128, 0)
+    assert _gemm_plan(handle, 0, 1, BF16, 0, BF16, E.EPI_STORE, 4000, 768, 2304)[1][:2] == (LDS128, 0)
+    assert _gemm_plan(handle, 0, 1, BF16, 0, BF16, E.EPI_DGELU, 4000, 3072, 768)[1][:2] == (RING, 8)
+    # ... and its k-major-A shapes cover both weight-gradient tiles
+    WG = _lib.GEMM_RING_WGRAD
+    assert _gemm_plan(handle, 1, 1, BF16, 0, F32, E.EPI_STORE, 520, 136, 4096, 128, 0, 1 << 62)[1][:4] == (WG, 0, 256, 128)
+    assert _gemm_plan(handle, 1, 1, BF16, 0, F32, E.EPI_STORE, 2304, 768, 4032, 128, 0, 1 << 62)[1][:4] == (WG, 0, 256, 256)
+    assert _gemm_plan(handle, 1, 1, BF16, 0, F32, E.EPI_ACCUM, 768, 3072, 8192, 128, 0, 1 << 62)[1][:4] == (WG, 0, 256, 256)
+    # the override names shipped kernels only: every (cfg, W layout) pair of the table is accepted and obeyed ...
+    shipped = {(8, 0), (8, 1), (9, 0), (10, 0), (24, 0), (24, 1), (25, 0), (26, 0)}
+    for cfg in range(2, 64):
+        for wk in (0, 1):
+            st, plan = _gemm_plan(handle, 0, wk, BF16, 0, BF16, E.EPI_STORE, 1031, 264, 64, 0, cfg)
+            if (cfg, wk) in shipped:
+                assert st == 0 and plan[:4] == (RING, cfg, 192 if cfg in (10, 26) else 256, 256), (cfg, wk, st, plan)
+            else:  # ... removed values (6, 12, 13, 40, ...) and unshipped pairs (cfg 9 with k-major W) are refused
+                assert st == _lib.PM_EINVAL, (cfg, wk, st)
+    assert _gemm_plan(handle, 0, 0, BF16, 0, BF16, E.EPI_STORE, 1031, 264, 64, 0, 1)[1][:2] == (LDS128, 0)
+    assert _gemm_plan(handle, 1, 1, BF16, 0, F32, E.EPI_STORE, 2304, 768, 4032, 128, 1 << 6, 1 << 62)[1][:4] == (WG, 0, 256, 128)
+    assert _gemm_plan(handle, 1, 1, BF16, 0, F32, E.EPI_STORE, 520, 136, 4096, 128, 2 << 6, 1 << 62)[1][:4] == (WG, 0, 256, 256)
+    assert _gemm_plan(handle, 1, 1, BF16, 0, F32, E.EPI_STORE, 2304, 768, 4032, 128, 3 << 6, 1 << 62)[0] == _lib.PM_EINVAL
+    assert _gemm_plan(handle, 0, 0, BF16, 0, BF16, E.EPI_STORE, 1031, 264, 64, 0, 256)[0] == _lib.PM_EINVAL
+    # refusals that need no pointer keep their status
+    assert _gemm_plan(handle, 0, 0, BF16, 0, BF16, E.EPI_STORE, 0, 264, 64)[0] == _lib.PM_ESHAPE
+    assert _gemm_plan(handle, 0, 0, BF16, 0, BF16, E.EPI_STORE, 128, 264, 36)[0] == _lib.PM_EALIGN
+    assert _gemm_plan(handle, 0, 0, BF16, 0, BF16, E.EPI_RESIDUAL, 128, 264, 64)[0] == _lib.PM_EINVAL  # f32 residual stream only
 
 
 def test_no_cpu_fallback():
