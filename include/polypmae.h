@@ -161,14 +161,6 @@ size_t pm_wgrad_group_workspace_bytes(const pm_wgrad_item* items, int n, int K, 
 int pm_wgrad_group_plan(const pm_wgrad_item* items, int n, int K, int in_dtype, size_t* ws_bytes, int* tiles256,
                         int* k_slices);
 
-/* pm_gemm followed by the column sums of the stored result: colsum[n] += sum_m C[m][n] (f32 [N]) -- the bias gradient of
- * the Linear whose output gradient C is (reference: autograd of nn.Linear).  Convenience composition (pm_gemm_ws +
- * pm_colsum_ws on the same stream; `workspace` is the column sum's).  The training engine does not use it: the bias
- * gradients of a block ride on pm_wgrad_group (dbias) and on pm_layernorm_bwd (dcolsum). */
-int pm_gemm_colsum(const void* A, long lda, int a_kmajor, const void* B, long ldb, int b_kmajor, int in_dtype,
-                   const float* bias, void* C, long ldc, int c_dtype, int epilogue, void* aux, const float* resid,
-                   float* colsum, int M, int N, int K, void* workspace, size_t ws_bytes, void* stream);
-
 /* Fused multi-head self-attention core -- replaces timm Attention.forward between qkv and proj:
  * softmax(q k^T * dh^-0.5) v, never materialising the [N,N] scores in HBM.
  * qkv: act [B, N, 3, H, dh] (the qkv Linear's output as stored); out: act [B, N, H*dh];
@@ -178,6 +170,22 @@ int pm_attention_fwd(const void* qkv, void* out, float* lse, int B, int N, int H
 /* Backward: dqkv [B,N,3,H,dh] from dout [B,N,H*dh]; delta: f32 workspace [B,H,N]. */
 int pm_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
                      int B, int N, int H, int dh, int dtype, void* stream);
+
+/* What pm_attention_fwd / pm_attention_bwd launch for a shape, WITHOUT launching: returns the status they would return
+ * (PM_OK, PM_ESHAPE, PM_EINVAL; pointers are not seen) and, when PM_OK, fills *info. */
+#define PM_ATTN_FWD_HEAD 0        /* forward, one workgroup per (batch, head) */
+#define PM_ATTN_FWD_PERSISTENT 1  /* forward, a workgroup walks several heads, the next one's K / V / Q in flight */
+#define PM_ATTN_BWD_SPLIT 2       /* backward, query-side and key-side kernels (two launches; delta is their hand-over) */
+#define PM_ATTN_BWD_FUSED 3       /* backward, dQ, dK and dV of a head from one set of LDS images */
+typedef struct pm_attention_plan_info {
+  int family;          /* PM_ATTN_* */
+  int nt;              /* 32-token tiles of the instantiated kernel = waves per workgroup */
+  int ct;              /* tiles an LDS image holds at a time (== nt: the head is staged once) */
+  int grid;            /* workgroups per launch */
+  int launches;
+  size_t lds_bytes[2]; /* dynamic LDS of each launch */
+} pm_attention_plan_info;
+int pm_attention_plan(int backward, int B, int N, int H, int dh, int dtype, pm_attention_plan_info* info);
 
 /* Column sums of a [M,N] act matrix into f32 [N] (+=) -- bias gradients of qkv / fc1 / decoder Linears. */
 int pm_colsum(const void* x, long ldx, int dtype, float* out, int M, int N, void* stream);
@@ -576,8 +584,8 @@ int pm_grad_stats(const float* g, long n, float* out, void* stream);
  * (two-stage, fixed-order) form of the op for the given shape, 0 when the op needs none.
  *   pm_gemm_workspace_bytes: the split-K slabs pm_gemm_ws / pm_gemm_ex would use for this GEMM under `opts`.
  *   pm_workspace_bytes(kind, M, N): PM_WS_LAYERNORM_BWD (M rows, N = D), PM_WS_COLSUM (M x N matrix),
- *   PM_WS_GEMM_COLSUM (pm_gemm_colsum of an M x N result), PM_WS_UNSHUFFLE_BWD (N = D). */
-enum pm_ws_kind { PM_WS_LAYERNORM_BWD = 1, PM_WS_COLSUM = 2, PM_WS_GEMM_COLSUM = 3, PM_WS_UNSHUFFLE_BWD = 4 };
+ *   PM_WS_UNSHUFFLE_BWD (N = D). */
+enum pm_ws_kind { PM_WS_LAYERNORM_BWD = 1, PM_WS_COLSUM = 2, PM_WS_UNSHUFFLE_BWD = 4 };
 size_t pm_gemm_workspace_bytes(int a_kmajor, int b_kmajor, int in_dtype, int M, int N, int K, const pm_gemm_opts* opts);
 size_t pm_workspace_bytes(int kind, int M, int N);
 

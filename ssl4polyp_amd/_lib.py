@@ -29,7 +29,7 @@ SIGNATURES = {
     "pm_wgrad_group": [P, I, I, I, I, P, ctypes.c_size_t, P],
     "pm_wgrad_group_plan": [P, I, I, I, P, P, P],
     "pm_gemm_plan": [I, I, I, I, I, I, I, I, I, I, ctypes.c_size_t, P, P],
-    "pm_gemm_colsum": [P, L, I, P, L, I, I, P, P, L, I, I, P, P, P, I, I, I, P, ctypes.c_size_t, P],
+    "pm_attention_plan": [I, I, I, I, I, I, P],
     "pm_attention_fwd": [P, P, P, I, I, I, I, I, P],
     "pm_attention_bwd": [P, P, P, P, P, P, I, I, I, I, I, P],
     "pm_colsum": [P, L, I, P, I, I, P],
@@ -86,10 +86,10 @@ SIGNATURES = {
     "pm_boot_metrics": [P, P, P, P, P, P, P, I, I, I, I, I, I, P, ctypes.c_size_t, P],
 }
 
-ABI_VERSION = 15  # pm_abi_version() of the library these signatures describe
+ABI_VERSION = 16  # pm_abi_version() of the library these signatures describe
 PM_GROUP_WHOLE_K = -1  # pm_wgrad_group(max_blocks=...): never slice, whole-K 256x256 tiles
 
-WS_LAYERNORM_BWD, WS_COLSUM, WS_GEMM_COLSUM, WS_UNSHUFFLE_BWD = 1, 2, 3, 4
+WS_LAYERNORM_BWD, WS_COLSUM, WS_UNSHUFFLE_BWD = 1, 2, 4
 
 
 class GemmPlanInfo(ctypes.Structure):
@@ -99,6 +99,15 @@ class GemmPlanInfo(ctypes.Structure):
 
 
 GEMM_GENERIC, GEMM_LDS128, GEMM_RING, GEMM_RING_WGRAD = 0, 1, 2, 3  # pm_gemm_plan_info.family
+
+
+class AttentionPlanInfo(ctypes.Structure):
+    """pm_attention_plan_info of include/polypmae.h."""
+    _fields_ = [("family", c_int), ("nt", c_int), ("ct", c_int), ("grid", c_int), ("launches", c_int),
+                ("lds_bytes", ctypes.c_size_t * 2)]
+
+
+ATTN_FWD_HEAD, ATTN_FWD_PERSISTENT, ATTN_BWD_SPLIT, ATTN_BWD_FUSED = 0, 1, 2, 3  # pm_attention_plan_info.family
 
 
 class GemmOpts(ctypes.Structure):

@@ -12,18 +12,21 @@
 // with no LDS round trip ("accumulator as operand"):
 //   fwd   : S^T[key][q] = K Q^T   (lane = q)  -> softmax over registers (+1 cross-half shuffle)
 //           O^T[d][q]  += V^T[d][key] P^T[key][q]          (V^T fragments by ds_read_b64_tr_b16)
-//   bwd   : bf16: ONE kernel per (batch, head) (attn_bwd_fused_kernel below): Q, K, V, dO staged once by LDS-DMA;
+//   bwd   : 16-bit, dh 32 / 64: ONE kernel per (batch, head) (attn_bwd_fused_kernel below): Q, K, V, dO staged once by LDS-DMA;
 //           pass 1 (wave = query tile, lane = q):  S^T, dP^T[key][q] = V dO^T -> dS^T -> dQ^T[d][q] += K^T[d][key] dS^T[key][q]
 //           pass 2 (wave = key tile, lane = key):  S[q][key] = Q K^T, dP[q][key] = dO V^T ->
 //                   dV^T[d][key] += dO^T[d][q] P[q][key] ;  dK^T[d][key] += Q^T[d][q] dS[q][key]
-//           f32 mode keeps the two-kernel form (attn_bwd_q_kernel / attn_bwd_kv_kernel: the same two passes, each staging
-//           half of the head and fetching the other half as per-lane global fragments).
+//           f32 mode, and the 80-wide heads of ViT-H in every type, keep the two-kernel form (attn_bwd_q_kernel /
+//           attn_bwd_kv_kernel: the same two passes, each staging half of the head and fetching the other half as per-lane
+//           global fragments).
 // Every output tile therefore has (q or key) on the lane and 4 consecutive d per register quad: stores
 // are 8-B (bf16) / 16-B (f32) vectors into the [B,N,(3,)H,dh] activations, the head transpose is free.
 // S and dP are recomputed in pass 2 (7 products instead of 5) to avoid any cross-wave reduction or atomics:
 // deterministic.  Roofline: HBM / MFMA; algorithmic FLOPs fwd 4*N^2*dh per head, bwd 10*N^2*dh.
+// Which kernel a shape runs on is ONE host function (plan_attention, at the end of the file; pm_attention_plan exposes it): only
+// the instantiations it can name are compiled, and nothing here reads the environment or has a build switch.
 #include "pm_common.h"
-#include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -44,9 +47,8 @@ template <int RB> __device__ __forceinline__ int swz(int row) {
 // not a power of two: the row is padded to a pitch the chunk swizzle covers (16-bit: 128 elements = 256 B, 16 slots; f32: 96
 // elements = 384 B, 24 slots); the products run over 5 k-steps of 16 (10 of 8 in f32) and 3 output tiles of 32 features, the
 // last one half padding (zeros in the image, never stored).
-template <typename T, int DH> constexpr int row_bytes() {
-  return DH == 80 ? (sizeof(T) == 2 ? 256 : 384) : DH * (int)sizeof(T);
-}
+constexpr int row_bytes_of(int esize, int dh) { return dh == 80 ? (esize == 2 ? 256 : 384) : dh * esize; }
+template <typename T, int DH> constexpr int row_bytes() { return row_bytes_of((int)sizeof(T), DH); }
 
 // Stage `rows_valid` rows of DH elements (global row stride `ld` elements) into an LDS image of `rows_total`
 // rows; rows beyond rows_valid are zero filled.
@@ -150,24 +152,6 @@ template <int DH> __device__ __forceinline__ constexpr int tile_cols(int dt) { r
 
 constexpr float kLog2e = 1.4426950408889634f;
 
-// Where Q / K / V rows of (batch b, head h) live inside the qkv buffer, in elements:
-//   base(which, b, h) = which * which_stride + b * batch_stride + h * head_stride, consecutive tokens `ld` apart.
-// token-major (timm's reshape of the qkv Linear's output, [B, N, 3, H, dh]): ld = 3 H dh, which = H dh, head = dh, batch = N ld.
-// head-major ([3, B, H, N, dh]: a head's rows contiguous, 25 KB at N = 197, dh = 64): ld = dh, which = B H N dh, head = N dh,
-// batch = H N dh -- what a qkv GEMM epilogue that scatters by head would write (experiment: PM_ATTN_HEADMAJOR=1 reads the
-// buffer that way; scratch/bench_attn_layout.py permutes the input accordingly).
-struct QkvLayout {
-  long ld, which_stride, head_stride, batch_stride;
-};
-inline QkvLayout qkv_layout(int B, int N, int H, int DH, bool head_major) {
-  if (head_major) return QkvLayout{(long)DH, (long)B * H * N * DH, (long)N * DH, (long)H * N * DH};
-  return QkvLayout{3L * H * DH, (long)H * DH, (long)DH, (long)N * 3L * H * DH};
-}
-inline bool attn_head_major() {
-  static const bool v = [] { const char* e = getenv("PM_ATTN_HEADMAJOR"); return e && e[0] == '1'; }();
-  return v;
-}
-
 // Which (batch, head) problem a workgroup of the one-problem-per-workgroup kernels takes.  dh = 32 (the MAE decoder: 16 heads of 32):
 // a head's rows are 64-B pieces of the [B, N, 3, H, dh] rows -- HALF a cache line, the other half belongs to the neighbouring head.
 // The hardware deals workgroup ids to the 8 XCDs round-robin, so with the identity map heads 2p and 2p + 1 run on different XCDs and
@@ -176,25 +160,21 @@ inline bool attn_head_major() {
 // same XCD, dispatched back to back, so the second finds the lines in that XCD's L2.  Needs an even H and B H % 16 == 0 (else identity).
 template <int DH> __device__ __forceinline__ int problem_of_block(int bid, int nprob, int H) {
   if constexpr (DH == 32) {
-#ifndef PM_ATTN_NO_PAIR_MAP
     if ((nprob & 15) == 0 && (H & 1) == 0) {
       const int xcd = bid & 7, j = bid >> 3;
       return (((j >> 1) << 3) + xcd) * 2 + (j & 1);
     }
-#endif
   }
   return bid;
 }
 
-// one wave per 32-row tile (7 waves for N = 197): every wave does identical work, nothing idles on a tail tile
-template <int NT> struct Waves { static constexpr int value = NT; };
-
+// One wave per 32-row tile (7 waves for N = 197): every wave does identical work, nothing idles on a tail tile.
 // Tiles of the OTHER side of the product an LDS image pair holds at a time.  Normally all NT of them (one staging, one barrier).
 // f32 rows of an 80-wide head at N = 257 (ViT-H/14 at 224^2) would need 2 x 288 x 384 B = 216 KiB: the images are then staged
 // in chunks of CT tiles, the per-wave state (running max / sum and O^T; dQ^T; dK^T and dV^T) living in registers across chunks.
-template <typename T, int DH, int NT> constexpr int chunk_tiles() {
-  constexpr int per_tile = 2 * 32 * row_bytes<T, DH>() + 2 * 32 * (int)sizeof(float);
-  if (NT * per_tile <= 150 * 1024) return NT;
+constexpr int chunk_tiles(int row_bytes, int nt) {
+  const int per_tile = 2 * 32 * row_bytes + 2 * 32 * (int)sizeof(float);
+  if (nt * per_tile <= 150 * 1024) return nt;
   return (80 * 1024) / per_tile;   // two workgroups per CU
 }
 
@@ -202,14 +182,12 @@ template <typename T, int DH, int NT> constexpr int chunk_tiles() {
 // forward
 // ------------------------------------------------------------------------------------------------
 template <typename T, int DH, int NT, int CT>
-__global__ __launch_bounds__(Waves<NT>::value * 64) void attn_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ out,
+__global__ __launch_bounds__(NT * 64) void attn_fwd_kernel(const T* __restrict__ qkv, T* __restrict__ out,
                                                                         float* __restrict__ lse, int N, int H,
                                                                         float scale) {
   constexpr int RB = row_bytes<T, DH>();
   constexpr int KS = DH * sizeof(T) / 32;   // 16-B fragment pairs along the head dim
   constexpr int DT = (DH + 31) / 32;        // 32-wide output tiles along the head dim
-  constexpr int NW = Waves<NT>::value;
-  static_assert(NW == NT, "one wave per query tile: its softmax state stays in registers across key chunks");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* imgK = smem;
   char* imgV = smem + CT * 32 * RB;
@@ -230,8 +208,8 @@ __global__ __launch_bounds__(Waves<NT>::value * 64) void attn_fwd_kernel(const T
   float m = -INFINITY, l = 0.f;
   for (int c0 = 0; c0 < NT; c0 += CT) {
     if (c0) __syncthreads();  // every wave is done with the previous chunk's images
-    load_image<T, DH>(imgK, base + H * DH + (long)c0 * 32 * ld, ld, N - c0 * 32, CT * 32, tid, NW * 64);
-    load_image<T, DH>(imgV, base + 2 * H * DH + (long)c0 * 32 * ld, ld, N - c0 * 32, CT * 32, tid, NW * 64);
+    load_image<T, DH>(imgK, base + H * DH + (long)c0 * 32 * ld, ld, N - c0 * 32, CT * 32, tid, NT * 64);
+    load_image<T, DH>(imgV, base + 2 * H * DH + (long)c0 * 32 * ld, ld, N - c0 * 32, CT * 32, tid, NT * 64);
     __syncthreads();
     if (c0 == 0) {
 #pragma unroll
@@ -289,7 +267,7 @@ __global__ __launch_bounds__(Waves<NT>::value * 64) void attn_fwd_kernel(const T
 // backward, query side: dQ (and delta = rowsum(dO * O), written for the key-side kernel)
 // ------------------------------------------------------------------------------------------------
 template <typename T, int DH, int NT, int CT>
-__global__ __launch_bounds__(Waves<NT>::value * 64) void attn_bwd_q_kernel(const T* __restrict__ qkv, const T* __restrict__ out,
+__global__ __launch_bounds__(NT * 64) void attn_bwd_q_kernel(const T* __restrict__ qkv, const T* __restrict__ out,
                                                                           const T* __restrict__ dout,
                                                                           const float* __restrict__ lse,
                                                                           float* __restrict__ delta, T* __restrict__ dqkv,
@@ -297,9 +275,7 @@ __global__ __launch_bounds__(Waves<NT>::value * 64) void attn_bwd_q_kernel(const
   constexpr int RB = row_bytes<T, DH>();
   constexpr int KS = DH * sizeof(T) / 32;
   constexpr int DT = (DH + 31) / 32;
-  constexpr int NW = Waves<NT>::value;
   constexpr int EPC = 16 / sizeof(T);
-  static_assert(NW == NT, "one wave per query tile");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* imgK = smem;
   char* imgV = smem + CT * 32 * RB;
@@ -319,8 +295,8 @@ __global__ __launch_bounds__(Waves<NT>::value * 64) void attn_bwd_q_kernel(const
   for (int dt = 0; dt < DT; ++dt) dq[dt] = zero16();
   for (int c0 = 0; c0 < NT; c0 += CT) {
     if (c0) __syncthreads();
-    load_image<T, DH>(imgK, base + H * DH + (long)c0 * 32 * ld, ld, N - c0 * 32, CT * 32, tid, NW * 64);
-    load_image<T, DH>(imgV, base + 2 * H * DH + (long)c0 * 32 * ld, ld, N - c0 * 32, CT * 32, tid, NW * 64);
+    load_image<T, DH>(imgK, base + H * DH + (long)c0 * 32 * ld, ld, N - c0 * 32, CT * 32, tid, NT * 64);
+    load_image<T, DH>(imgV, base + 2 * H * DH + (long)c0 * 32 * ld, ld, N - c0 * 32, CT * 32, tid, NT * 64);
     __syncthreads();
     if (c0 == 0) {
       const T* orow = out + ((long)b * N + q) * ldo + h * DH;
@@ -370,15 +346,13 @@ __global__ __launch_bounds__(Waves<NT>::value * 64) void attn_bwd_q_kernel(const
 // backward, key side: dK and dV
 // ------------------------------------------------------------------------------------------------
 template <typename T, int DH, int NT, int CT>
-__global__ __launch_bounds__(Waves<NT>::value * 64) void attn_bwd_kv_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
+__global__ __launch_bounds__(NT * 64) void attn_bwd_kv_kernel(const T* __restrict__ qkv, const T* __restrict__ dout,
                                                                            const float* __restrict__ lse,
                                                                            const float* __restrict__ delta,
                                                                            T* __restrict__ dqkv, int N, int H, float scale) {
   constexpr int RB = row_bytes<T, DH>();
   constexpr int KS = DH * sizeof(T) / 32;
   constexpr int DT = (DH + 31) / 32;
-  constexpr int NW = Waves<NT>::value;
-  static_assert(NW == NT, "one wave per key tile");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* imgQ = smem;
   char* imgDO = smem + CT * 32 * RB;
@@ -401,9 +375,9 @@ __global__ __launch_bounds__(Waves<NT>::value * 64) void attn_bwd_kv_kernel(cons
   }
   for (int c0 = 0; c0 < NT; c0 += CT) {
     if (c0) __syncthreads();
-    load_image<T, DH>(imgQ, base + (long)c0 * 32 * ld, ld, N - c0 * 32, CT * 32, tid, NW * 64);
-    load_image<T, DH>(imgDO, dout + ((long)b * N + c0 * 32) * ldo + h * DH, ldo, N - c0 * 32, CT * 32, tid, NW * 64);
-    for (int i = tid; i < CT * 32; i += NW * 64) {
+    load_image<T, DH>(imgQ, base + (long)c0 * 32 * ld, ld, N - c0 * 32, CT * 32, tid, NT * 64);
+    load_image<T, DH>(imgDO, dout + ((long)b * N + c0 * 32) * ldo + h * DH, ldo, N - c0 * 32, CT * 32, tid, NT * 64);
+    for (int i = tid; i < CT * 32; i += NT * 64) {
       const int qi = c0 * 32 + i;
       const long sidx = ((long)b * H + h) * N + qi;
       sl2[i] = qi < N ? lse[sidx] * kLog2e : 0.f;
@@ -458,7 +432,7 @@ __global__ __launch_bounds__(Waves<NT>::value * 64) void attn_bwd_kv_kernel(cons
 }
 
 // ------------------------------------------------------------------------------------------------
-// forward, persistent form (bf16, 193 <= N <= 224: the ViT-B/16 encoder at 224^2 and the MAE decoder)
+// forward, persistent form (16-bit, dh = 64, 193 <= N <= 224: the ViT-B/16 encoder at 224^2)
 // ------------------------------------------------------------------------------------------------
 // The one-block-per-head kernel above spends 43 % of its wave cycles parked behind the K/V load of its head (PMC,
 // DESIGN.md).  Here a workgroup walks several (batch, head) problems: K, V and Q of the NEXT head arrive by LDS-DMA
@@ -480,8 +454,7 @@ template <int RB, typename T> __device__ __forceinline__ void dma_rows(char* img
 
 template <typename T, int DH, int NT>
 __global__ __launch_bounds__(NT * 64) void attn_fwd2_kernel(const T* __restrict__ qkv, T* __restrict__ out,
-                                                           float* __restrict__ lse, int N, int H, int BH, float scale,
-                                                           QkvLayout lay) {
+                                                           float* __restrict__ lse, int N, int H, int BH, float scale) {
   constexpr int RB = DH * 2;
   constexpr int IMG = NT * 32 * RB;  // bytes per image
   constexpr int PCS = IMG / 1024;    // DMA pieces per image
@@ -491,18 +464,18 @@ __global__ __launch_bounds__(NT * 64) void attn_fwd2_kernel(const T* __restrict_
   char* imgQ = smem + 4 * IMG;
   const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const long ld = lay.ld;
+  const long hd = (long)H * DH, ld = 3 * hd;   // Q / K / V of a token are hd elements apart, tokens ld
   const float c = scale * kLog2e;
   auto issue = [&](int head, int buf) {
     const int b = head / H, h = head % H;
-    const T* base = qkv + (long)b * lay.batch_stride + (long)h * lay.head_stride;
+    const T* base = qkv + (long)b * N * ld + (long)h * DH;
     char* imgK = smem + buf * 2 * IMG;
 #pragma unroll
     for (int i = 0; i < (PCS + NT - 1) / NT; ++i) {
       const int p = wave + NT * i;
       if (p < PCS) {
-        dma_rows<RB>(imgK, base + lay.which_stride, ld, N, p, lane);
-        dma_rows<RB>(imgK + IMG, base + 2 * lay.which_stride, ld, N, p, lane);
+        dma_rows<RB>(imgK, base + hd, ld, N, p, lane);
+        dma_rows<RB>(imgK + IMG, base + 2 * hd, ld, N, p, lane);
         dma_rows<RB>(imgQ, base, ld, N, p, lane);
       }
     }
@@ -571,36 +544,8 @@ __global__ __launch_bounds__(NT * 64) void attn_fwd2_kernel(const T* __restrict_
   }
 }
 
-template <typename T, int DH>
-int launch_fwd2(const void* qkv, void* out, float* lse, int B, int N, int H, hipStream_t s) {
-  constexpr int NT = 7;
-  const int BH = B * H;
-  constexpr int SLOTS = DH == 32 ? 512 : 256;   // workgroups the chip holds at once (72 KiB of LDS at dh = 32: two per CU)
-  const int rounds = (BH + SLOTS - 1) / SLOTS;  // heads per workgroup ...
-  const int grid = (BH + rounds - 1) / rounds;  // ... spread evenly: no workgroup walks one head more than another
-  constexpr size_t lds = 5 * NT * 32 * DH * 2;
-  const float scale = 1.0f / sqrtf((float)DH);
-  auto kern = attn_fwd2_kernel<T, DH, NT>;
-  PM_ALLOW_LDS(kern, lds);
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(NT * 64), lds, s, (const T*)qkv, (T*)out, lse, N, H, BH, scale,
-                     qkv_layout(B, N, H, DH, attn_head_major()));
-  return pm_check_launch();
-}
-
-template <typename T, int DH, int NT>
-int launch_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, hipStream_t s) {
-  constexpr int NW = Waves<NT>::value;
-  constexpr int CT = chunk_tiles<T, DH, NT>();
-  const size_t lds = 2 * CT * 32 * row_bytes<T, DH>();
-  const float scale = 1.0f / sqrtf((float)DH);
-  auto kern = attn_fwd_kernel<T, DH, NT, CT>;
-  PM_ALLOW_LDS(kern, lds);
-  hipLaunchKernelGGL(kern, dim3(B * H), dim3(NW * 64), lds, s, (const T*)qkv, (T*)out, lse, N, H, scale);
-  return pm_check_launch();
-}
-
 // ------------------------------------------------------------------------------------------------
-// backward, fused (bf16): dQ, dK and dV of one (batch, head) from ONE set of LDS images
+// backward, fused (16-bit, dh = 32 / 64): dQ, dK and dV of one (batch, head) from ONE set of LDS images
 // ------------------------------------------------------------------------------------------------
 // The two kernels above each stage half of the head (K, V | Q, dO) and fetch the other half as per-lane fragments from
 // global memory, so every operand crosses HBM twice (231 MB per ViT-B launch against 155 MB algorithmic) and both spend
@@ -615,14 +560,7 @@ template <typename T, int DH, int NT>
 __global__ __launch_bounds__(NT * 64) void attn_bwd_fused_kernel(const T* __restrict__ qkv, const T* __restrict__ out,
                                                                 const T* __restrict__ dout,
                                                                 const float* __restrict__ lse, T* __restrict__ dqkv,
-                                                                int N, int H, float scale, QkvLayout lay
-#ifdef PM_ATTN_DEBUG
-                                                                , int dbg  // diagnostic build: bit 0 skips pass 1, bit 1 pass 2
-#endif
-                                                                ) {
-#ifndef PM_ATTN_DEBUG
-  constexpr int dbg = 0;
-#endif
+                                                                int N, int H, float scale) {
   constexpr int RB = DH * 2;
   constexpr int IMG = NT * 32 * RB;
   constexpr int PCS = IMG / 1024;
@@ -640,16 +578,16 @@ __global__ __launch_bounds__(NT * 64) void attn_bwd_fused_kernel(const T* __rest
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int prob = problem_of_block<DH>(blockIdx.x, gridDim.x, H);
   const int b = prob / H, h = prob % H;
-  const long ld = 3L * H * DH, ldo = (long)H * DH;   // (dqkv, out and dout stay token-major)
-  const T* base = qkv + (long)b * lay.batch_stride + (long)h * lay.head_stride;
+  const long ld = 3L * H * DH, ldo = (long)H * DH;
+  const T* base = qkv + (long)b * N * ld + h * DH;
   const T* dobase = dout + (long)b * N * ldo + h * DH;
 #pragma unroll
   for (int i = 0; i < (PCS + NT - 1) / NT; ++i) {
     const int p = wave + NT * i;
     if (p < PCS) {
-      dma_rows<RB>(imgQ, base, lay.ld, N, p, lane);
-      dma_rows<RB>(imgK, base + lay.which_stride, lay.ld, N, p, lane);
-      dma_rows<RB>(imgV, base + 2 * lay.which_stride, lay.ld, N, p, lane);
+      dma_rows<RB>(imgQ, base, ld, N, p, lane);
+      dma_rows<RB>(imgK, base + H * DH, ld, N, p, lane);
+      dma_rows<RB>(imgV, base + 2 * H * DH, ld, N, p, lane);
       dma_rows<RB>(imgDO, dobase, ldo, N, p, lane);
     }
   }
@@ -701,7 +639,7 @@ __global__ __launch_bounds__(NT * 64) void attn_bwd_fused_kernel(const T* __rest
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) dq[dt] = zero16();
 #pragma unroll kTileUnroll<DH>
-    for (int kt = 0; kt < ((dbg & 1) ? 0 : NT); ++kt) {
+    for (int kt = 0; kt < NT; ++kt) {
       f32x16 s = zero16(), dp = zero16();
 #pragma unroll
       for (int kk = 0; kk < KS; ++kk) {
@@ -735,7 +673,7 @@ __global__ __launch_bounds__(NT * 64) void attn_bwd_fused_kernel(const T* __rest
       dv[dt] = zero16();
     }
 #pragma unroll kTileUnroll<DH>
-    for (int qt = 0; qt < ((dbg & 2) ? 0 : NT); ++qt) {
+    for (int qt = 0; qt < NT; ++qt) {
       f32x16 s = zero16(), dp = zero16();
 #pragma unroll
       for (int kk = 0; kk < KS; ++kk) {
@@ -770,139 +708,140 @@ __global__ __launch_bounds__(NT * 64) void attn_bwd_fused_kernel(const T* __rest
   }
 }
 
-template <typename T, int DH, int NT>
-int launch_bwd_fused(const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int N, int H,
-                     hipStream_t s) {
-  const size_t lds = 4 * NT * 32 * DH * 2 + 2 * NT * 32 * sizeof(float);
-  const float scale = 1.0f / sqrtf((float)DH);
-  auto kern = attn_bwd_fused_kernel<T, DH, NT>;
-  PM_ALLOW_LDS(kern, lds);
-#ifdef PM_ATTN_DEBUG
-  static const int dbg = [] { const char* e = getenv("PM_ATTN_BWD_SKIP"); return e ? atoi(e) : 0; }();
-  hipLaunchKernelGGL(kern, dim3(B * H), dim3(NT * 64), lds, s, (const T*)qkv, (const T*)out, (const T*)dout, lse,
-                     (T*)dqkv, N, H, scale, qkv_layout(B, N, H, DH, attn_head_major()), dbg);
-#else
-  hipLaunchKernelGGL(kern, dim3(B * H), dim3(NT * 64), lds, s, (const T*)qkv, (const T*)out, (const T*)dout, lse,
-                     (T*)dqkv, N, H, scale, qkv_layout(B, N, H, DH, attn_head_major()));
-#endif
-  return pm_check_launch();
-}
-
-template <typename T, int DH>
-int dispatch_bwd_fused(int nt, const void* qkv, const void* out, const void* dout, const float* lse, void* dqkv, int B, int N,
-                       int H, hipStream_t s) {
-  if (nt <= 1) return launch_bwd_fused<T, DH, 1>(qkv, out, dout, lse, dqkv, B, N, H, s);
-  if (nt <= 2) return launch_bwd_fused<T, DH, 2>(qkv, out, dout, lse, dqkv, B, N, H, s);
-  if (nt <= 7) return launch_bwd_fused<T, DH, 7>(qkv, out, dout, lse, dqkv, B, N, H, s);
-  return launch_bwd_fused<T, DH, 9>(qkv, out, dout, lse, dqkv, B, N, H, s);   // N = 257: patch 14 at 224^2 (4 x 36 KiB images)
-}
-
-template <typename T, int DH, int NT>
-int launch_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv, int B,
-               int N, int H, hipStream_t s) {
-  constexpr int NW = Waves<NT>::value;
-  constexpr int CT = chunk_tiles<T, DH, NT>();
-  const size_t lds = 2 * CT * 32 * row_bytes<T, DH>();
-  const size_t lds_kv = lds + 2 * CT * 32 * sizeof(float);
-  const float scale = 1.0f / sqrtf((float)DH);
-  auto kq = attn_bwd_q_kernel<T, DH, NT, CT>;
-  auto kkv = attn_bwd_kv_kernel<T, DH, NT, CT>;
-  PM_ALLOW_LDS(kq, lds);
-  PM_ALLOW_LDS(kkv, lds_kv);
-  hipLaunchKernelGGL(kq, dim3(B * H), dim3(NW * 64), lds, s, (const T*)qkv, (const T*)out, (const T*)dout, lse, delta,
-                     (T*)dqkv, N, H, scale);
-  hipLaunchKernelGGL(kkv, dim3(B * H), dim3(NW * 64), lds_kv, s, (const T*)qkv, (const T*)dout, lse,
-                     (const float*)delta, (T*)dqkv, N, H, scale);
-  return pm_check_launch();
-}
-
-template <typename T, int DH>
-int dispatch_fwd(int nt, const void* qkv, void* out, float* lse, int B, int N, int H, hipStream_t s) {
-  if constexpr (DH == 80) {  // ViT-H: N = 65 under MAE masking, 257 unmasked
-    if (nt <= 3) return launch_fwd<T, DH, 3>(qkv, out, lse, B, N, H, s);
-    return launch_fwd<T, DH, 9>(qkv, out, lse, B, N, H, s);
-  } else {
-    if (nt <= 1) return launch_fwd<T, DH, 1>(qkv, out, lse, B, N, H, s);
-    if (nt <= 2) return launch_fwd<T, DH, 2>(qkv, out, lse, B, N, H, s);
-    if (nt <= 7) return launch_fwd<T, DH, 7>(qkv, out, lse, B, N, H, s);
-    return launch_fwd<T, DH, 9>(qkv, out, lse, B, N, H, s);
-  }
-}
-template <typename T, int DH>
-int dispatch_bwd(int nt, const void* qkv, const void* out, const void* dout, const float* lse, float* delta, void* dqkv,
-                 int B, int N, int H, hipStream_t s) {
-  if constexpr (DH == 80) {
-    if (nt <= 3) return launch_bwd<T, DH, 3>(qkv, out, dout, lse, delta, dqkv, B, N, H, s);
-    return launch_bwd<T, DH, 9>(qkv, out, dout, lse, delta, dqkv, B, N, H, s);
-  } else {
-    if (nt <= 1) return launch_bwd<T, DH, 1>(qkv, out, dout, lse, delta, dqkv, B, N, H, s);
-    if (nt <= 2) return launch_bwd<T, DH, 2>(qkv, out, dout, lse, delta, dqkv, B, N, H, s);
-    if (nt <= 7) return launch_bwd<T, DH, 7>(qkv, out, dout, lse, delta, dqkv, B, N, H, s);
-    return launch_bwd<T, DH, 9>(qkv, out, dout, lse, delta, dqkv, B, N, H, s);
-  }
-}
-
-// A/B switch for the tuning scripts (PM_ATTN_V1=1: the one-block-per-head kernels everywhere); read once.
-bool attn_v1() {
-  static const bool v = [] { const char* e = getenv("PM_ATTN_V1"); return e && e[0] == '1'; }();
-  return v;
-}
-bool attn_fwd2_dh32() {  // the persistent forward for the 32-wide MAE decoder heads too (measured slower: 80 vs 71 us)
-  static const bool v = [] { const char* e = getenv("PM_ATTN_FWD2_DH32"); return e && e[0] == '1'; }();
-  return v;
-}
-
-inline int check_shape(int B, int N, int H, int dh, int dtype) {
+// ------------------------------------------------------------------------------------------------
+// host: one plan, one launch per family
+// ------------------------------------------------------------------------------------------------
+// Everything a launch needs, from the shape alone (pm_attention_plan exposes it; tests/golden/attention_plan.json is its table).
+//   forward : 16-bit, dh = 64, seven tiles (N = 193..224: the ViT-B/16 encoder at 224^2) -> the persistent kernel (26 vs 28 us);
+//             everything else one workgroup per head -- the 32-wide MAE decoder heads are faster that way, two workgroups per CU
+//             (70 vs 77 us); both forms are bound by the strided qkv reads
+//   backward: 16-bit, dh = 32 / 64 -> the fused kernel; f32, and the 80-wide heads of ViT-H (four images of 288 x 256 B would not
+//             fit the LDS) -> the q and kv kernels, two launches
+// Instantiated tile counts: dh = 32 / 64: 1, 2, 7, 9 (N <= 32, 64, 224, 288); dh = 80: 3, 9 (N = 65 under MAE masking, 257 unmasked).
+int plan_attention(bool backward, int B, int N, int H, int dh, int dtype, pm_attention_plan_info* p) {
   if (B <= 0 || N <= 0 || H <= 0) return PM_ESHAPE;
   if (N > 288) return PM_ESHAPE;
   if (dh != 32 && dh != 64 && dh != 80) return PM_ESHAPE;
   if (dtype != PM_BF16 && dtype != PM_F16 && dtype != PM_F32) return PM_EINVAL;
+  const int tiles = (N + 31) / 32, BH = B * H;
+  const bool half = dtype != PM_F32;
+  const int rb = row_bytes_of(half ? 2 : 4, dh);
+  p->nt = dh == 80 ? (tiles <= 3 ? 3 : 9) : tiles <= 1 ? 1 : tiles <= 2 ? 2 : tiles <= 7 ? 7 : 9;
+  p->ct = p->nt;
+  p->grid = BH;
+  p->launches = 1;
+  p->lds_bytes[1] = 0;
+  if (!backward && half && dh == 64 && tiles == 7) {
+    p->family = PM_ATTN_FWD_PERSISTENT;
+    const int rounds = (BH + 255) / 256;            // heads per workgroup (the chip holds 256 workgroups at once) ...
+    p->grid = (BH + rounds - 1) / rounds;           // ... spread evenly: no workgroup walks one head more than another
+    p->lds_bytes[0] = 5 * 7 * 32 * dh * 2;          // [K0 | V0 | K1 | V1 | Q]
+  } else if (!backward) {
+    p->family = PM_ATTN_FWD_HEAD;
+    p->ct = chunk_tiles(rb, p->nt);
+    p->lds_bytes[0] = 2 * p->ct * 32 * rb;          // [K | V]
+  } else if (half && dh != 80) {
+    p->family = PM_ATTN_BWD_FUSED;
+    p->lds_bytes[0] = 4 * p->nt * 32 * rb + 2 * p->nt * 32 * sizeof(float);  // [Q | K | V | dO | lse | delta]
+  } else {
+    p->family = PM_ATTN_BWD_SPLIT;
+    p->launches = 2;
+    p->ct = chunk_tiles(rb, p->nt);
+    p->lds_bytes[0] = 2 * p->ct * 32 * rb;                                   // q kernel: [K | V]
+    p->lds_bytes[1] = p->lds_bytes[0] + 2 * p->ct * 32 * sizeof(float);      // kv kernel: [Q | dO | lse | delta]
+  }
   return PM_OK;
+}
+
+// the plan's runtime tile count -> the template parameter, over the tile counts instantiated for this head width
+template <int N> using Tiles = std::integral_constant<int, N>;
+template <int DH, typename F> int with_nt(int nt, F&& f) {
+  if constexpr (DH == 80) {
+    if (nt == 3) return f(Tiles<3>{});
+  } else {
+    if (nt == 1) return f(Tiles<1>{});
+    if (nt == 2) return f(Tiles<2>{});
+    if (nt == 7) return f(Tiles<7>{});
+  }
+  return nt == 9 ? f(Tiles<9>{}) : PM_ESHAPE;
+}
+
+template <typename T, int DH>
+int launch_fwd(const pm_attention_plan_info& p, const void* qkv, void* out, float* lse, int B, int N, int H, hipStream_t s) {
+  const float scale = 1.0f / sqrtf((float)DH);
+  if constexpr (sizeof(T) == 2 && DH == 64) {
+    if (p.family == PM_ATTN_FWD_PERSISTENT) {
+      auto kern = attn_fwd2_kernel<T, 64, 7>;
+      PM_ALLOW_LDS(kern, p.lds_bytes[0]);
+      hipLaunchKernelGGL(kern, dim3(p.grid), dim3(7 * 64), p.lds_bytes[0], s, (const T*)qkv, (T*)out, lse, N, H, B * H, scale);
+      return pm_check_launch();
+    }
+  }
+  return with_nt<DH>(p.nt, [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    auto kern = attn_fwd_kernel<T, DH, NT, chunk_tiles(row_bytes<T, DH>(), NT)>;
+    PM_ALLOW_LDS(kern, p.lds_bytes[0]);
+    hipLaunchKernelGGL(kern, dim3(p.grid), dim3(NT * 64), p.lds_bytes[0], s, (const T*)qkv, (T*)out, lse, N, H, scale);
+    return pm_check_launch();
+  });
+}
+
+template <typename T, int DH>
+int launch_bwd(const pm_attention_plan_info& p, const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
+               void* dqkv, int B, int N, int H, hipStream_t s) {
+  const float scale = 1.0f / sqrtf((float)DH);
+  return with_nt<DH>(p.nt, [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    if constexpr (sizeof(T) == 2 && DH != 80) {
+      auto kern = attn_bwd_fused_kernel<T, DH, NT>;
+      PM_ALLOW_LDS(kern, p.lds_bytes[0]);
+      hipLaunchKernelGGL(kern, dim3(p.grid), dim3(NT * 64), p.lds_bytes[0], s, (const T*)qkv, (const T*)out, (const T*)dout, lse,
+                         (T*)dqkv, N, H, scale);
+    } else {
+      constexpr int CT = chunk_tiles(row_bytes<T, DH>(), NT);
+      auto kq = attn_bwd_q_kernel<T, DH, NT, CT>;
+      auto kkv = attn_bwd_kv_kernel<T, DH, NT, CT>;
+      PM_ALLOW_LDS(kq, p.lds_bytes[0]);
+      PM_ALLOW_LDS(kkv, p.lds_bytes[1]);
+      hipLaunchKernelGGL(kq, dim3(p.grid), dim3(NT * 64), p.lds_bytes[0], s, (const T*)qkv, (const T*)out, (const T*)dout, lse,
+                         delta, (T*)dqkv, N, H, scale);
+      hipLaunchKernelGGL(kkv, dim3(p.grid), dim3(NT * 64), p.lds_bytes[1], s, (const T*)qkv, (const T*)dout, lse,
+                         (const float*)delta, (T*)dqkv, N, H, scale);
+    }
+    return pm_check_launch();
+  });
 }
 
 }  // namespace
 
+extern "C" int pm_attention_plan(int backward, int B, int N, int H, int dh, int dtype, pm_attention_plan_info* info) {
+  if (!info) return PM_EINVAL;
+  return plan_attention(backward != 0, B, N, H, dh, dtype, info);
+}
+
 extern "C" int pm_attention_fwd(const void* qkv, void* out, float* lse, int B, int N, int H, int dh, int dtype,
                                 void* stream) {
   if (!qkv || !out || !lse) return PM_EINVAL;
-  const int st = check_shape(B, N, H, dh, dtype);
+  pm_attention_plan_info p;
+  const int st = plan_attention(false, B, N, H, dh, dtype, &p);
   if (st) return st;
-  const int nt = (N + 31) / 32;
   hipStream_t s = pm_stream(stream);
-  if (dtype != PM_F32) {
-    // persistent double-buffered form for the ViT-B encoder heads (dh = 64, N = 197: 26 vs 28 us); the 32-wide MAE decoder
-    // heads are faster one block per head, two blocks per CU (70 vs 77 us) -- both are bound by the strided qkv reads
-    PM_DISPATCH_16(dtype, T, {
-      if (nt == 7 && dh == 64 && !attn_v1()) return launch_fwd2<T, 64>(qkv, out, lse, B, N, H, s);
-      if (nt == 7 && dh == 32 && attn_fwd2_dh32()) return launch_fwd2<T, 32>(qkv, out, lse, B, N, H, s);
-      if (dh == 80) return dispatch_fwd<T, 80>(nt, qkv, out, lse, B, N, H, s);
-      return dh == 64 ? dispatch_fwd<T, 64>(nt, qkv, out, lse, B, N, H, s) : dispatch_fwd<T, 32>(nt, qkv, out, lse, B, N, H, s);
-    });
-  }
-  if (dh == 80) return dispatch_fwd<float, 80>(nt, qkv, out, lse, B, N, H, s);
-  return dh == 64 ? dispatch_fwd<float, 64>(nt, qkv, out, lse, B, N, H, s)
-                  : dispatch_fwd<float, 32>(nt, qkv, out, lse, B, N, H, s);
+  PM_DISPATCH_ACT(dtype, T, {
+    if (dh == 80) return launch_fwd<T, 80>(p, qkv, out, lse, B, N, H, s);
+    return dh == 64 ? launch_fwd<T, 64>(p, qkv, out, lse, B, N, H, s) : launch_fwd<T, 32>(p, qkv, out, lse, B, N, H, s);
+  });
 }
 
 extern "C" int pm_attention_bwd(const void* qkv, const void* out, const void* dout, const float* lse, float* delta,
                                 void* dqkv, int B, int N, int H, int dh, int dtype, void* stream) {
   if (!qkv || !out || !dout || !lse || !delta || !dqkv) return PM_EINVAL;
-  const int st = check_shape(B, N, H, dh, dtype);
+  pm_attention_plan_info p;
+  const int st = plan_attention(true, B, N, H, dh, dtype, &p);
   if (st) return st;
-  const int nt = (N + 31) / 32;
   hipStream_t s = pm_stream(stream);
-  if (dtype != PM_F32) {
-    PM_DISPATCH_16(dtype, T, {
-      // 80-wide heads (ViT-H): the two-kernel form (the fused kernel's four images of 288 x 256 B would not fit the LDS)
-      if (dh == 80) return dispatch_bwd<T, 80>(nt, qkv, out, dout, lse, delta, dqkv, B, N, H, s);
-      if (!attn_v1())
-        return dh == 64 ? dispatch_bwd_fused<T, 64>(nt, qkv, out, dout, lse, dqkv, B, N, H, s)
-                        : dispatch_bwd_fused<T, 32>(nt, qkv, out, dout, lse, dqkv, B, N, H, s);
-      return dh == 64 ? dispatch_bwd<T, 64>(nt, qkv, out, dout, lse, delta, dqkv, B, N, H, s)
-                      : dispatch_bwd<T, 32>(nt, qkv, out, dout, lse, delta, dqkv, B, N, H, s);
-    });
-  }
-  if (dh == 80) return dispatch_bwd<float, 80>(nt, qkv, out, dout, lse, delta, dqkv, B, N, H, s);
-  return dh == 64 ? dispatch_bwd<float, 64>(nt, qkv, out, dout, lse, delta, dqkv, B, N, H, s)
-                  : dispatch_bwd<float, 32>(nt, qkv, out, dout, lse, delta, dqkv, B, N, H, s);
+  PM_DISPATCH_ACT(dtype, T, {
+    if (dh == 80) return launch_bwd<T, 80>(p, qkv, out, dout, lse, delta, dqkv, B, N, H, s);
+    return dh == 64 ? launch_bwd<T, 64>(p, qkv, out, dout, lse, delta, dqkv, B, N, H, s)
+                    : launch_bwd<T, 32>(p, qkv, out, dout, lse, delta, dqkv, B, N, H, s);
+  });
 }

@@ -1555,17 +1555,6 @@ extern "C" int pm_gemm_ws(const void* A, long lda, int a_kmajor, const void* B, 
                        workspace, ws_bytes, nullptr, stream);
 }
 
-extern "C" int pm_gemm_colsum(const void* A, long lda, int a_kmajor, const void* B, long ldb, int b_kmajor, int in_dtype,
-                              const float* bias, void* C, long ldc, int c_dtype, int epilogue, void* aux,
-                              const float* resid, float* colsum, int M, int N, int K, void* workspace, size_t ws_bytes,
-                              void* stream) {
-  if (!colsum) return PM_EINVAL;
-  const int st = gemm_dispatch(A, lda, a_kmajor, B, ldb, b_kmajor, in_dtype, bias, C, ldc, c_dtype, epilogue, aux, resid, M, N, K,
-                               nullptr, 0, nullptr, stream);
-  if (st) return st;
-  return pm_colsum_ws(C, ldc, c_dtype, colsum, M, N, workspace, ws_bytes, stream);
-}
-
 extern "C" int pm_gemm(const void* A, long lda, int a_kmajor, const void* B, long ldb, int b_kmajor, int in_dtype,
                        const float* bias, void* C, long ldc, int c_dtype, int epilogue, void* aux, const float* resid,
                        int M, int N, int K, void* stream) {

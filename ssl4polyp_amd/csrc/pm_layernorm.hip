@@ -5,7 +5,6 @@
 // per lane is a template parameter), f32 statistics, two-pass variance.
 // Algorithmic bytes per row: fwd 4D (x) + sizeof(act)*D (y); bwd sizeof(act)*D (dy) + 4D (x) + 4D (dres)
 // + 4D (dx) + sizeof(act)*D (dx_act).
-#include <stdlib.h>
 #include "pm_common.h"
 
 namespace {
@@ -227,17 +226,9 @@ __global__ __launch_bounds__(1024) void ln_bwd_reduce_kernel(const float* __rest
   }
 }
 
-// A/B switch, read once: PM_LN_BWD_BLOCKS = most workgroups of one ln_bwd_kernel launch (64 .. 1024, default kLnBwdBlocks); the
-// workspace the caller passes bounds it further.  Another bound is another (still deterministic) association of the column sums.
+// Most workgroups of one ln_bwd_kernel launch; the workspace the caller passes bounds it further.  Another bound is another (still
+// deterministic) association of the column sums.
 constexpr int kLnBwdBlocks = 1024;
-int ln_bwd_max_blocks() {
-  static const int v = [] {
-    const char* e = getenv("PM_LN_BWD_BLOCKS");
-    const int n = e && e[0] ? atoi(e) : kLnBwdBlocks;
-    return n < 64 ? 64 : (n > 1024 ? 1024 : n);
-  }();
-  return v;
-}
 }  // namespace
 
 extern "C" int pm_layernorm_fwd(const float* x, long ldx, const float* gamma, const float* beta, void* y, int out_dtype,
@@ -266,11 +257,11 @@ extern "C" int pm_layernorm_bwd(const void* dy, int dy_dtype, const float* x, lo
   const bool want_sums = dgamma || dbeta || dcolsum;
   if (want_sums && workspace && ws_bytes >= (size_t)64 * 3 * D * sizeof(float)) {
     const size_t fit = ws_bytes / ((size_t)3 * D * sizeof(float));
-    cap = ln_bwd_max_blocks();
+    cap = kLnBwdBlocks;
     if ((size_t)cap > fit) cap = (int)fit;
     partials = reinterpret_cast<float*>(workspace);
   } else if (!want_sums) {
-    cap = ln_bwd_max_blocks();
+    cap = kLnBwdBlocks;
   }
   // the parent kernel's grid and row assignment (wave gw of 4 * grid takes rows gw, gw + 4 * grid, ...): with the fixed order inside
   // a wave, a workgroup and ln_bwd_reduce_kernel, the column sums come out bit for bit as before the rows went in flight

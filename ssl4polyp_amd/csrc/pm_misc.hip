@@ -622,7 +622,8 @@ extern "C" const char* pm_strerror(int status) {
 // 3: pm_gemm_ex / pm_gemm_opts replace pm_tune, workspace queries, pm_vit_head_*, pm_supervised_loss_fwd, pm_scale
 // 10: PM_F16 (precision mode fp16), pm_loss_scale_update, pm_dgelu
 // 15: pm_gemm_plan; pm_gemm_opts.variant names shipped kernels only (anything else: PM_EINVAL)
-extern "C" int pm_abi_version(void) { return 15; }
+// 16: pm_attention_plan; pm_gemm_colsum and PM_WS_GEMM_COLSUM are gone (pm_gemm_ws, then pm_colsum_ws)
+extern "C" int pm_abi_version(void) { return 16; }
 
 extern "C" size_t pm_workspace_bytes(int kind, int M, int N) {
   if (M <= 0 || N <= 0) return 0;
@@ -634,11 +635,6 @@ extern "C" size_t pm_workspace_bytes(int kind, int M, int N) {
       return (size_t)g * 3 * N * sizeof(float);
     }
     case PM_WS_COLSUM: return (size_t)cap_grid(M, 64, 128) * N * sizeof(float);
-    case PM_WS_GEMM_COLSUM: {  // per (row tile of 192, wave row) partial rows of the fused epilogue, or the plain column sum
-      const size_t fused = (size_t)((M + 191) / 192) * 2 * N * sizeof(float);
-      const size_t plain = (size_t)cap_grid(M, 64, 128) * N * sizeof(float);
-      return fused > plain ? fused : plain;
-    }
     case PM_WS_UNSHUFFLE_BWD: return (size_t)1024 * N * sizeof(float);  // partial rows of the mask-token gradient
     default: return 0;
   }

@@ -17,7 +17,6 @@ from __future__ import annotations
 import concurrent.futures
 import ctypes
 import math
-import os
 from typing import Iterable, Iterator, Optional, Sequence, Tuple
 
 import numpy as np
@@ -948,7 +947,7 @@ class DevicePrefetcher:
         if self.device.type != "cuda":
             raise _lib.PolypMaeError("DevicePrefetcher needs a GPU (the transform tail is a HIP kernel)")
         if self._stream is None:
-            mode = {"0": "own", "1": "side"}.get(os.environ.get("PM_PREFETCH_ON_SIDE", ""), self.stream_mode)  # (A/B switch)
+            mode = self.stream_mode
             if mode == "auto":
                 import torch.distributed as dist
                 mode = "side" if dist.is_available() and dist.is_initialized() else "own"

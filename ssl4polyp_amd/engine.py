@@ -53,13 +53,12 @@ def _stream() -> int:
 
 _STREAMS: Dict[Tuple[int, str], "torch.cuda.Stream"] = {}
 # The second weight-gradient stream (busy in the backward only) IS the second forward chain's stream (busy in the forward only):
-# three engine streams + the main stream = four busy streams at most, one per hardware queue of the runtime's default, and one queue
-# left for RCCL in a data-parallel rank (scratch/archive_r3/r3_exp23.sh; PM_MERGE_AUX_SIDE2=0 gives the weight gradients a stream of their own)
-MERGE_AUX_SIDE2 = os.environ.get("PM_MERGE_AUX_SIDE2", "1") == "1"
+# two engine streams + the main stream = three busy streams, each on a hardware queue of its own under the runtime's default of four,
+# and one queue left for RCCL in a data-parallel rank (scratch/archive_r3/r3_exp23.sh)
 
 
 def _shared_stream(device, role: str):
-    """The process-wide side stream of this role ("aux0", "side", "side2", ...) on `device`, created on first use."""
+    """The process-wide side stream of this role ("aux0", "side", ...) on `device`, created on first use."""
     dev = torch.device(device)
     key = (dev.index if dev.index is not None else torch.cuda.current_device(), role)
     st = _STREAMS.get(key)
@@ -77,7 +76,7 @@ def reserve_streams(device) -> None:
     (measured with RCCL initialised first: the second forward chain behind the main stream, cls step 15.0 instead of 10.6 ms)."""
     dev = torch.device(device)
     torch.zeros(1, device=dev)  # (the main stream first)
-    for role in ("aux0", "side") + (() if MERGE_AUX_SIDE2 else ("side2",)):
+    for role in ("aux0", "side"):
         with torch.cuda.stream(_shared_stream(dev, role)):
             torch.zeros(1, device=dev)
     torch.cuda.synchronize(dev)
@@ -93,6 +92,23 @@ PRECISIONS = {"bf16": (torch.bfloat16, PM_BF16), "fp16": (torch.float16, PM_F16)
 
 class Kernels:
     """Thin typed wrappers: torch tensors in, C-ABI calls out (include/polypmae.h)."""
+
+    # The switches: what the tests and bench.py flip per object, and a whole-process A/B run by the environment variable.
+    SPLIT_FORWARD = int(os.environ.get("PM_SPLIT_FWD", "2"))     # The forward runs as this many sub-batches on concurrent streams (1 = off).
+    # Workgroups a split-K weight gradient takes beside the dgrad chain on the main stream (pm_gemm_opts.max_blocks; 128 best of 96..256).
+    WGRAD_BLOCKS = int(os.environ.get("PM_WGRAD_BLOCKS", "128"))
+    # A whole-K block's weight gradients go out as (fc2, fc1) behind dfc2 and (proj, qkv) behind the attention backward, on two side streams.
+    TWO_GROUPS = os.environ.get("PM_TWO_GROUPS", "1") == "1"
+    TIME_BLOCK_EVENTS = False                                    # The fork / done events of pm_vit_block_bwd carry timestamps (bench.py times its weight gradients by them).
+    gemm_variant = int(os.environ.get("PM_GEMM_VARIANT", "0"))   # pm_gemm_opts.variant of every GEMM: 0 = the dispatcher's heuristics.
+    BLOCK_CALLS = os.environ.get("PM_BLOCK_CALLS", "1") != "0"   # A block is ONE C call (pm_vit_block_fwd / pm_vit_block_bwd) instead of a call per kernel.
+    GROUP_BLOCKS = int(os.environ.get("PM_GROUP_BLOCKS", "0"))   # CUs a grouped weight-gradient launch may take (0 = one workgroup per tile).
+    GROUP_BLOCKS_SLICED = int(os.environ.get("PM_GROUP_BLOCKS_SLICED", "0"))  # The same for a k-sliced group (0 = one workgroup per tile and slice).
+    # A block's weight gradients are one grouped launch from this many 256x256 tiles on, and below it when the library k-slices them (0 = always).
+    GROUP_MIN_TILES = int(os.environ.get("PM_GROUP_MIN_TILES", "64"))
+    # The lowest trainable blocks of a stack that ends the pass, this many, issue their four weight gradients one by one (no dgrad chain runs beside them).
+    UNGROUP_TAIL = int(os.environ.get("PM_UNGROUP_TAIL", "1"))
+    SPARSE_TOP = os.environ.get("PM_SPARSE_TOP", "1") != "0"     # The classifier's top block runs on its cls rows behind the attention (backward too).
 
     def __init__(self, precision: str, eps: float = LN_EPS):
         self.eps = float(eps)
@@ -114,25 +130,6 @@ class Kernels:
                                              _ptr(rstd), _ptr(dres), D, _ptr(dx), D, _ptr(dx_act), self.act,
                                              _ptr(dgamma), _ptr(dbeta), _ptr(dcolsum), M, D, _ptr(ws), ws.numel(), _stream()),
                    "pm_layernorm_bwd")
-
-    SPLIT_FORWARD = int(os.environ.get("PM_SPLIT_FWD", "2"))  # forward: this many sub-batches as concurrent chains (1 = off)
-    # workgroups a split-K weight gradient spreads over (pm_gemm_opts.max_blocks): the weight gradients run beside the
-    # dgrad chain on a side stream, so each takes ~half of the CUs and leaves the rest to LayerNorm / attention backward /
-    # dgrad GEMMs (measured: 128 best of 96..256)
-    WGRAD_BLOCKS = int(os.environ.get("PM_WGRAD_BLOCKS", "128"))
-    # fc1.bias gradient inside the dGELU dgrad epilogue (pm_gemm_colsum) instead of a column-sum kernel on the side
-    # stream.  Off: the HBM-bound column sum overlaps the MFMA-bound GEMMs for free, while the fused reduction
-    # lengthens the dgrad chain (measured -2.5 % step rate when fused).
-    FUSE_COLSUM = os.environ.get("PM_FUSE_COLSUM", "0") == "1"
-    # pm_vit_block_bwd.two_groups: a whole-K block's weight gradients as (fc2, fc1) behind dfc2 and (proj, qkv) behind the
-    # attention backward, on two side streams: each launch starts as soon as its operands exist, and the 72 + 36 workgroups
-    # of a ViT-B block spread over the whole dgrad chain instead of 108 behind the attention backward (measured, 5 pairs of
-    # runs: MAE +0.5 %, cls +0.1 %; gradients bit-identical to the single launch)
-    TWO_GROUPS = os.environ.get("PM_TWO_GROUPS", "1") == "1"
-    # bench.py's kernel statistics: the fork / done events of pm_vit_block_bwd carry timestamps, so that the weight-gradient launches
-    # of the one-call-per-block path can be timed in place (fork -> done on an idle side stream = the launch)
-    TIME_BLOCK_EVENTS = False
-    gemm_variant = int(os.environ.get("PM_GEMM_VARIANT", "0"))  # pm_gemm_opts.variant: 0 = the dispatcher's heuristics (tuning scripts set it per Kernels object)
 
     # -- scratch buffers: sized by the library's own queries (pm_gemm_workspace_bytes / pm_workspace_bytes), cached per
     #    shape; a buffer only ever grows, and growing it (first step of a new shape) drains the device first because the
@@ -167,9 +164,10 @@ class Kernels:
         return st
 
     def side_stream2(self, device):
+        """The second weight-gradient stream (busy in the backward only) IS the second forward chain's (busy in the forward only)."""
         st = getattr(self, "_side2", None)
         if st is None or st.device != device:
-            st = self._side2 = _shared_stream(device, "aux0" if MERGE_AUX_SIDE2 else "side2")
+            st = self._side2 = _shared_stream(device, "aux0")
         return st
 
     def _opts(self, wgrad: bool):
@@ -179,17 +177,10 @@ class Kernels:
             o = self._opts_cache = (key, _lib.GemmOpts(self.WGRAD_BLOCKS, self.gemm_variant), _lib.GemmOpts(0, self.gemm_variant))
         return o[1] if wgrad else o[2]
 
-    def gemm(self, A, lda, a_kmajor, B, ldb, b_kmajor, bias, C, ldc, epilogue, M, N, K, aux=None, resid=None, colsum=None,
-             ws_name="_ws"):
+    def gemm(self, A, lda, a_kmajor, B, ldb, b_kmajor, bias, C, ldc, epilogue, M, N, K, aux=None, resid=None, ws_name="_ws"):
         in_dtype = _lib.dtype_code(A.dtype)
         if _lib.dtype_code(B.dtype) != in_dtype:
             raise _lib.PolypMaeError("pm_gemm: operand dtypes differ")
-        if colsum is not None:  # colsum[n] += sum_m C[m][n], fused into the epilogue where the kernel supports it
-            ws = self._colsum_workspace(A.device, M, N, True)
-            _lib.check(self.lib.pm_gemm_colsum(_ptr(A), lda, int(a_kmajor), _ptr(B), ldb, int(b_kmajor), in_dtype, _ptr(bias),
-                                               _ptr(C), ldc, _lib.dtype_code(C.dtype), epilogue, _ptr(aux), _ptr(resid),
-                                               _ptr(colsum), M, N, K, _ptr(ws), ws.numel(), _stream()), "pm_gemm_colsum")
-            return
         wgrad = bool(a_kmajor and b_kmajor)
         opts = self._opts(wgrad)
         ws = None
@@ -205,23 +196,9 @@ class Kernels:
         """out[M,N] = x[M,K] @ W[N,K]^T + bias  (nn.Linear forward)."""
         self.gemm(x, K, 0, W, K, 0, bias, out, N, epilogue, M, N, K, aux=aux, resid=resid)
 
-    def linear_dgrad(self, dy, W, dx, M, N_out, K_in, epilogue=EPI_STORE, aux=None, colsum=None):
-        """dx[M,K_in] = dy[M,N_out] @ W[N_out,K_in]  (W read as stored: k-major B operand); colsum += column sums of dx."""
-        self.gemm(dy, N_out, 0, W, K_in, 1, None, dx, K_in, epilogue, M, K_in, N_out, aux=aux, colsum=colsum)
-
-    DEFER_JOIN = os.environ.get("PM_DEFER_JOIN", "1") != "0"    # A/B switch: the embedding's backward before the side-stream join
-    BLOCK_CALLS = os.environ.get("PM_BLOCK_CALLS", "1") != "0"  # block forward as ONE C call (pm_vit_block_fwd) instead of seven
-    GROUP_WGRAD = os.environ.get("PM_GROUP_WGRAD", "1") != "0"  # A/B switch: one grouped weight-gradient launch per block
-    GROUP_BLOCKS = int(os.environ.get("PM_GROUP_BLOCKS", "0"))  # CUs the grouped launch may take (0 = one workgroup per tile)
-    # the same for a k-sliced group (MAE decoder block: 48 tiles x 4 slices = 192 work items; 0 = one workgroup per item)
-    GROUP_BLOCKS_SLICED = int(os.environ.get("PM_GROUP_BLOCKS_SLICED", "0"))
-    GROUP_MIN_TILES = int(os.environ.get("PM_GROUP_MIN_TILES", "64"))
-    GROUP_BIAS = os.environ.get("PM_GROUP_BIAS", "1") != "0"    # qkv / fc1 bias gradients inside that launch (no pm_colsum pass)
-    GROUP_SPLIT = os.environ.get("PM_GROUP_SPLIT", "1") != "0"  # A/B switch: groups of < 64 tiles as k-sliced grouped launches
-    # The last blocks of a backward pass (lowest trainable ones) have no dgrad chain below them to run beside: a grouped
-    # launch there holds 108 CUs for ~0.4 ms while the rest idle, so those blocks issue their four gradients one by one
-    # (whole-chip split-K launches, each as soon as its dY exists).
-    UNGROUP_TAIL = int(os.environ.get("PM_UNGROUP_TAIL", "1"))
+    def linear_dgrad(self, dy, W, dx, M, N_out, K_in, epilogue=EPI_STORE, aux=None):
+        """dx[M,K_in] = dy[M,N_out] @ W[N_out,K_in]  (W read as stored: k-major B operand)."""
+        self.gemm(dy, N_out, 0, W, K_in, 1, None, dx, K_in, epilogue, M, K_in, N_out, aux=aux)
 
     def wgrad_group(self, items, K, whole_k: bool = False) -> bool:
         """items: [(dy [K, n_out], x [K, n_in], dW f32 [n_out, n_in], accumulate[, dbias f32 [n_out] (+=)])].  One launch for all
@@ -249,9 +226,7 @@ class Kernels:
         """Would pm_wgrad_group take these (n_out, n_in) gradients over K tokens, and does the engine want it to?  The
         admission rules are the LIBRARY's (pm_wgrad_group_plan: bf16, whole 32-token k-steps, K >= 2048, tiles of at least
         256 x 128, 16-byte alignment) -- asked, not restated here; the policy on top is the engine's."""
-        if not self.GROUP_WGRAD:
-            return False
-        key = ("can_group", K, self.act, tuple(dims), self.GROUP_MIN_TILES, self.GROUP_SPLIT)
+        key = ("can_group", K, self.act, tuple(dims), self.GROUP_MIN_TILES)
         cache = self.__dict__.setdefault("_need_cache", {})
         hit = cache.get(key)
         if hit is not None:
@@ -265,7 +240,7 @@ class Kernels:
         # >= 64 tiles of 256x256 (ViT-B block: 108): one full-K tile per workgroup.  Fewer (the 512-wide MAE decoder block:
         # 48) group as well when the library's plan cuts every tile into k-slices (48 tiles x 4 slices of >= 128 k-steps);
         # otherwise the gradients keep the per-GEMM split-K path (PM_GROUP_MIN_TILES=0 forces grouping: whole-K 256x128 tiles).
-        ok = st == 0 and (tiles.value >= self.GROUP_MIN_TILES or (self.GROUP_SPLIT and slices.value > 1))
+        ok = st == 0 and (tiles.value >= self.GROUP_MIN_TILES or slices.value > 1)
         cache[key] = ok
         return ok
 
@@ -296,11 +271,10 @@ class Kernels:
         its own."""
         self.gemm(dy, N_out, 1, x, K_in, 1, None, dW, K_in, EPI_ACCUM if accumulate else EPI_STORE, N_out, K_in, M, ws_name=ws_name)
 
-    def _colsum_workspace(self, device, M: int, N: int, fused: bool = False):
+    def _colsum_workspace(self, device, M: int, N: int):
         # partial rows: one scratch per stream (main / wgrad side stream) so concurrent column sums never share it
         on_side = getattr(self, "_side", None) is not None and torch.cuda.current_stream() == self._side
-        kind = _lib.WS_GEMM_COLSUM if fused else _lib.WS_COLSUM
-        need = self._need(("cs", kind, M, N), lambda: self.lib.pm_workspace_bytes(kind, M, N))
+        need = self._need(("cs", M, N), lambda: self.lib.pm_workspace_bytes(_lib.WS_COLSUM, M, N))
         return self._scratch("_ws_cs_side" if on_side else "_ws_cs_main", need, device)
 
     def colsum(self, x, out, M, N):
@@ -328,8 +302,6 @@ class Kernels:
         """dst[m] = src[inv[m]] where inv[m] >= 0, zeros elsewhere (every row of dst is written)."""
         _lib.check(self.lib.pm_scatter_rows_zero(_ptr(src), _ptr(inv), _ptr(dst), dst.shape[0], dst.shape[1] * dst.element_size(),
                                                  _stream()), "pm_scatter_rows_zero")
-
-    SPARSE_TOP = os.environ.get("PM_SPARSE_TOP", "1") != "0"   # A/B switch: the classifier's top block on its cls rows (backward)
 
     def cast(self, src, dst):
         _lib.check(self.lib.pm_cast(_ptr(src), _ptr(dst), _lib.dtype_code(dst.dtype), src.numel(), _stream()), "pm_cast")
@@ -639,8 +611,8 @@ class BlockStack:
                     main.wait_event(ev)
 
         # PM_BLOCK_CALLS: fully trainable, grouped blocks go through pm_vit_block_bwd (one C call per block)
-        fast = (k.BLOCK_CALLS and k.GROUP_BIAS and not k.FUSE_COLSUM and dx.is_cuda and
-                not torch.cuda.is_current_stream_capturing())
+        fast = k.BLOCK_CALLS and dx.is_cuda and not torch.cuda.is_current_stream_capturing()
+        dims = ((D, Hd), (Hd, D), (D, D), (3 * D, D))  # (n_out, n_in) of fc2, fc1, proj, qkv
         bcache = ws.__dict__.setdefault("_bwd_descs", {})
         ptr_of = lambda t: t.data_ptr() if t is not None else 0
         for i in reversed(range(g.depth)):
@@ -683,8 +655,9 @@ class BlockStack:
                 side.wait_event(ev)
 
             # One grouped launch for the block's four weight gradients (full-K tiles, no split-K slabs), issued once the
-            # whole dgrad chain of the block is enqueued; it runs beside block i-1's chain.
-            grouped = tr and (not ends_pass or i - lowest >= k.UNGROUP_TAIL) and k.can_group_wgrad(M, ((D, Hd), (Hd, D), (D, D), (3 * D, D)))
+            # whole dgrad chain of the block is enqueued; it runs beside block i-1's chain.  A grouped launch carries the qkv / fc1
+            # bias gradients (column sums of its dY); otherwise they are k.colsum launches on the side stream.
+            grouped = tr and (not ends_pass or i - lowest >= k.UNGROUP_TAIL) and k.can_group_wgrad(M, dims)
             if grouped and fast:
                 # the whole block in ONE C call (pm_vit_block_bwd): the same launches, the same fork / done events, from a
                 # descriptor built once per block and kept (every buffer it names is persistent)
@@ -717,26 +690,20 @@ class BlockStack:
                 fork()
                 with torch.cuda.stream(side):
                     k.linear_wgrad(dx_act, bw.h_act, gr["mlp.fc2.weight"], M, D, Hd, accumulate("mlp.fc2.weight", i))
-            # fc1.bias gradient = column sums of d_hidden: optionally fused into the dGELU epilogue that produces it
-            fuse_cs = tr and k.FUSE_COLSUM
             # the launcher's two-launch schedule, kernel by kernel: (fc2, fc1) behind dfc2 on the side stream, (proj, qkv) behind
             # the attention backward on the second one
-            two = (grouped and k.GROUP_BIAS and not fuse_cs and
-                   k.two_launch_group(M, ((D, Hd), (Hd, D), (D, D), (3 * D, D))))
+            two = grouped and k.two_launch_group(M, dims)
             group_mlp = [(dx_act, bw.h_act, gr["mlp.fc2.weight"], accumulate("mlp.fc2.weight", i)),
-                         (d_hidden, bw.ln2, gr["mlp.fc1.weight"], accumulate("mlp.fc1.weight", i),
-                          gr["mlp.fc1.bias"] if (grouped and k.GROUP_BIAS and not fuse_cs) else None)] if grouped else None
+                         (d_hidden, bw.ln2, gr["mlp.fc1.weight"], accumulate("mlp.fc1.weight", i), gr["mlp.fc1.bias"])] if grouped else None
             ev_mlp = None
-            k.linear_dgrad(dx_act, p["mlp.fc2.weight"], d_hidden, M, D, Hd, EPI_DGELU, aux=bw.h_pre,
-                           colsum=gr["mlp.fc1.bias"] if fuse_cs else None)
+            k.linear_dgrad(dx_act, p["mlp.fc2.weight"], d_hidden, M, D, Hd, EPI_DGELU, aux=bw.h_pre)
             if tr:
                 fork()
                 with torch.cuda.stream(side):
                     if not grouped:
                         k.linear_wgrad(d_hidden, bw.ln2, gr["mlp.fc1.weight"], M, Hd, D, accumulate("mlp.fc1.weight", i))
-                    if not fuse_cs and not (grouped and k.GROUP_BIAS):
                         k.colsum(d_hidden, gr["mlp.fc1.bias"], M, Hd)
-                    if two:
+                    elif two:
                         if not k.wgrad_group(group_mlp, M):
                             raise _lib.PolypMaeError("pm_wgrad_group refused a group that two_launch_group admitted")
                         ev_mlp = torch.cuda.Event()
@@ -758,17 +725,14 @@ class BlockStack:
                 ev.record(main)
                 last.wait_event(ev)
                 with torch.cuda.stream(last):
-                    gb = grouped and k.GROUP_BIAS  # bias gradients (column sums of dY) inside the grouped launch
-                    if not gb:
-                        k.colsum(d_qkv, gr["attn.qkv.bias"], M, 3 * D)
                     if grouped:
                         group_attn = [(dmid_act, bw.attn, gr["attn.proj.weight"], accumulate("attn.proj.weight", i)),
-                                      (d_qkv, bw.ln1, gr["attn.qkv.weight"], accumulate("attn.qkv.weight", i),
-                                       gr["attn.qkv.bias"] if gb else None)]
+                                      (d_qkv, bw.ln1, gr["attn.qkv.weight"], accumulate("attn.qkv.weight", i), gr["attn.qkv.bias"])]
                         ok = k.wgrad_group(group_attn, M, whole_k=True) if two else k.wgrad_group(group_mlp + group_attn, M)
                         if not ok:
                             raise _lib.PolypMaeError("pm_wgrad_group refused a group that can_group_wgrad admitted")
                     else:
+                        k.colsum(d_qkv, gr["attn.qkv.bias"], M, 3 * D)
                         k.linear_wgrad(d_qkv, bw.ln1, gr["attn.qkv.weight"], M, 3 * D, D, accumulate("attn.qkv.weight", i))
                     # no join here: the main stream runs on into block i-1 and waits for these events only before
                     # block i-2.  The block's matrix gradients are final behind the last launch of each stream.

@@ -365,7 +365,7 @@ class _VitClsFn(torch.autograd.Function):
             # the embedding's backward does not read the blocks' weight gradients: it runs BEFORE the main stream joins the
             # side stream, beside the tail block's last weight-gradient launches instead of behind them
             dx0, _ = BlockStack(k, g).backward(ws, x0, W, G, dx, dx_act, False, trainable, front,
-                                               lambda n, i: accumulate, cb, defer_join=k.DEFER_JOIN,
+                                               lambda n, i: accumulate, cb, defer_join=True,
                                                sparse_top=True if cls_top else None)
             if front and dx0 is not None:
                 _EncoderFrontMixin.front_bwd(rt, dx0, cols, None, B, L, accumulate, need, learn_pos)
@@ -583,7 +583,7 @@ class _MaeFn(torch.autograd.Function):
         front = need("cls_token") or need("patch_embed.proj.weight") or need("patch_embed.proj.bias")
         cb_e = (lambda i: sync.block_done("blocks.", i)) if sync is not None else None
         dx0, _ = BlockStack(k, ge).backward(ws_e, x0, We, Ge, ws_e.dx[last & 1 ^ 1], ws_e.dx_act[last & 1 ^ 1], True, tr_e,
-                                            front, acc_fn, cb_e, defer_join=k.DEFER_JOIN)
+                                            front, acc_fn, cb_e, defer_join=True)
         if front and dx0 is not None:
             _EncoderFrontMixin.front_bwd(rt, dx0, cols, ids_keep, B, keep, accumulate, need, False)
         BlockStack.join_deferred(ws_e)

@@ -37,7 +37,7 @@ def test_library_exports_every_declared_symbol(built):
     assert set(_lib.SIGNATURES) | {"pm_strerror", "pm_abi_version", "pm_gemm_workspace_bytes", "pm_workspace_bytes",
                                    "pm_wgrad_group_workspace_bytes", "pm_aug_resized_crop_workspace_bytes"} == set(names)
     handle = _lib.load()
-    assert handle.pm_abi_version() == _lib.ABI_VERSION == 15
+    assert handle.pm_abi_version() == _lib.ABI_VERSION == 16
     # nothing undeclared leaves the library: every exported pm_* symbol is in the header (diagnostic hooks included)
     import subprocess
     out = subprocess.run(["nm", "-D", "--defined-only", built], capture_output=True, text=True).stdout
@@ -139,6 +139,64 @@ def test_gemm_dispatch_table(built):
     assert _gemm_plan(handle, 0, 0, BF16, 0, BF16, E.EPI_STORE, 0, 264, 64)[0] == _lib.PM_ESHAPE
     assert _gemm_plan(handle, 0, 0, BF16, 0, BF16, E.EPI_STORE, 128, 264, 36)[0] == _lib.PM_EALIGN
     assert _gemm_plan(handle, 0, 0, BF16, 0, BF16, E.EPI_RESIDUAL, 128, 264, 64)[0] == _lib.PM_EINVAL  # f32 residual stream only
+
+
+def _attention_plan(handle, backward, B, N, H, dh, dtype):
+    """pm_attention_plan -> (status, (family, nt, ct, grid, launches, lds bytes of launch 0, of launch 1))."""
+    from ssl4polyp_amd import _lib
+    info = _lib.AttentionPlanInfo()
+    st = handle.pm_attention_plan(backward, B, N, H, dh, dtype, ctypes.byref(info))
+    return st, (info.family, info.nt, info.ct, info.grid, info.launches, info.lds_bytes[0], info.lds_bytes[1])
+
+
+def test_attention_dispatch_table(built):
+    """What pm_attention_fwd / pm_attention_bwd launch for a shape (pm_attention_plan), against tests/golden/attention_plan.json:
+    the table the dispatcher gave when its rules were gathered into plan_attention, before the kernels and switches it cannot
+    name were deleted.  Rows: (B, H) = (64, 12) at 20 sequence lengths x dh 32 / 64 / 80 x bf16 / fp16 / fp32, forward and
+    backward; the persistent forward's grid at B H = 6 .. 3072; the refusals."""
+    import json
+    from ssl4polyp_amd import _lib
+    handle = _lib.load()
+    BF16, F16, F32 = _lib.PM_BF16, _lib.PM_F16, _lib.PM_F32
+    HEAD, PERSISTENT, SPLIT, FUSED = _lib.ATTN_FWD_HEAD, _lib.ATTN_FWD_PERSISTENT, _lib.ATTN_BWD_SPLIT, _lib.ATTN_BWD_FUSED
+    rows = json.load(open(os.path.join(REPO, "tests", "golden", "attention_plan.json")))
+    assert len(rows) == 360 + 6 + 8
+    for r in rows:
+        st, plan = _attention_plan(handle, r["backward"], r["B"], r["N"], r["H"], r["dh"], r["dtype"])
+        assert st == r["status"], (r, st)
+        if st == 0:
+            want = tuple(r["plan"][f] for f in ("family", "nt", "ct", "grid", "launches")) + tuple(r["plan"]["lds_bytes"])
+            assert plan == want, (r, plan)
+    assert {(r["B"] * r["H"]) for r in rows[360:366]} == {6, 256, 257, 259, 768, 3072}
+    assert [r["status"] for r in rows[366:]] == [_lib.PM_ESHAPE, _lib.PM_ESHAPE, _lib.PM_EINVAL, _lib.PM_ESHAPE] * 2
+    # rows derived by hand from the rules
+    plan = lambda *a: _attention_plan(handle, *a)
+    for half in (BF16, F16):
+        # forward, dh 64, N 193..224: persistent, [K0 | V0 | K1 | V1 | Q] of 7 x 32 rows of 128 B; rounds = ceil(BH / 256),
+        # grid = ceil(BH / rounds)
+        for (B, H), grid in (((64, 12), 256), ((257, 1), 129), ((37, 7), 130), ((1, 6), 6)):
+            for N in (193, 197, 224):
+                assert plan(0, B, N, H, 64, half) == (0, (PERSISTENT, 7, 7, grid, 1, 143360, 0)), (B, H, N)
+        assert 5 * 7 * 32 * 64 * 2 == 143360
+        assert plan(0, 64, 192, 12, 64, half)[1][0] == plan(0, 64, 225, 12, 64, half)[1][0] == HEAD
+        assert plan(0, 64, 197, 12, 32, half) == (0, (HEAD, 7, 7, 768, 1, 28672, 0))
+        assert plan(0, 64, 100, 12, 64, half)[1][:2] == (HEAD, 7)  # the seven-tile instantiation serves 65 <= N <= 192 too
+        assert plan(1, 64, 197, 12, 64, half) == (0, (FUSED, 7, 7, 768, 1, 116480, 0))
+        assert plan(1, 64, 257, 12, 64, half) == (0, (FUSED, 9, 9, 768, 1, 149760, 0))
+        assert plan(1, 64, 65, 12, 80, half) == (0, (SPLIT, 3, 3, 768, 2, 49152, 49920))
+    assert plan(0, 64, 257, 12, 80, F32) == (0, (HEAD, 9, 3, 768, 1, 73728, 0))
+    assert plan(1, 64, 197, 12, 64, F32) == (0, (SPLIT, 7, 7, 768, 2, 114688, 116480))
+    for dt in (BF16, F16, F32):
+        assert plan(0, 64, 65, 12, 80, dt)[1][:2] == (HEAD, 3)
+        for bwd in (0, 1):  # the instantiated tile counts
+            for dh, ladder in ((32, (1, 2, 7, 9)), (64, (1, 2, 7, 9)), (80, (3, 9))):
+                got = {N: plan(bwd, 64, N, 12, dh, dt)[1][1] for N in range(1, 289)}
+                assert sorted(set(got.values())) == list(ladder)
+                assert all(32 * nt >= N for N, nt in got.items())
+                if dh != 80:
+                    assert (got[32], got[33], got[64], got[65], got[224], got[225]) == (1, 2, 2, 7, 7, 9)
+                else:
+                    assert (got[96], got[97]) == (3, 9)
 
 
 def test_no_cpu_fallback():

@@ -6,8 +6,8 @@ One JSON line per shape: microseconds per call (the median of `--windows` window
 listed), the algorithmic GB/s of that median (dy + x + dres in, dx + dx_act out), and with --parent DIR (a checkout of the commit
 to compare with, its library built: DIR/ssl4polyp_amd/lib/libpolypmae.so, or the library file itself) the same for the parent's
 library in the same process, windows alternating, plus whether dx / dx_act and the three column sums are bit-identical to the
-parent's (they are under the default grid bound; another bound is another association of the sums).  The default shapes are
-the ViT-B/16 fine-tune step at bs 64 and 32 and the MAE decoder at bs 256.  PM_LN_BWD_BLOCKS (read once by the library) picks the grid bound of the new build.
+parent's (they are as long as both builds bound the grid alike; another bound is another association of the sums).  The default
+shapes are the ViT-B/16 fine-tune step at bs 64 and 32 and the MAE decoder at bs 256.
 
 A stand-alone figure says what the kernel can do with the whole device; inside the step it shares the CUs with the weight
 gradients, and only the in-step A/B (profiles/README.md) decides a default."""
@@ -61,8 +61,7 @@ def main():
                                                 _ptr(o["dx"]), D, _ptr(o["dx_act"]), k.act, _ptr(o["sums"][0]), _ptr(o["sums"][1]),
                                                 _ptr(o["sums"][2]), M, D, _ptr(ws), ws.numel(), _stream()), "pm_layernorm_bwd")
 
-        rec = {"M": M, "D": D, "precision": args.precision, "calls": args.calls,
-               "grid_bound": os.environ.get("PM_LN_BWD_BLOCKS", "default")}
+        rec = {"M": M, "D": D, "precision": args.precision, "calls": args.calls}
         for n in libs:  # one call each on zeroed sums: the results to compare
             call(n)
         torch.cuda.synchronize()
