@@ -117,6 +117,10 @@ class Kernels:
         self.lib = _lib.load()
         self.precision = precision
         self.act_dtype, self.act = PRECISIONS[precision]
+        self._need_cache: Dict[tuple, object] = {}      # what the library answered per shape: workspace bytes, grouping plans
+        self._opts_cache: Optional[tuple] = None        # ((WGRAD_BLOCKS, gemm_variant), weight-gradient pm_gemm_opts, the others')
+        self._side = self._side2 = None                 # the two weight-gradient streams, once a backward has asked for them
+        self._scratch_bufs: Dict[str, torch.Tensor] = {}  # "_ws", "_ws_front", "_ws_group", "_ws_ln", "_ws_cs_main", "_ws_cs_side"
 
     # -- helpers ------------------------------------------------------------------------------
     def layernorm_fwd(self, x, gamma, beta, y, mean, rstd, M, D):
@@ -135,19 +139,17 @@ class Kernels:
     #    shape; a buffer only ever grows, and growing it (first step of a new shape) drains the device first because the
     #    side stream may still be using the old one
     def _need(self, key, query) -> int:
-        cache = self.__dict__.setdefault("_need_cache", {})
-        n = cache.get(key)
+        n = self._need_cache.get(key)
         if n is None:
-            n = cache[key] = int(query())
+            n = self._need_cache[key] = int(query())
         return n
 
     def _scratch(self, name: str, nbytes: int, device) -> torch.Tensor:
-        ws = getattr(self, name, None)
+        ws = self._scratch_bufs.get(name)
         if ws is None or ws.device != device or ws.numel() < nbytes:
             if ws is not None and ws.device == device:
                 torch.cuda.synchronize(device)
-            ws = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
-            setattr(self, name, ws)
+            ws = self._scratch_bufs[name] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
         return ws
 
     # The side streams are shared by every Kernels object of the process (one set per device): the HIP runtime multiplexes
@@ -158,20 +160,20 @@ class Kernels:
         return _shared_stream(device, f"aux{j}")
 
     def side_stream(self, device):
-        st = getattr(self, "_side", None)
+        st = self._side
         if st is None or st.device != device:
             st = self._side = _shared_stream(device, "side")
         return st
 
     def side_stream2(self, device):
         """The second weight-gradient stream (busy in the backward only) IS the second forward chain's (busy in the forward only)."""
-        st = getattr(self, "_side2", None)
+        st = self._side2
         if st is None or st.device != device:
             st = self._side2 = _shared_stream(device, "aux0")
         return st
 
     def _opts(self, wgrad: bool):
-        o = self.__dict__.get("_opts_cache")
+        o = self._opts_cache
         if o is None or o[0] != (self.WGRAD_BLOCKS, self.gemm_variant):
             key = (self.WGRAD_BLOCKS, self.gemm_variant)
             o = self._opts_cache = (key, _lib.GemmOpts(self.WGRAD_BLOCKS, self.gemm_variant), _lib.GemmOpts(0, self.gemm_variant))
@@ -227,7 +229,7 @@ class Kernels:
         admission rules are the LIBRARY's (pm_wgrad_group_plan: bf16, whole 32-token k-steps, K >= 2048, tiles of at least
         256 x 128, 16-byte alignment) -- asked, not restated here; the policy on top is the engine's."""
         key = ("can_group", K, self.act, tuple(dims), self.GROUP_MIN_TILES)
-        cache = self.__dict__.setdefault("_need_cache", {})
+        cache = self._need_cache
         hit = cache.get(key)
         if hit is not None:
             return hit
@@ -251,7 +253,7 @@ class Kernels:
         if not self.TWO_GROUPS:
             return False
         key = ("two_launch", K, self.act, tuple(dims))
-        cache = self.__dict__.setdefault("_need_cache", {})
+        cache = self._need_cache
         hit = cache.get(key)
         if hit is None:
             ok = True
@@ -273,7 +275,7 @@ class Kernels:
 
     def _colsum_workspace(self, device, M: int, N: int):
         # partial rows: one scratch per stream (main / wgrad side stream) so concurrent column sums never share it
-        on_side = getattr(self, "_side", None) is not None and torch.cuda.current_stream() == self._side
+        on_side = self._side is not None and torch.cuda.current_stream() == self._side
         need = self._need(("cs", M, N), lambda: self.lib.pm_workspace_bytes(_lib.WS_COLSUM, M, N))
         return self._scratch("_ws_cs_side" if on_side else "_ws_cs_main", need, device)
 
@@ -289,6 +291,14 @@ class Kernels:
     def attention_bwd(self, qkv, out, dout, lse, delta, dqkv, B, N, H, dh):
         _lib.check(self.lib.pm_attention_bwd(_ptr(qkv), _ptr(out), _ptr(dout), _ptr(lse), _ptr(delta), _ptr(dqkv), B, N,
                                              H, dh, self.act, _stream()), "pm_attention_bwd")
+
+    def mae_unshuffle_bwd(self, dx, ids_shuffle, demb, dmask_token, B, L, keep, D):
+        """Backward of pm_mae_unshuffle: dx f32 [B (L + 1), D] -> demb act [B (keep + 1), D], the masked rows summed into dmask_token
+        (f32 [D], += ; None: frozen) in a fixed order through partial rows in the main stream's column-sum scratch."""
+        ws = self._scratch("_ws_cs_main", self._need(("unshuf", D), lambda: self.lib.pm_workspace_bytes(_lib.WS_UNSHUFFLE_BWD, 1, D)),
+                           dx.device)
+        _lib.check(self.lib.pm_mae_unshuffle_bwd(_ptr(dx), _ptr(ids_shuffle), _ptr(demb), self.act, _ptr(dmask_token), B, L, keep, D,
+                                                 _ptr(ws), ws.numel(), _stream()), "pm_mae_unshuffle_bwd")
 
     def gather_rows(self, src: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """dst[r] = src[idx[r]] for a 2-D (or 1-D) contiguous src; idx int32 on the device; out: a contiguous [R, width] destination."""
@@ -383,9 +393,18 @@ class StackWorkspace:
             self.delta = e(B * g.heads * N, dt=f32)
             self.dx = [e(M, D, dt=f32), e(M, D, dt=f32)]
             self.dx_act = [e(M, D) for _ in range(5)]
+        # what BlockStack keeps here between calls
+        self._fwd_descs: Dict[tuple, tuple] = {}   # (block, sample range) -> (key, pm_block_fwd_desc)
+        self._bwd_descs: Dict[int, tuple] = {}     # block -> (key, pm_block_bwd_desc, done events, objects kept alive)
+        self._top_c: Optional[dict] = None         # the cls-row top block's compact buffers (BlockStack.top_compact)
+        self._deferred_join: list = []             # events a backward(defer_join=True) left for join_deferred
+        self.cls_top = False                       # the last forward ran its top block on the cls rows: its result is [B, D]
 
     def block(self, i: int) -> BlockWorkspace:
         return self.blocks[i if self.training else i % len(self.blocks)]
+
+
+_MLP_HALF_BUFFERS = ("x", "attn", "x_mid", "ln2", "mean2", "rstd2", "h_pre", "h_act", "x_out")  # BlockStack._mlp_half, in its order
 
 
 class BlockStack:
@@ -393,6 +412,14 @@ class BlockStack:
 
     def __init__(self, k: Kernels, g: StackGeom):
         self.k, self.g = k, g
+
+    @staticmethod
+    def fork(src, dst):
+        """Everything enqueued on `src` so far happens before whatever `dst` is given next (a fresh event per fork: an event still
+        waited for by an overlapped optimizer update must not be re-recorded)."""
+        ev = torch.cuda.Event()
+        ev.record(src)
+        dst.wait_event(ev)
 
     def forward(self, ws: StackWorkspace, x_in: torch.Tensor, W: Sequence[Dict[str, torch.Tensor]],
                 before_block: Optional[Callable[[int], None]] = None, keep_from: int = 0, cls_top: bool = False) -> torch.Tensor:
@@ -403,17 +430,23 @@ class BlockStack:
         (evaluation, linear probe) keeps none.
         cls_top: the caller reads row 0 of every sample of the result only (out_token "cls", models.py:134-136).  Behind its attention,
         the TOP block is then per-token work whose other rows nobody reads: proj + residual, LayerNorm2, fc1 + GELU, fc2 + residual run
-        on the B cls rows (gathered behind the attention), and the result comes back as [B, D] (= [B, 1, D] for the head kernels)."""
+        on the B cls rows (gathered behind the attention), and the result comes back as [B, D] (= [B, 1, D] for the head kernels).
+        Whether the stack took that path (it needs N > 1 and a block to run) is left in `ws.cls_top`, where the backward and the
+        caller read it; a training workspace takes it at a batch that is a multiple of 8 only, and is refused here otherwise."""
         k, g = self.k, self.g
         if not ws.training:
             keep_from = g.depth
-        cls_top = cls_top and ws.N > 1 and g.depth >= 1
-        B, N, M, D, Hd = ws.B, ws.N, ws.M, g.dim, g.hidden
+        B, N, D = ws.B, ws.N, g.dim
+        cls_top = bool(cls_top and N > 1 and g.depth >= 1)
+        if cls_top and ws.training and B % 8:
+            raise _lib.PolypMaeError("the cls-row top block needs a batch that is a multiple of 8 to train (16-byte k-major rows)")
+        ws.cls_top = cls_top
+        tc = None
         if cls_top and x_in.is_cuda:
             # a new workspace fills its cls-row index tables with launches on THIS stream: they must be enqueued before the fork
             # below, or the other half's gather reads `rows` on its own stream before they are written (recycled allocator
             # memory then holds stale indices: an out-of-bounds gather)
-            self.top_compact(ws, g, k.act_dtype, x_in.device)
+            tc = self.top_compact(ws, g, k.act_dtype, x_in.device)
         # The forward has no second stream of its own work to share the CUs with, so the batch is cut into two halves
         # that run as independent chains on two streams: one half's GEMM tails / attention / LayerNorm fill the CUs
         # the other half's kernels leave idle (every op is per token or per (sample, head), and the halves write
@@ -423,10 +456,8 @@ class BlockStack:
         split = nparts > 1 and main is not None and not torch.cuda.is_current_stream_capturing()
         if split:
             auxs = [k.aux_stream(x_in.device, j) for j in range(nparts - 1)]
-            ev = torch.cuda.Event()
-            ev.record(main)
             for aux in auxs:
-                aux.wait_event(ev)
+                self.fork(main, aux)
             cuts = [B * j // nparts for j in range(nparts + 1)]
             parts = [((main if j == 0 else auxs[j - 1]), cuts[j], cuts[j + 1]) for j in range(nparts)]
         else:
@@ -435,7 +466,7 @@ class BlockStack:
         fast = k.BLOCK_CALLS and x_in.is_cuda
         if fast:
             lib = k.lib
-            cache = ws.__dict__.setdefault("_fwd_descs", {})
+            cache = ws._fwd_descs
             raw = [(st.cuda_stream if st is not None and st is not main else None) for st, _, _ in parts]
         x = x_in
         for i in range(g.depth):
@@ -445,10 +476,8 @@ class BlockStack:
                 else:
                     before_block(i)
             bw, p = ws.block(i), W[i]
-            if cls_top and i == g.depth - 1:
-                x = self._top_block_forward_cls(ws, bw, p, x, parts, main, i >= keep_from)
-                continue
-            if fast:
+            top = cls_top and i == g.depth - 1
+            if fast and not top:
                 # one C call per (block, sample range): pm_vit_block_fwd issues the same seven launches from a descriptor that
                 # is built once and kept (every buffer it names is persistent: workspace, flat parameters, bf16 shadow)
                 for j, (st, b0, b1) in enumerate(parts):
@@ -461,72 +490,62 @@ class BlockStack:
                                "pm_vit_block_fwd")
                 x = bw.x_out
                 continue
+            if top and tc is None:
+                tc = self.top_compact(ws, g, k.act_dtype, x.device)
             for st, b0, b1 in parts:
-                r0, r1, Bh = b0 * N, b1 * N, b1 - b0
-                Mh = r1 - r0
-                h0, h1 = b0 * g.heads * N, b1 * g.heads * N
+                r0, r1 = b0 * N, b1 * N
                 with (torch.cuda.stream(st) if st is not None and st is not main else contextlib.nullcontext()):
-                    xs = x[r0:r1]
-                    k.layernorm_fwd(xs, p["norm1.weight"], p["norm1.bias"], bw.ln1[r0:r1], bw.mean1[r0:r1], bw.rstd1[r0:r1],
-                                    Mh, D)
-                    k.linear_fwd(bw.ln1[r0:r1], p["attn.qkv.weight"], p["attn.qkv.bias"], bw.qkv[r0:r1], Mh, 3 * D, D)
-                    k.attention_fwd(bw.qkv[r0:r1], bw.attn[r0:r1], bw.lse[h0:h1], Bh, N, g.heads, g.dh)
-                    k.linear_fwd(bw.attn[r0:r1], p["attn.proj.weight"], p["attn.proj.bias"], bw.x_mid[r0:r1], Mh, D, D,
-                                 EPI_RESIDUAL, resid=xs)
-                    k.layernorm_fwd(bw.x_mid[r0:r1], p["norm2.weight"], p["norm2.bias"], bw.ln2[r0:r1], bw.mean2[r0:r1],
-                                    bw.rstd2[r0:r1], Mh, D)
-                    k.linear_fwd(bw.ln2[r0:r1], p["mlp.fc1.weight"], p["mlp.fc1.bias"], bw.h_act[r0:r1], Mh, Hd, D, EPI_GELU,
-                                 aux=bw.h_pre[r0:r1] if i >= keep_from else None)
-                    k.linear_fwd(bw.h_act[r0:r1], p["mlp.fc2.weight"], p["mlp.fc2.bias"], bw.x_out[r0:r1], Mh, D, Hd,
-                                 EPI_RESIDUAL, resid=bw.x_mid[r0:r1])
-            x = bw.x_out
+                    self._attn_half(bw, p, x, b0, b1, N)
+                    if top:  # the two gathers, then the rest of the block on the cls rows of these samples
+                        idx = tc["rows"][b0:b1]
+                        k.gather_rows(x.view(-1, D), idx, out=tc["x"][b0:b1])
+                        k.gather_rows(bw.attn.view(-1, D), idx, out=tc["attn"][b0:b1])
+                        self._mlp_half(p, [tc[n][b0:b1] for n in _MLP_HALF_BUFFERS], b1 - b0, i >= keep_from)
+                    else:
+                        self._mlp_half(p, [t[r0:r1] for t in (x, bw.attn, bw.x_mid, bw.ln2, bw.mean2, bw.rstd2, bw.h_pre, bw.h_act,
+                                                              bw.x_out)], r1 - r0, i >= keep_from)
+            x = tc["x_out"] if top else bw.x_out
         if split:
             for aux in auxs:
-                ev = torch.cuda.Event()
-                ev.record(aux)
-                main.wait_event(ev)
+                self.fork(aux, main)
         return x
+
+    def _attn_half(self, bw: BlockWorkspace, p, x: torch.Tensor, b0: int, b1: int, N: int) -> None:
+        """The first three launches of a block over samples [b0, b1) of the dense workspaces: LayerNorm1, qkv GEMM, attention."""
+        k, g = self.k, self.g
+        D = g.dim
+        r0, r1, h0, h1 = b0 * N, b1 * N, b0 * g.heads * N, b1 * g.heads * N
+        ln1 = bw.ln1[r0:r1]
+        qkv = bw.qkv[r0:r1]
+        k.layernorm_fwd(x[r0:r1], p["norm1.weight"], p["norm1.bias"], ln1, bw.mean1[r0:r1], bw.rstd1[r0:r1], r1 - r0, D)
+        k.linear_fwd(ln1, p["attn.qkv.weight"], p["attn.qkv.bias"], qkv, r1 - r0, 3 * D, D)
+        k.attention_fwd(qkv, bw.attn[r0:r1], bw.lse[h0:h1], b1 - b0, N, g.heads, g.dh)
+
+    def _mlp_half(self, p, bufs, M: int, keep: bool) -> None:
+        """The last four launches of a block over M rows: proj + residual, LayerNorm2, fc1 + GELU, fc2 + residual.  bufs: the row
+        ranges (_MLP_HALF_BUFFERS) of a BlockWorkspace and the block's input, or of the compact cls-row buffers.  keep: fc1 stores
+        its pre-activation (a backward will run through this block)."""
+        k, D, Hd = self.k, self.g.dim, self.g.hidden
+        x, attn, x_mid, ln2, mean2, rstd2, h_pre, h_act, x_out = bufs
+        k.linear_fwd(attn, p["attn.proj.weight"], p["attn.proj.bias"], x_mid, M, D, D, EPI_RESIDUAL, resid=x)
+        k.layernorm_fwd(x_mid, p["norm2.weight"], p["norm2.bias"], ln2, mean2, rstd2, M, D)
+        k.linear_fwd(ln2, p["mlp.fc1.weight"], p["mlp.fc1.bias"], h_act, M, Hd, D, EPI_GELU, aux=h_pre if keep else None)
+        k.linear_fwd(h_act, p["mlp.fc2.weight"], p["mlp.fc2.bias"], x_out, M, D, Hd, EPI_RESIDUAL, resid=x_mid)
 
     @staticmethod
     def top_compact(ws: StackWorkspace, g: StackGeom, act_dtype, dev) -> dict:
         """Compact [B, ...] buffers of the top block's cls rows (forward saves + the head's gradient), kept on the workspace."""
-        tc = ws.__dict__.get("_top_c")
+        tc = ws._top_c
         if tc is None:
             B, N, D, Hd, f32 = ws.B, ws.N, g.dim, g.hidden, torch.float32
             e = lambda *s, dt=act_dtype: torch.empty(*s, dtype=dt, device=dev)
             rows = torch.arange(B, dtype=torch.int32, device=dev) * N          # (built on the device: no host copy, no sync)
             inv = torch.full((B * N,), -1, dtype=torch.int32, device=dev)
             inv[rows.long()] = torch.arange(B, dtype=torch.int32, device=dev)
-            tc = ws.__dict__["_top_c"] = dict(
+            tc = ws._top_c = dict(
                 rows=rows, inv=inv, x=e(B, D, dt=f32), attn=e(B, D), x_mid=e(B, D, dt=f32), ln2=e(B, D), mean2=e(B, dt=f32),
                 rstd2=e(B, dt=f32), h_pre=e(B, Hd), h_act=e(B, Hd), x_out=e(B, D, dt=f32), dx=e(B, D, dt=f32), dx_act=e(B, D))
         return tc
-
-    def _top_block_forward_cls(self, ws, bw, p, x, parts, main, keep: bool) -> torch.Tensor:
-        k, g = self.k, self.g
-        N, D, Hd = ws.N, g.dim, g.hidden
-        tc = self.top_compact(ws, g, k.act_dtype, x.device)
-        for st, b0, b1 in parts:
-            r0, r1, Bh = b0 * N, b1 * N, b1 - b0
-            Mh = r1 - r0
-            h0, h1 = b0 * g.heads * N, b1 * g.heads * N
-            with (torch.cuda.stream(st) if st is not None and st is not main else contextlib.nullcontext()):
-                xs = x[r0:r1]
-                k.layernorm_fwd(xs, p["norm1.weight"], p["norm1.bias"], bw.ln1[r0:r1], bw.mean1[r0:r1], bw.rstd1[r0:r1], Mh, D)
-                k.linear_fwd(bw.ln1[r0:r1], p["attn.qkv.weight"], p["attn.qkv.bias"], bw.qkv[r0:r1], Mh, 3 * D, D)
-                k.attention_fwd(bw.qkv[r0:r1], bw.attn[r0:r1], bw.lse[h0:h1], Bh, N, g.heads, g.dh)
-                idx = tc["rows"][b0:b1]
-                k.gather_rows(x.view(-1, D), idx, out=tc["x"][b0:b1])
-                k.gather_rows(bw.attn.view(-1, D), idx, out=tc["attn"][b0:b1])
-                k.linear_fwd(tc["attn"][b0:b1], p["attn.proj.weight"], p["attn.proj.bias"], tc["x_mid"][b0:b1], Bh, D, D, EPI_RESIDUAL,
-                             resid=tc["x"][b0:b1])
-                k.layernorm_fwd(tc["x_mid"][b0:b1], p["norm2.weight"], p["norm2.bias"], tc["ln2"][b0:b1], tc["mean2"][b0:b1],
-                                tc["rstd2"][b0:b1], Bh, D)
-                k.linear_fwd(tc["ln2"][b0:b1], p["mlp.fc1.weight"], p["mlp.fc1.bias"], tc["h_act"][b0:b1], Bh, Hd, D, EPI_GELU,
-                             aux=tc["h_pre"][b0:b1] if keep else None)
-                k.linear_fwd(tc["h_act"][b0:b1], p["mlp.fc2.weight"], p["mlp.fc2.bias"], tc["x_out"][b0:b1], Bh, D, Hd, EPI_RESIDUAL,
-                             resid=tc["x_mid"][b0:b1])
-        return tc["x_out"]
 
     def _fwd_desc(self, ws: StackWorkspace, bw: BlockWorkspace, p, x: torch.Tensor, b0: int, b1: int, keep: bool = True):
         """pm_block_fwd_desc of block `bw` for samples [b0, b1): every pointer at the first row of the range.  keep = False:
@@ -585,8 +604,7 @@ class BlockStack:
                  last_bias_grad_done: bool, trainable: Sequence[bool], need_input_grad: bool,
                  accumulate: Callable[[str, int], bool], on_block_done: Optional[Callable[[int], None]] = None,
                  prev_bias_grad: Optional[torch.Tensor] = None,
-                 ends_pass: bool = True, defer_join: bool = False,
-                 sparse_top: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+                 ends_pass: bool = True, defer_join: bool = False) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
         """dx / dx_act: gradient w.r.t. the stack output (f32 + act copy).  G[i][name] = f32 gradient
         tensors (vectors are += targets and must be zeroed or hold the running sum; matrices follow
         accumulate(name, i)).  `last_bias_grad_done`: the producer of dx already added colsum(dx) into the
@@ -596,8 +614,8 @@ class BlockStack:
         `defer_join`: do not make the main stream wait for the last blocks' weight gradients here -- the caller still has
         main-stream work that does not read them (the embedding's backward) and calls `join_deferred(ws)` after it; the side
         stream's last launches then run beside that work instead of in front of it.
-        `sparse_top` (any non-None value): the forward ran with cls_top and dx / dx_act are the head's gradient on the B cls rows
-        ([B, D]); the top block's backward then runs on those rows up to its attention (see _top_block_sparse).
+        `ws.cls_top` (left by the forward): dx / dx_act are the head's gradient on the B cls rows ([B, D]); the top block's backward
+        then runs on those rows up to its attention (see _top_block_sparse).
         Returns (dx_in f32, dx_in act) or (None, None) when nothing below needs it."""
         k, g = self.k, self.g
         B, N, M, D, Hd = ws.B, ws.N, ws.M, g.dim, g.hidden
@@ -613,7 +631,7 @@ class BlockStack:
         # PM_BLOCK_CALLS: fully trainable, grouped blocks go through pm_vit_block_bwd (one C call per block)
         fast = k.BLOCK_CALLS and dx.is_cuda and not torch.cuda.is_current_stream_capturing()
         dims = ((D, Hd), (Hd, D), (D, D), (3 * D, D))  # (n_out, n_in) of fc2, fc1, proj, qkv
-        bcache = ws.__dict__.setdefault("_bwd_descs", {})
+        bcache = ws._bwd_descs
         ptr_of = lambda t: t.data_ptr() if t is not None else 0
         for i in reversed(range(g.depth)):
             if i < lowest and not need_input_grad:
@@ -621,6 +639,8 @@ class BlockStack:
                 return None, None
             bw, p, gr, tr = ws.block(i), W[i], G[i], trainable[i]
             xin = x_in if i == 0 else ws.block(i - 1).x_out
+            # the bias gradient of the Linear below this block (fc2 of block i-1, or the caller's): LayerNorm1' adds colsum(d x_in) to it
+            below_bias = (G[i - 1]["mlp.fc2.bias"] if trainable[i - 1] else None) if i > 0 else prev_bias_grad
             need_dx_in = need_input_grad or i > lowest
             o = i & 1
             dmid, din = ws.dx[o], ws.dx[o ^ 1]  # f32 residual gradients: main stream only, ping-pong (in-place add is fine)
@@ -631,11 +651,8 @@ class BlockStack:
             pin = next((j for j in range(5) if dx_act is ws.dx_act[j]), 4)
             dmid_act, din_act = ws.dx_act[(pin + 1) % 5], ws.dx_act[(pin + 2) % 5]
             join(i + 2)  # block i overwrites what the side stream read for block i+2
-            if i == g.depth - 1 and sparse_top is not None:
-                if tr and ws.B % 8:
-                    raise _lib.PolypMaeError("the cls-row top block needs a batch that is a multiple of 8 to train (16-byte k-major rows)")
-                below_bias = (G[i - 1]["mlp.fc2.bias"] if trainable[i - 1] else None) if i > 0 else prev_bias_grad
-                ev_last = self._top_block_sparse(ws, bw, p, gr, xin, dx, dx_act, sparse_top, last_bias_grad_done, dmid, din, din_act,
+            if i == g.depth - 1 and ws.cls_top:
+                ev_last = self._top_block_sparse(ws, bw, p, gr, xin, dx, dx_act, last_bias_grad_done, dmid, din, din_act,
                                                  d_qkv, below_bias, lambda n: accumulate(n, i), main, on_block_done, i, tr)
                 if ev_last is not None:
                     pending[i] = ev_last
@@ -648,12 +665,6 @@ class BlockStack:
             # other's k-loop (both read the same dY; every buffer the side stream reads stays untouched until the
             # join below).
             side = k.side_stream(main.device) if tr else None
-
-            def fork():
-                ev = torch.cuda.Event()
-                ev.record(main)
-                side.wait_event(ev)
-
             # One grouped launch for the block's four weight gradients (full-K tiles, no split-K slabs), issued once the
             # whole dgrad chain of the block is enqueued; it runs beside block i-1's chain.  A grouped launch carries the qkv / fc1
             # bias gradients (column sums of its dY); otherwise they are k.colsum launches on the side stream.
@@ -661,13 +672,12 @@ class BlockStack:
             if grouped and fast:
                 # the whole block in ONE C call (pm_vit_block_bwd): the same launches, the same fork / done events, from a
                 # descriptor built once per block and kept (every buffer it names is persistent)
-                below_bias = (G[i - 1]["mlp.fc2.bias"] if trainable[i - 1] else None) if i > 0 else prev_bias_grad
                 acc = (int(accumulate("attn.qkv.weight", i)) | int(accumulate("attn.proj.weight", i)) << 1 |
                        int(accumulate("mlp.fc1.weight", i)) << 2 | int(accumulate("mlp.fc2.weight", i)) << 3)
                 key = (dx.data_ptr(), dx_act.data_ptr(), xin.data_ptr(), gr["attn.qkv.weight"].data_ptr(),
                        p["attn.qkv.weight"].data_ptr(), gr["norm1.weight"].data_ptr(),
                        below_bias.data_ptr() if below_bias is not None else 0, acc, k.gemm_variant, k.GROUP_BLOCKS, k.GROUP_BLOCKS_SLICED, k.TWO_GROUPS, k.TIME_BLOCK_EVENTS,
-                       ptr_of(k.__dict__.get("_ws_ln")), ptr_of(k.__dict__.get("_ws_group")))  # (scratch is replaced when it grows)
+                       ptr_of(k._scratch_bufs.get("_ws_ln")), ptr_of(k._scratch_bufs.get("_ws_group")))  # (scratch is replaced when it grows)
                 ent = bcache.get(i)
                 if ent is None or ent[0] != key:
                     ent = bcache[i] = (key,) + self._bwd_desc(ws, bw, p, gr, xin, dx, dx_act, dmid, dmid_act, din, din_act,
@@ -687,7 +697,7 @@ class BlockStack:
                 continue
             # ---- MLP branch ----
             if tr and not grouped:
-                fork()
+                self.fork(main, side)
                 with torch.cuda.stream(side):
                     k.linear_wgrad(dx_act, bw.h_act, gr["mlp.fc2.weight"], M, D, Hd, accumulate("mlp.fc2.weight", i))
             # the launcher's two-launch schedule, kernel by kernel: (fc2, fc1) behind dfc2 on the side stream, (proj, qkv) behind
@@ -696,9 +706,10 @@ class BlockStack:
             group_mlp = [(dx_act, bw.h_act, gr["mlp.fc2.weight"], accumulate("mlp.fc2.weight", i)),
                          (d_hidden, bw.ln2, gr["mlp.fc1.weight"], accumulate("mlp.fc1.weight", i), gr["mlp.fc1.bias"])] if grouped else None
             ev_mlp = None
-            k.linear_dgrad(dx_act, p["mlp.fc2.weight"], d_hidden, M, D, Hd, EPI_DGELU, aux=bw.h_pre)
-            if tr:
-                fork()
+
+            def wgrad_behind_dfc2():
+                nonlocal ev_mlp
+                self.fork(main, side)
                 with torch.cuda.stream(side):
                     if not grouped:
                         k.linear_wgrad(d_hidden, bw.ln2, gr["mlp.fc1.weight"], M, Hd, D, accumulate("mlp.fc1.weight", i))
@@ -708,22 +719,19 @@ class BlockStack:
                             raise _lib.PolypMaeError("pm_wgrad_group refused a group that two_launch_group admitted")
                         ev_mlp = torch.cuda.Event()
                         ev_mlp.record(side)
-            k.linear_dgrad(d_hidden, p["mlp.fc1.weight"], ws.d_ln, M, Hd, D)
-            k.layernorm_bwd(ws.d_ln, bw.x_mid, p["norm2.weight"], bw.mean2, bw.rstd2, dx, dmid, dmid_act,
-                            gr["norm2.weight"] if tr else None, gr["norm2.bias"] if tr else None,
-                            gr["attn.proj.bias"] if tr else None, M, D)
+
+            self._mlp_dgrad(p, gr if tr else None, M, dx, dx_act, bw.h_pre, d_hidden, ws.d_ln, bw.x_mid, bw.mean2, bw.rstd2, dmid, dmid_act,
+                            wgrad_behind_dfc2 if tr else None)
             # ---- attention branch ----
             if tr and not grouped:
-                fork()
+                self.fork(main, side)
                 with torch.cuda.stream(side):
                     k.linear_wgrad(dmid_act, bw.attn, gr["attn.proj.weight"], M, D, D, accumulate("attn.proj.weight", i))
             k.linear_dgrad(dmid_act, p["attn.proj.weight"], ws.d_attn, M, D, D)
             k.attention_bwd(bw.qkv, bw.attn, ws.d_attn, bw.lse, ws.delta, d_qkv, B, N, g.heads, g.dh)
             if tr:
                 last = k.side_stream2(main.device) if two else side
-                ev = torch.cuda.Event()
-                ev.record(main)
-                last.wait_event(ev)
+                self.fork(main, last)
                 with torch.cuda.stream(last):
                     if grouped:
                         group_attn = [(dmid_act, bw.attn, gr["attn.proj.weight"], accumulate("attn.proj.weight", i)),
@@ -743,19 +751,10 @@ class BlockStack:
                         if two:
                             last.wait_event(ev_mlp)
                         on_block_done(i)
-            run_ln1 = need_dx_in or tr
-            if run_ln1:
-                k.linear_dgrad(d_qkv, p["attn.qkv.weight"], ws.d_ln, M, 3 * D, D)
-            if not run_ln1:
+            if not (need_dx_in or tr):
                 join(0)
                 return None, None
-            below_bias = None
-            if i > 0 and trainable[i - 1]:
-                below_bias = G[i - 1]["mlp.fc2.bias"]
-            elif i == 0:
-                below_bias = prev_bias_grad
-            k.layernorm_bwd(ws.d_ln, xin, p["norm1.weight"], bw.mean1, bw.rstd1, dmid, din, din_act,
-                            gr["norm1.weight"] if tr else None, gr["norm1.bias"] if tr else None, below_bias, M, D)
+            self._qkv_dgrad_ln1(p, gr if tr else None, M, d_qkv, ws.d_ln, xin, bw.mean1, bw.rstd1, dmid, din, din_act, below_bias)
             dx, dx_act = din, din_act
             if on_block_done is not None and not tr:
                 on_block_done(i)
@@ -765,10 +764,33 @@ class BlockStack:
             join(0)
         return dx, dx_act
 
-    def _top_block_sparse(self, ws, bw, p, gr, xin, dx, dx_act, sparse_top, last_bias_grad_done, dmid, din, din_act, d_qkv, below_bias,
+    def _mlp_dgrad(self, p, gr, M: int, dy, dy_act, h_pre, d_hidden, d_ln, x_mid, mean2, rstd2, dmid, dmid_act,
+                   behind_dfc2: Optional[Callable[[], None]] = None) -> None:
+        """The dgrad chain of a block's MLP branch over M rows, dense or compact: dfc2 + dGELU (dy_act -> d_hidden), dfc1 (-> d_ln),
+        LayerNorm2' (+ the residual gradient dy -> dmid f32, dmid_act).  gr: the block's gradient tensors, None when it is frozen
+        (LayerNorm2' then leaves out d gamma, d beta and the proj bias gradient it carries).  behind_dfc2(): the caller's weight
+        gradients that read d_hidden, enqueued between dfc2 and dfc1 -- on which stream and through which scratch is its business."""
+        k, D, Hd = self.k, self.g.dim, self.g.hidden
+        k.linear_dgrad(dy_act, p["mlp.fc2.weight"], d_hidden, M, D, Hd, EPI_DGELU, aux=h_pre)
+        if behind_dfc2 is not None:
+            behind_dfc2()
+        k.linear_dgrad(d_hidden, p["mlp.fc1.weight"], d_ln, M, Hd, D)
+        k.layernorm_bwd(d_ln, x_mid, p["norm2.weight"], mean2, rstd2, dy, dmid, dmid_act,
+                        gr["norm2.weight"] if gr else None, gr["norm2.bias"] if gr else None, gr["attn.proj.bias"] if gr else None, M, D)
+
+    def _qkv_dgrad_ln1(self, p, gr, M: int, d_qkv, d_ln, xin, mean1, rstd1, dmid, din, din_act, below_bias) -> None:
+        """The tail of a block's backward over M rows: qkv dgrad (d_qkv -> d_ln), LayerNorm1' (+ dmid -> din f32, din_act; colsum of
+        din into below_bias).  gr as in _mlp_dgrad."""
+        k, D = self.k, self.g.dim
+        k.linear_dgrad(d_qkv, p["attn.qkv.weight"], d_ln, M, 3 * D, D)
+        k.layernorm_bwd(d_ln, xin, p["norm1.weight"], mean1, rstd1, dmid, din, din_act,
+                        gr["norm1.weight"] if gr else None, gr["norm1.bias"] if gr else None, below_bias, M, D)
+
+    def _top_block_sparse(self, ws, bw, p, gr, xin, dx, dx_act, last_bias_grad_done, dmid, din, din_act, d_qkv, below_bias,
                           acc, main, on_block_done, i, tr):
-        """Backward of the top block of a classifier that reads the cls row only (forward: _top_block_forward_cls).  dx / dx_act are the
-        head's gradient on the B cls rows ([B, D], pm_vit_head_bwd with N = 1); the block's saves behind the attention are compact too.
+        """Backward of the top block of a classifier that reads the cls row only (forward: the cls_top block of BlockStack.forward).
+        dx / dx_act are the head's gradient on the B cls rows ([B, D], pm_vit_head_bwd with N = 1); the block's saves behind the
+        attention are compact too.
         The MLP branch and the proj Linear -- dfc2 + dGELU, dfc1, LayerNorm2', proj dgrad, the fc2 / fc1 / proj weight gradients -- run at
         M = B; d mid and d attn are scattered into zero-filled dense buffers (a zero row of dY adds nothing anywhere, and the residual
         path adds zero to zero), and from the attention backward on -- which spreads the gradient over all keys -- the block is dense:
@@ -776,41 +798,33 @@ class BlockStack:
         is the same kind of identity as embedding only the kept patches in MAE."""
         k, g = self.k, self.g
         tc = self.top_compact(ws, g, k.act_dtype, dx.device)
-        rows, inv = tc["rows"], tc["inv"]
         B, N, M, D, Hd = ws.B, ws.N, ws.M, g.dim, g.hidden
         R = B
-        dev, f32 = dx.device, torch.float32
-        e = lambda *s, dt=k.act_dtype: torch.empty(*s, dtype=dt, device=dev)
+        e = lambda *s, dt=k.act_dtype: torch.empty(*s, dtype=dt, device=dx.device)
         dxc, dxac = dx.view(R, D), dx_act.view(R, D)
-        G_ = (lambda n: gr[n]) if tr else (lambda n: None)
         if tr and not last_bias_grad_done:
             k.colsum(dxc, gr["mlp.fc2.bias"], R, D)
-        # ---- MLP branch on the live rows
-        d_hidden_c = e(R, Hd)
-        k.linear_dgrad(dxac, p["mlp.fc2.weight"], d_hidden_c, R, D, Hd, EPI_DGELU, aux=tc["h_pre"])
-        if tr:
+        # ---- MLP branch on the live rows: its weight gradients are a few tiles each, on the main stream behind dfc2
+        d_hidden_c, d_ln_c, dmid_c, dmid_act_c, d_attn_c = e(R, Hd), e(R, D), e(R, D, dt=torch.float32), e(R, D), e(R, D)
+
+        def wgrad_behind_dfc2():
             k.linear_wgrad(dxac, tc["h_act"], gr["mlp.fc2.weight"], R, D, Hd, acc("mlp.fc2.weight"), ws_name="_ws_front")
             k.linear_wgrad(d_hidden_c, tc["ln2"], gr["mlp.fc1.weight"], R, Hd, D, acc("mlp.fc1.weight"), ws_name="_ws_front")
             k.colsum(d_hidden_c, gr["mlp.fc1.bias"], R, Hd)
-        d_ln_c = e(R, D)
-        k.linear_dgrad(d_hidden_c, p["mlp.fc1.weight"], d_ln_c, R, Hd, D)
-        dmid_c, dmid_act_c = e(R, D, dt=f32), e(R, D)
-        k.layernorm_bwd(d_ln_c, tc["x_mid"], p["norm2.weight"], tc["mean2"], tc["rstd2"], dxc, dmid_c, dmid_act_c, G_("norm2.weight"),
-                        G_("norm2.bias"), G_("attn.proj.bias"), R, D)
+
+        self._mlp_dgrad(p, gr if tr else None, R, dxc, dxac, tc["h_pre"], d_hidden_c, d_ln_c, tc["x_mid"], tc["mean2"], tc["rstd2"],
+                        dmid_c, dmid_act_c, wgrad_behind_dfc2 if tr else None)
         # ---- proj on the live rows, then dense again for the attention backward
         if tr:
             k.linear_wgrad(dmid_act_c, tc["attn"], gr["attn.proj.weight"], R, D, D, acc("attn.proj.weight"), ws_name="_ws_front")
-        d_attn_c = e(R, D)
         k.linear_dgrad(dmid_act_c, p["attn.proj.weight"], d_attn_c, R, D, D)
-        k.scatter_rows_zero(dmid_c, inv, dmid.view(M, D))
-        k.scatter_rows_zero(d_attn_c, inv, ws.d_attn.view(M, D))
+        k.scatter_rows_zero(dmid_c, tc["inv"], dmid.view(M, D))
+        k.scatter_rows_zero(d_attn_c, tc["inv"], ws.d_attn.view(M, D))
         k.attention_bwd(bw.qkv, bw.attn, ws.d_attn, bw.lse, ws.delta, d_qkv, B, N, g.heads, g.dh)
         ev_last = None
         if tr:
             side = k.side_stream(main.device)
-            ev = torch.cuda.Event()
-            ev.record(main)
-            side.wait_event(ev)
+            self.fork(main, side)
             with torch.cuda.stream(side):
                 k.colsum(d_qkv, gr["attn.qkv.bias"], M, 3 * D)
                 k.linear_wgrad(d_qkv, bw.ln1, gr["attn.qkv.weight"], M, 3 * D, D, acc("attn.qkv.weight"))
@@ -818,9 +832,7 @@ class BlockStack:
                 ev_last.record(side)
                 if on_block_done is not None:
                     on_block_done(i)
-        k.linear_dgrad(d_qkv, p["attn.qkv.weight"], ws.d_ln, M, 3 * D, D)
-        k.layernorm_bwd(ws.d_ln, xin, p["norm1.weight"], bw.mean1, bw.rstd1, dmid, din, din_act, G_("norm1.weight"), G_("norm1.bias"),
-                        below_bias, M, D)
+        self._qkv_dgrad_ln1(p, gr if tr else None, M, d_qkv, ws.d_ln, xin, bw.mean1, bw.rstd1, dmid, din, din_act, below_bias)
         if not tr and on_block_done is not None:
             on_block_done(i)
         return (ev_last,) if ev_last is not None else None
@@ -829,5 +841,6 @@ class BlockStack:
     def join_deferred(ws: StackWorkspace) -> None:
         """Make the current stream wait for the weight-gradient launches a backward(..., defer_join=True) left running."""
         main = torch.cuda.current_stream()
-        for ev in ws.__dict__.pop("_deferred_join", []):
+        for ev in ws._deferred_join:
             main.wait_event(ev)
+        ws._deferred_join = []

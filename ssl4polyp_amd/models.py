@@ -109,6 +109,7 @@ class _Runtime:
         # parameters of the module that take no part in its forward and therefore never get a gradient, whatever their
         # requires_grad flag says (ViT_from_MAE keeps the deleted decoder's positional table, models.py:171-175)
         self.unused: tuple = ()
+        self.grad_enabled = True  # torch.is_grad_enabled() where the op was called (ops.py): it is already off inside Function.forward
 
     def wait_updates(self, mat_through: Optional[int] = None, also=()) -> None:
         """Make the current stream (and the streams in `also`) wait for pending optimizer updates: all of them
@@ -203,6 +204,77 @@ def _plan_grads(rt: _Runtime, names: List[str], needs: List[bool]):
     return False
 
 
+_FRONT_PARAMS = ("cls_token", "patch_embed.proj.weight", "patch_embed.proj.bias")
+
+
+class _Needs:
+    """Which parameters get a gradient in this pass: the autograd node's (names, needs_input_grad) without the parameters that
+    take no part in the forward (rt.unused), asked by name, per block stack, and for the embedding in front of the encoder."""
+
+    def __init__(self, names, needs, unused=()):
+        self.map = {n: bool(nd) and n not in unused for n, nd in zip(names, needs)}
+
+    def __call__(self, name: str) -> bool:
+        return self.map.get(name, False)
+
+    def blocks(self, prefix: str, depth: int) -> List[bool]:
+        """Per block of the stack `prefix`: does any of its parameters train?"""
+        return [any(self(f"{prefix}{i}.{n}") for n in BLOCK_PARAM_NAMES) for i in range(depth)]
+
+    def front(self, learn_pos: bool) -> bool:
+        """Does anything in front of the encoder's first block train?  learn_pos: the positional table follows its flag (the
+        classifiers: timm's table is learnable, models.py:28-33, and finetune.py:52-55 mode "full" sets requires_grad on the
+        MAE-derived one too); MAE pre-training keeps its sincos table fixed whatever the flag says (models_mae.py:37)."""
+        return any(self(n) for n in _FRONT_PARAMS) or (learn_pos and self("pos_embed"))
+
+    def keep_from(self, depth: int) -> int:
+        """The lowest encoder block a backward reaches (BlockStack.forward keep_from): staged fine-tuning (finetune.py:49-91: head +
+        the last one or two blocks) with the front frozen too never runs below its lowest trainable block."""
+        return 0 if self.front(True) else min((i for i, t in enumerate(self.blocks("blocks.", depth)) if t), default=depth)
+
+
+# A Linear whose reduction dimension is not a multiple of the GEMM k-step (patch 14: 3 * 14 * 14 = 588 -> 640) runs in a layout padded
+# with zeros (Kernels.padded_k): `shape` is the parameter's [out, in] matrix, `padded` the same with the reduction dimension rounded up.
+def _padded_operand(rt: "_Runtime", name: str, shape, padded) -> torch.Tensor:
+    """The act-typed matrix of Linear `name` as a GEMM operand: its view of the shadow when nothing is padded, else a zero-padded
+    cast of the f32 parameter (pm_pad_cast)."""
+    if padded == shape:
+        return rt.flat.shadow_view(name).view(*shape)
+    return rt.k.pad_cast(rt.flat.param_view(name).view(*shape), *padded)
+
+
+def _padded_wgrad(rt: "_Runtime", dy, x, name: str, shape, padded, M: int, accumulate: bool, ws_name: str = "_ws") -> None:
+    """d W of Linear `name` (+)= dy[M, out]^T x[M, in]: straight into the flat gradient when nothing is padded, else through a
+    temporary in the padded layout whose valid part pm_unpad_add moves (or adds) there."""
+    k = rt.k
+    dw = rt.flat.grad_view(name).view(*shape)
+    if padded == shape:
+        k.linear_wgrad(dy, x, dw, M, shape[0], shape[1], accumulate, ws_name=ws_name)
+    else:
+        tmp = torch.empty(*padded, dtype=torch.float32, device=dy.device)
+        k.linear_wgrad(dy, x, tmp, M, padded[0], padded[1], False, ws_name=ws_name)
+        k.unpad_add(tmp, dw, accumulate)
+
+
+def _final_norm_and_stack_bwd(rt: "_Runtime", g: StackGeom, ws: StackWorkspace, prefix: str, norm: str, x, mean, rstd, x_in,
+                              need: _Needs, accumulate: bool, need_input_grad: bool, **schedule):
+    """Backward of a stack's final LayerNorm `norm` (its dY is in ws.d_ln, its input x the stack's output) into the dx slot the top
+    block reads -- carrying the top block's fc2 bias gradient -- then of the stack itself.  schedule: ends_pass / defer_join of
+    BlockStack.backward.  -> the gradient of the stack's input (f32), or None when nothing below needs it."""
+    k, f = rt.k, rt.flat
+    W, G = rt.stack_weights(prefix, g.depth)
+    tr = need.blocks(prefix, g.depth)
+    last = g.depth - 1
+    dx, dx_act = ws.dx[last & 1 ^ 1], ws.dx_act[last & 1 ^ 1]
+    k.layernorm_bwd(ws.d_ln, x, f.param_view(norm + ".weight"), mean, rstd, None, dx, dx_act,
+                    f.grad_view(norm + ".weight") if need(norm + ".weight") else None,
+                    f.grad_view(norm + ".bias") if need(norm + ".bias") else None,
+                    G[last]["mlp.fc2.bias"] if tr[last] else None, ws.M, g.dim)
+    sync = rt.grad_sync
+    cb = (lambda i: sync.block_done(prefix, i)) if sync is not None else None
+    return BlockStack(k, g).backward(ws, x_in, W, G, dx, dx_act, True, tr, need_input_grad, lambda n, i: accumulate, cb, **schedule)[0]
+
+
 class _EncoderFrontMixin:
     """Patch-embed + token assembly shared by both paths."""
 
@@ -219,10 +291,7 @@ class _EncoderFrontMixin:
         _lib.check(k.lib.pm_patch_im2col(_ptr(imgs), _ptr(ids_keep), _ptr(cols), PEp, k.act, B, C, img, p, keep, _stream()),
                    "pm_patch_im2col")
         emb = torch.empty(B * keep, D, dtype=torch.float32, device=dev)
-        if PEp == PE:
-            w = f.shadow_view("patch_embed.proj.weight").view(D, PE)
-        else:
-            w = k.pad_cast(f.param_view("patch_embed.proj.weight").view(D, PE), D, PEp)
+        w = _padded_operand(rt, "patch_embed.proj.weight", (D, PE), (D, PEp))
         k.linear_fwd(cols, w, f.param_view("patch_embed.proj.bias"), emb, B * keep, D, PEp)
         x0 = torch.empty(B * (keep + 1), D, dtype=torch.float32, device=dev)
         _lib.check(k.lib.pm_assemble_tokens(_ptr(emb), _ptr(f.param_view("cls_token")), _ptr(f.param_view(pos_name)),
@@ -249,13 +318,7 @@ class _EncoderFrontMixin:
                                                     keep, D, _stream()), "pm_assemble_tokens_bwd")
         if need("patch_embed.proj.weight"):
             # (its own split-K scratch: the last blocks' weight gradients may still be running on the side stream)
-            if PEp == PE:
-                k.linear_wgrad(demb, cols, f.grad_view("patch_embed.proj.weight").view(D, PE), B * keep, D, PE, accumulate,
-                               ws_name="_ws_front")
-            else:  # the gradient in the padded layout, its valid columns into the parameter's gradient
-                dw = torch.empty(D, PEp, dtype=torch.float32, device=cols.device)
-                k.linear_wgrad(demb, cols, dw, B * keep, D, PEp, False, ws_name="_ws_front")
-                k.unpad_add(dw, f.grad_view("patch_embed.proj.weight").view(D, PE), accumulate)
+            _padded_wgrad(rt, demb, cols, "patch_embed.proj.weight", (D, PE), (D, PEp), B * keep, accumulate, ws_name="_ws_front")
         if need("patch_embed.proj.bias"):
             k.colsum(demb, f.grad_view("patch_embed.proj.bias"), B * keep, D)
 
@@ -271,7 +334,7 @@ class _VitClsFn(torch.autograd.Function):
         L = mod.patch_embed.num_patches
         N = L + 1
         D = g.dim
-        needs = ctx.needs_input_grad[5:] if getattr(rt, "grad_enabled", True) else (False,) * len(params)   # (set by ops._vit_forward)
+        needs = ctx.needs_input_grad[5:] if rt.grad_enabled else (False,) * len(params)   # (set by ops._vit_forward)
         # (grad mode is already off inside Function.forward.)  Linear probe (finetune.py mode "none": only lin_head
         # trains): nothing below the head needs saved activations -> the forward-only workspace (2 blocks instead of 12).
         below = any(nd for n, nd in zip(names, needs) if not n.startswith("lin_head"))
@@ -280,18 +343,13 @@ class _VitClsFn(torch.autograd.Function):
         cols, x0 = _EncoderFrontMixin.front_fwd(rt, imgs, None, L)
         ws = rt.get_ws(g, B, N, below)
         W, _ = rt.stack_weights("blocks.", g.depth)
-        # staged fine-tuning (finetune.py:49-91: head + the last one or two blocks): with the front frozen too, no backward reaches
-        # the blocks below the lowest trainable one -- their fc1 pre-activations need not be stored
-        need_map = dict(zip(names, needs))
-        front_needs = any(need_map.get(n, False) for n in ("cls_token", "pos_embed", "patch_embed.proj.weight", "patch_embed.proj.bias"))
-        keep_from = 0 if front_needs else min((i for i in range(g.depth)
-                                                if any(need_map.get(f"blocks.{i}.{n}", False) for n in BLOCK_PARAM_NAMES)), default=g.depth)
         # out_token "cls" (models.py:134-136): the head reads row 0 of every sample -- behind its attention the top block runs on those
-        # rows only, forward and backward (engine.BlockStack._top_block_forward_cls / _top_block_sparse).  Training needs B % 8 == 0
-        # (16-byte rows of the k-major weight-gradient operands); otherwise the dense block.
+        # rows only, forward and backward (engine.BlockStack.forward cls_top / _top_block_sparse).  Training needs B % 8 == 0
+        # (16-byte rows of the k-major weight-gradient operands); otherwise the dense block.  What the stack did is in ws.cls_top.
         cls_top = pool == 0 and k.SPARSE_TOP and N > 1 and (B % 8 == 0 or not any(needs))
-        x = BlockStack(k, g).forward(ws, x0, W, before_block=_update_gate(rt, "blocks."), keep_from=keep_from, cls_top=cls_top)
-        Nh = 1 if cls_top else N   # rows per sample of what the head kernels see
+        x = BlockStack(k, g).forward(ws, x0, W, before_block=_update_gate(rt, "blocks."),
+                                     keep_from=_Needs(names, needs, rt.unused).keep_from(g.depth), cls_top=cls_top)
+        Nh = 1 if ws.cls_top else N   # rows per sample of what the head kernels see
         rt.wait_updates()  # norm / lin_head and anything else still pending
         dev = imgs.device
         f32 = torch.float32
@@ -314,8 +372,7 @@ class _VitClsFn(torch.autograd.Function):
                 ctx.ws = None
                 cols = x0 = None
             ctx.saved = (cols, x0, x, feat, xhm, mean, rstd)
-            ctx.dims = (B, L, N, D, n_class, pool, head, below)
-            ctx.cls_top = cls_top
+            ctx.dims = (B, L, N, D, n_class, pool, head, below, Nh if (below or pool) else 1)   # (last: rows per sample of the saved x)
         else:
             rt.put_ws(g, ws)
         return logits if head else feat
@@ -325,30 +382,22 @@ class _VitClsFn(torch.autograd.Function):
         rt, names, ws = ctx.rt, ctx.names, ctx.ws
         k, f, mod, g = rt.k, rt.flat, rt.module, rt.enc_geom
         cols, x0, x, feat, xhm, mean, rstd = ctx.saved
-        B, L, N, D, n_class, pool, head, below = ctx.dims
+        B, L, N, D, n_class, pool, head, below, x_rows = ctx.dims
         needs = list(ctx.needs_input_grad[5:])
-        need_map = dict(zip(names, needs))
-        need = lambda n: need_map.get(n, False)
+        need = _Needs(names, needs, rt.unused)
         accumulate = _plan_grads(rt, names, needs)
         if not accumulate and need("lin_head.weight"):
             f.grad_view("lin_head.weight").zero_()
-        trainable = [any(need(f"blocks.{i}.{n}") for n in BLOCK_PARAM_NAMES) for i in range(g.depth)]
-        # timm's table is learnable (models.py:28-33); the MAE-derived classifier's is a frozen sincos buffer-like Parameter
-        # (models_mae.py:37) -- until finetune.py:52-55 (mode "full": requires_grad_(True) on EVERY parameter, applied by
-        # tc.py:5740 to whatever the factory returned) makes it trainable too.  Either way: follow the flag.
-        learn_pos = need("pos_embed")
-        front = need("cls_token") or need("patch_embed.proj.weight") or need("patch_embed.proj.bias") or \
-            (learn_pos and need("pos_embed"))
+        trainable = need.blocks("blocks.", g.depth)
+        front = need.front(True)
         below_head = front or any(trainable)
         dout = dout.contiguous().float()
-        cls_top = bool(getattr(ctx, "cls_top", False))
-        if below_head and cls_top:   # the head's gradient on the B cls rows only ([B, 1, D]): what the cls-row top block takes
+        if below_head and ws.cls_top:   # the head's gradient on the B cls rows only ([B, 1, D]): what the cls-row top block takes
             tc = BlockStack.top_compact(ws, g, k.act_dtype, dout.device)
             dx, dx_act = tc["dx"], tc["dx_act"]
         else:
             dx = ws.dx[0] if below_head else None
             dx_act = ws.dx_act[0] if below_head else None
-        x_rows = 1 if cls_top else (N if (below or pool) else 1)   # linear probe, cls token: only the saved cls rows [B, 1, D]
         _lib.check(k.lib.pm_vit_head_bwd(
             _ptr(dout) if head else None, None if head else _ptr(dout), _ptr(x), x_rows, pool,
             _ptr(f.param_view("norm.weight")), _ptr(f.param_view("lin_head.weight")) if head else None, _ptr(feat), _ptr(xhm),
@@ -365,10 +414,9 @@ class _VitClsFn(torch.autograd.Function):
             # the embedding's backward does not read the blocks' weight gradients: it runs BEFORE the main stream joins the
             # side stream, beside the tail block's last weight-gradient launches instead of behind them
             dx0, _ = BlockStack(k, g).backward(ws, x0, W, G, dx, dx_act, False, trainable, front,
-                                               lambda n, i: accumulate, cb, defer_join=True,
-                                               sparse_top=True if cls_top else None)
+                                               lambda n, i: accumulate, cb, defer_join=True)
             if front and dx0 is not None:
-                _EncoderFrontMixin.front_bwd(rt, dx0, cols, None, B, L, accumulate, need, learn_pos)
+                _EncoderFrontMixin.front_bwd(rt, dx0, cols, None, B, L, accumulate, need, True)
             BlockStack.join_deferred(ws)
         if sync is not None:
             sync.backward_done()
@@ -377,7 +425,7 @@ class _VitClsFn(torch.autograd.Function):
         ctx.saved = None
         # decoder_pos_embed survives in ViT_from_MAE (models.py:171-175) but takes no part in the forward: like autograd in the
         # reference it gets NO gradient (None, not zeros -- AdamW must skip it, not decay it) even when mode "full" flags it
-        grads = [None if (accumulate or not nd or n in rt.unused) else f.grad_view(n) for n, nd in zip(names, needs)]
+        grads = [None if (accumulate or not need(n)) else f.grad_view(n) for n in names]
         return (None, None, None, None, None, *grads)
 
 
@@ -446,7 +494,7 @@ class _MaeFn(torch.autograd.Function):
         De, Dd, PE = ge.dim, gd.dim, p * p * C
         dev = imgs.device
         f32 = torch.float32
-        training = any(ctx.needs_input_grad) and getattr(rt, "grad_enabled", True)  # (grad mode is already off inside Function.forward)
+        training = any(ctx.needs_input_grad) and rt.grad_enabled  # (grad mode is already off inside Function.forward)
         imgs = imgs.contiguous().float()
         ctx.set_materialize_grads(False)
         # -- masking (models_mae.py:123-148)
@@ -519,10 +567,8 @@ class _MaeFn(torch.autograd.Function):
         Me, Md = B * (keep + 1), B * (L + 1)
         dev = imgs.device
         needs = list(ctx.needs_input_grad[5:])
-        need_map = dict(zip(names, needs))
-        need = lambda n: need_map.get(n, False)
+        need = _Needs(names, needs, rt.unused)
         accumulate = _plan_grads(rt, names, needs)
-        acc_fn = lambda n, i: accumulate
         sync = rt.grad_sync
         if dloss is None:
             dloss = torch.zeros((), dtype=torch.float32, device=dev)
@@ -532,58 +578,29 @@ class _MaeFn(torch.autograd.Function):
         dpred_act = torch.empty(Md, PEp, dtype=k.act_dtype, device=dev)
         _lib.check(k.lib.pm_mae_loss_bwd(_ptr(imgs), _ptr(pred_full), PE, 1, _ptr(mask), _ptr(sums), _ptr(dloss),
                                          _ptr(dpred_act), PEp, k.act, B, C, img, p, npx, _stream()), "pm_mae_loss_bwd")
-        if PEp == PE:
-            if need("decoder_pred.weight"):
-                k.linear_wgrad(dpred_act, yn, f.grad_view("decoder_pred.weight"), Md, PE, Dd, accumulate)
-            if need("decoder_pred.bias"):
+        if need("decoder_pred.weight"):
+            _padded_wgrad(rt, dpred_act, yn, "decoder_pred.weight", (PE, Dd), (PEp, Dd), Md, accumulate)
+        if need("decoder_pred.bias"):
+            if PEp == PE:
                 k.colsum(dpred_act, f.grad_view("decoder_pred.bias"), Md, PE)
-            k.linear_dgrad(dpred_act, f.shadow_view("decoder_pred.weight"), ws_d.d_ln, Md, PE, Dd)
-        else:
-            if need("decoder_pred.weight"):
-                dw = torch.empty(PEp, Dd, dtype=torch.float32, device=dev)
-                k.linear_wgrad(dpred_act, yn, dw, Md, PEp, Dd, False)
-                k.unpad_add(dw, f.grad_view("decoder_pred.weight").view(PE, Dd), accumulate)
-            if need("decoder_pred.bias"):
+            else:
                 db = torch.zeros(1, PEp, dtype=torch.float32, device=dev)
                 k.colsum(dpred_act, db, Md, PEp)
                 k.unpad_add(db, f.grad_view("decoder_pred.bias").view(1, PE), True)  # (vector gradients always accumulate)
-            wpad = k.pad_cast(f.param_view("decoder_pred.weight").view(PE, Dd), PEp, Dd)
-            k.linear_dgrad(dpred_act, wpad, ws_d.d_ln, Md, PEp, Dd)
-        Wd, Gd = rt.stack_weights("decoder_blocks.", gd.depth)
-        tr_d = [any(need(f"decoder_blocks.{i}.{n}") for n in BLOCK_PARAM_NAMES) for i in range(gd.depth)]
-        last = gd.depth - 1
-        k.layernorm_bwd(ws_d.d_ln, xd, f.param_view("decoder_norm.weight"), mean_d, rstd_d, None, ws_d.dx[last & 1 ^ 1],
-                        ws_d.dx_act[last & 1 ^ 1],
-                        f.grad_view("decoder_norm.weight") if need("decoder_norm.weight") else None,
-                        f.grad_view("decoder_norm.bias") if need("decoder_norm.bias") else None,
-                        Gd[last]["mlp.fc2.bias"] if tr_d[last] else None, Md, Dd)
-        cb_d = (lambda i: sync.block_done("decoder_blocks.", i)) if sync is not None else None
-        dxd0, _ = BlockStack(k, gd).backward(ws_d, xd0, Wd, Gd, ws_d.dx[last & 1 ^ 1], ws_d.dx_act[last & 1 ^ 1], True, tr_d,
-                                             True, acc_fn, cb_d, ends_pass=False)
+        k.linear_dgrad(dpred_act, _padded_operand(rt, "decoder_pred.weight", (PE, Dd), (PEp, Dd)), ws_d.d_ln, Md, PEp, Dd)
+        dxd0 = _final_norm_and_stack_bwd(rt, gd, ws_d, "decoder_blocks.", "decoder_norm", xd, mean_d, rstd_d, xd0, need, accumulate,
+                                         True, ends_pass=False)
         # -- un-shuffle + decoder_embed
         demb_act = torch.empty(Me, Dd, dtype=k.act_dtype, device=dev)
-        # partial rows of the mask-token sum (fixed-order second stage)
-        cs_ws = k._scratch("_ws_cs_main", k._need(("unshuf", Dd), lambda: k.lib.pm_workspace_bytes(_lib.WS_UNSHUFFLE_BWD, 1, Dd)), dev)
-        _lib.check(k.lib.pm_mae_unshuffle_bwd(_ptr(dxd0), _ptr(ids_shuffle), _ptr(demb_act), k.act,
-                                              _ptr(f.grad_view("mask_token")) if need("mask_token") else None, B, L, keep,
-                                              Dd, _ptr(cs_ws), cs_ws.numel(), _stream()), "pm_mae_unshuffle_bwd")
+        k.mae_unshuffle_bwd(dxd0, ids_shuffle, demb_act, f.grad_view("mask_token") if need("mask_token") else None, B, L, keep, Dd)
         if need("decoder_embed.weight"):
             k.linear_wgrad(demb_act, latent, f.grad_view("decoder_embed.weight"), Me, Dd, De, accumulate)
         if need("decoder_embed.bias"):
             k.colsum(demb_act, f.grad_view("decoder_embed.bias"), Me, Dd)
         k.linear_dgrad(demb_act, f.shadow_view("decoder_embed.weight"), ws_e.d_ln, Me, Dd, De)
-        # -- encoder
-        We, Ge = rt.stack_weights("blocks.", ge.depth)
-        tr_e = [any(need(f"blocks.{i}.{n}") for n in BLOCK_PARAM_NAMES) for i in range(ge.depth)]
-        last = ge.depth - 1
-        k.layernorm_bwd(ws_e.d_ln, xe, f.param_view("norm.weight"), mean_e, rstd_e, None, ws_e.dx[last & 1 ^ 1],
-                        ws_e.dx_act[last & 1 ^ 1], f.grad_view("norm.weight") if need("norm.weight") else None,
-                        f.grad_view("norm.bias") if need("norm.bias") else None,
-                        Ge[last]["mlp.fc2.bias"] if tr_e[last] else None, Me, De)
-        front = need("cls_token") or need("patch_embed.proj.weight") or need("patch_embed.proj.bias")
-        cb_e = (lambda i: sync.block_done("blocks.", i)) if sync is not None else None
-        dx0, _ = BlockStack(k, ge).backward(ws_e, x0, We, Ge, ws_e.dx[last & 1 ^ 1], ws_e.dx_act[last & 1 ^ 1], True, tr_e,
-                                            front, acc_fn, cb_e, defer_join=True)
+        # -- encoder; the embedding's backward runs beside the last blocks' weight gradients, the join behind it
+        front = need.front(False)
+        dx0 = _final_norm_and_stack_bwd(rt, ge, ws_e, "blocks.", "norm", xe, mean_e, rstd_e, x0, need, accumulate, front, defer_join=True)
         if front and dx0 is not None:
             _EncoderFrontMixin.front_bwd(rt, dx0, cols, ids_keep, B, keep, accumulate, need, False)
         BlockStack.join_deferred(ws_e)

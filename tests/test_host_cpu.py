@@ -320,3 +320,12 @@ def test_module_patchify_helpers_match_the_reference_fixture(golden):
     ramp = torch.arange(2 * 3 * 32 * 32, dtype=torch.float32).reshape(2, 3, 32, 32)
     np.testing.assert_array_equal(m.patchify(ramp).numpy(), fx["patchify_ramp"])
     np.testing.assert_array_equal(m.unpatchify(torch.from_numpy(fx["patchify_ramp"])).numpy(), fx["unpatchify_ramp"])
+
+
+def test_stack_workspace_declares_its_state():
+    """What BlockStack keeps on a workspace between calls exists from construction on, as instance attributes (bench.py reads
+    `_bwd_descs` through the instance dictionary); building one needs neither the library nor a GPU."""
+    from ssl4polyp_amd.engine import StackGeom, StackWorkspace
+    ws = StackWorkspace(StackGeom(64, 2, 2, 256), 2, 5, torch.float32, torch.device("cpu"), True)
+    assert ws._fwd_descs == {} and ws._bwd_descs == {} and ws._top_c is None and ws._deferred_join == [] and ws.cls_top is False
+    assert {"_fwd_descs", "_bwd_descs", "_top_c", "_deferred_join", "cls_top"} <= set(vars(ws))
