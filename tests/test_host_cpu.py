@@ -199,6 +199,43 @@ def test_attention_dispatch_table(built):
                     assert (got[96], got[97]) == (3, 9)
 
 
+def test_attention_case_table_reaches_every_instantiation(built):
+    """tests/attention_cases.py (what tests/test_gpu_attention_edges.py runs, in every precision, forward and backward) against
+    pm_attention_plan: every (family, dh, tile count, 16-bit / f32) the plan can name for some N = 1..288 is the plan of some case;
+    the persistent forward walks 1, 2 and 3 heads per workgroup; the chunked configuration (ct < nt) is reached, with a whole
+    chunk of padding."""
+    from attention_cases import CASES
+    from ssl4polyp_amd import _lib
+    handle = _lib.load()
+    dtypes = {"bf16": _lib.PM_BF16, "fp16": _lib.PM_F16, "fp32": _lib.PM_F32}
+
+    def plans(B, N, H, dh):
+        for prec, dt in dtypes.items():
+            for bwd in (0, 1):
+                st, plan = _attention_plan(handle, bwd, B, N, H, dh, dt)
+                assert st == 0, (bwd, B, N, H, dh, prec)
+                yield prec, plan
+
+    key = lambda prec, plan, dh: (plan[0], dh, plan[1], prec != "fp32")
+    nameable = {key(prec, plan, dh) for dh in (32, 64, 80) for N in range(1, 289) for prec, plan in plans(64, N, 12, dh)}
+    assert len(nameable) == 2 * (2 * (4 + 4 + 2)) + 1   # forward + backward, 16-bit + f32, the ladders; the persistent forward
+    reached, walks, chunked = set(), set(), set()
+    for B, N, H, dh in CASES:
+        for prec, plan in plans(B, N, H, dh):
+            reached.add(key(prec, plan, dh))
+            if plan[0] == _lib.ATTN_FWD_PERSISTENT:
+                walks.add(-(-B * H // plan[3]))
+            if plan[2] < plan[1]:
+                chunked.add((plan[0], N, -(-N // (32 * plan[2]))))   # (family, N, chunks that hold a real row)
+    assert reached == nameable, sorted(nameable - reached)
+    assert walks == {1, 2, 3}
+    # f32, dh 80, nine tiles in chunks of three: N = 97 has one real row in the second chunk and a whole chunk of padding behind
+    # it, N = 193 one real row in the third chunk and two whole tiles of padding
+    for fam in (_lib.ATTN_FWD_HEAD, _lib.ATTN_BWD_SPLIT):
+        assert {c for f, _, c in chunked if f == fam} == {2, 3}, chunked
+        assert (fam, 97, 2) in chunked and (fam, 193, 3) in chunked
+
+
 def test_no_cpu_fallback():
     import ssl4polyp_amd as A
     from ssl4polyp_amd._lib import PolypMaeError
