@@ -634,6 +634,34 @@ int pm_boot_metrics(const double* score, const int* order, const unsigned char* 
                     const double* tau, double* out, int N, int M, int R, int K, int C, int sorted_ready, void* workspace,
                     size_t ws_bytes, void* stream);
 
+/* ---- the decision threshold of a run, chosen on its validation scores ------------------------------------------------------
+ * Replaces the reference's classification/metrics/thresholds.py: compute_policy_threshold (:299-390) for policy 0 f1_opt_on_val,
+ * 1 youden_on_val, 2 val_opt_youden (the same objective as 1), and compute_youden_j_threshold (:68-110: scikit-learn's roc_curve
+ * with drop_intermediate, first maximum of tpr - fpr, nextafter(max score, 1.0) when the curve's +inf point wins) for 3 youden.
+ *   score        f64 [M, N]  probabilities of the positive class in [0, 1] (anything else, NaN included, is outside the contract:
+ *                            no access leaves the buffers, the values are unspecified)
+ *   order        i32 [M, N]  per run, the frame indices in descending score order, as pm_boot_metrics takes it; an entry outside
+ *                            [0, N) is no frame (it belongs at the end of a run: it is placed at score 0 and counts for no class)
+ *   label        u8  [N]     0 / 1
+ *   previous_tau f64 [M]     the threshold carried into a run whose labels hold one class only; NaN = none (then 0.5)
+ *   out          f64 [M, 16] tau, n_candidates, degenerate, objective, tp, fp, tn, fn, recall, precision, f1, tpr, fpr, youden_j,
+ *                            n_unique, index.  Policies 0-2: n_unique is the number U of unique values of {0} + scores + {1}, the
+ *                            candidates are all of them (U <= 200) or those at numpy.linspace(0, U - 1, 200, dtype=int), index is the
+ *                            chosen candidate's.  Policy 3: n_candidates is the number of points roc_curve returns, n_unique the
+ *                            number of distinct scores, index the chosen point's in the curve before points are dropped (0 = +inf).
+ *                            One class only: degenerate = 1, n_candidates = 0, objective and n_unique NaN, tau = previous_tau if
+ *                            finite (index = -2) else 0.5 (index = -1) with the counts taken there; policy 3 has no answer (tau NaN,
+ *                            counts 0, index = -1).
+ *   candidates   f64 [M, 200] or NULL: the candidate list of policies 0-2 in ascending order (one class only: tau alone), NaN beyond
+ *                            it; all NaN for policy 3.
+ * Counts are exact and every ratio is one f64 division of them, so the values are the reference's bit for bit.  One launch of one
+ * workgroup per run on `stream`; nothing is read back, nothing is allocated.  Limits (PM_ESHAPE): 1 <= N <= 2^20, 1 <= M <= 256.
+ * workspace: 16-byte aligned, at least pm_select_tau_workspace(N, M, &bytes) bytes (PM_EINVAL otherwise, as for a missing buffer or
+ * a policy outside 0-3); its contents on entry do not matter. */
+int pm_select_tau_workspace(int N, int M, size_t* bytes);
+int pm_select_tau(const double* score, const int* order, const unsigned char* label, const double* previous_tau, int policy,
+                  double* out, double* candidates, int N, int M, void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

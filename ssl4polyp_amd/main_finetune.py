@@ -12,8 +12,14 @@ Training is the reference's: configure_finetune_parameters(--finetune_mode), Ada
 <output_dir>/log.txt (train loss, lr, img/s, val loss from the returned logits).  `--metrics` adds the reference's binary metrics at
 tau = 0.5 to the val and test records; `--bootstrap R` adds their 95 % cluster-bootstrap intervals (`bootstrap`, `ci_lower`,
 `ci_upper`) to the test record, with or without `--metrics` (metrics.py: one device call per chunk of replicates); a value that is
-not finite is logged as null; threshold selection stays in the reference's code.  `run(args)` returns
-the model and the last val logits.  Not here: sharded evaluation through the prefetcher.
+not finite is logged as null.  `--threshold_policy` chooses the decision threshold as the reference does (classification/metrics/
+thresholds.py; metrics.select_threshold, one device launch): f1_opt_on_val / youden_on_val / val_opt_youden / youden select tau on
+the val scores after every epoch (`val_tau`, `val_threshold` = the reference's record with split `<dataset_name>/val`, with
+`--metrics` also `val_metrics_at_tau`; the previous epoch's tau is carried into a one-class epoch), the checkpoint keeps it under
+`thresholds` / `threshold_records[<dataset>_val_<policy>]`, and the test record reports `test_tau`, `test_metrics_at_tau` and the
+bootstrap intervals at that tau; sun_val_frozen takes the tau from `--threshold_from`, such a checkpoint with exactly one
+threshold.  Without the flag nothing changes: tau = 0.5 and the records and checkpoints of before.  `run(args)` returns the model
+and the last val logits.  Not here: sharded evaluation through the prefetcher.
 """
 from __future__ import annotations
 
@@ -29,6 +35,10 @@ from . import models
 from .optim import FusedAdamW, LossScaler
 from .parallel import DataParallel
 from .train import FINETUNE_MODES, cls_cosine_lambda, configure_finetune_parameters, evaluate_cls, save_cls_checkpoint, train_epoch_cls
+
+
+SELECTING_POLICIES = ("f1_opt_on_val", "youden_on_val", "val_opt_youden", "youden")   # metrics.POLICIES
+FROZEN_POLICY = "sun_val_frozen"
 
 
 def get_args_parser():
@@ -67,6 +77,12 @@ def get_args_parser():
     p.add_argument("--bootstrap", default=0, type=int, metavar="R",
                    help="R > 0: 95 %% intervals of the test metrics from R cluster-bootstrap replicates (clusters: case_id per label)")
     p.add_argument("--bootstrap_seed", default=12345, type=int)
+    p.add_argument("--threshold_policy", default="none", choices=["none", *SELECTING_POLICIES, FROZEN_POLICY],
+                   help="how the decision threshold tau is chosen (the reference's threshold_policy): on the val split after every "
+                        "epoch, on the device; sun_val_frozen reuses the tau of --threshold_from")
+    p.add_argument("--dataset_name", default="dataset", help="names the val split in the threshold record and its checkpoint key")
+    p.add_argument("--threshold_from", default=None, metavar="CKPT",
+                   help="with --threshold_policy sun_val_frozen: a checkpoint of this command that holds exactly one threshold")
     return p
 
 
@@ -107,11 +123,13 @@ def strict(values) -> list:
 
 
 def metric_records(prefix: str, logits: torch.Tensor, targets: torch.Tensor, rows, device, metrics: bool = True, bootstrap: int = 0,
-                   seed: int = 0) -> dict:
+                   seed: int = 0, tau=None) -> dict:
     """The entries `--metrics` / `--bootstrap` add to a record.  metrics: <prefix>_metrics, the 16 values of the reference's
     compute_binary_metrics at tau = 0.5.  bootstrap > 0: `bootstrap`, ci_lower / ci_upper per reported metric from that many
     replicates that resample whole cases per label (rows without a case_id are clusters of their own).  A value that is not finite
-    (AUROC of a split without positives or without negatives) is logged as null, so that every line stays strict JSON."""
+    (AUROC of a split without positives or without negatives) is logged as null, so that every line stays strict JSON.
+    tau (f64 [1] on the device, the selected threshold): <prefix>_tau, with metrics also <prefix>_metrics_at_tau, and the intervals
+    are taken at that tau; it goes to the device calls as the tensor it is."""
     import numpy as np
     from . import metrics as MX
     probs = MX.positive_probs(logits.to(device))
@@ -119,16 +137,41 @@ def metric_records(prefix: str, logits: torch.Tensor, targets: torch.Tensor, row
     if metrics:
         values = MX.binary_metrics(probs, targets, METRICS_TAU, device=device)
         out[f"{prefix}_metrics"] = dict(zip(values, strict(values.values())))
+    if tau is not None:
+        out[f"{prefix}_tau"] = float(tau[0])
+        if metrics:
+            values = MX.binary_metrics(probs, targets, tau, device=device)
+            out[f"{prefix}_metrics_at_tau"] = dict(zip(values, strict(values.values())))
     if bootstrap > 0 and logits.shape[0] > 0:
         clusters = MX.build_cluster_set(rows, targets.tolist())
         draws = MX.draw_cluster_samples(clusters, np.random.default_rng(seed), bootstrap)
-        reps = MX.bootstrap_binary_metrics(probs, targets, METRICS_TAU, clusters.cluster, draws, n_clusters=clusters.n_clusters,
+        reps = MX.bootstrap_binary_metrics(probs, targets, METRICS_TAU if tau is None else tau, clusters.cluster, draws,
+                                           n_clusters=clusters.n_clusters,
                                            device=device)[:, 0, len(MX.METRIC_KEYS) - len(MX.REPORTED_KEYS):]
         lo, hi = MX.percentile_ci(reps, 0.95)
         out["bootstrap"] = int(bootstrap)
         out["ci_lower"] = dict(zip(MX.REPORTED_KEYS, strict(lo.tolist())))
         out["ci_upper"] = dict(zip(MX.REPORTED_KEYS, strict(hi.tolist())))
     return out
+
+
+def frozen_threshold(path):
+    """(tau, key, record) of the one threshold a checkpoint of this command holds (`thresholds` / `threshold_records`, written by a
+    run with a selecting --threshold_policy): what `--threshold_policy sun_val_frozen --threshold_from` reuses."""
+    if not path:
+        raise SystemExit("--threshold_policy sun_val_frozen reuses a selected tau: it needs --threshold_from CKPT")
+    if not os.path.exists(path):
+        raise SystemExit(f"--threshold_from {path}: no such file")
+    payload = torch.load(path, map_location="cpu", weights_only=False)
+    thresholds = payload.get("thresholds") if isinstance(payload, dict) else None
+    if not isinstance(thresholds, dict) or len(thresholds) != 1:
+        raise SystemExit(f"--threshold_from {path}: expected a checkpoint of this command with exactly one entry under 'thresholds' "
+                         f"(found {sorted(thresholds) if isinstance(thresholds, dict) else 'none'})")
+    (key, tau), = thresholds.items()
+    if not isinstance(tau, (int, float)) or not math.isfinite(float(tau)):
+        raise SystemExit(f"--threshold_from {path}: the threshold under {key!r} is not a finite number ({tau!r})")
+    record = dict((payload.get("threshold_records") or {}).get(key) or {})
+    return float(tau), key, record
 
 
 def run(args):
@@ -138,6 +181,15 @@ def run(args):
         raise SystemExit("--metrics / --bootstrap report the binary metrics: they need --num_classes 2")
     if args.fused_decode and args.decode != "device":
         raise SystemExit("--fused_decode needs --decode device")
+    policy = args.threshold_policy
+    selecting = policy in SELECTING_POLICIES
+    if policy != "none" and args.num_classes != 2:
+        raise SystemExit("--threshold_policy chooses a binary decision threshold: it needs --num_classes 2")
+    if selecting and not args.val_csv:
+        raise SystemExit(f"--threshold_policy {policy} selects tau on the val split: it needs --val_csv")
+    frozen = frozen_threshold(args.threshold_from) if policy == FROZEN_POLICY else None
+    if policy != FROZEN_POLICY and args.threshold_from:
+        raise SystemExit("--threshold_from goes with --threshold_policy sun_val_frozen")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -184,6 +236,26 @@ def run(args):
             with open(log_path, "a") as f:
                 f.write(json.dumps(record) + "\n")
 
+    tau_dev = None if frozen is None else torch.tensor([frozen[0]], dtype=torch.float64, device=device)   # f64 [1]: the tau in force
+    extra = None
+
+    def select(record, epoch):
+        """tau of this epoch's val scores (every rank holds all of them): val_tau / val_threshold into the record, the checkpoint's
+        `thresholds` / `threshold_records`; the tau stays on the device and is the next epoch's previous_tau."""
+        nonlocal tau_dev, extra
+        from . import metrics as MX
+        row = MX.select_threshold(MX.positive_probs(val_logits.to(device)), val_targets, policy, previous_tau=tau_dev, device=device)
+        try:
+            rec = MX.threshold_record(row[0], policy, f"{args.dataset_name}/val", epoch)
+        except ValueError as e:
+            raise SystemExit(f"--threshold_policy {policy} on {args.val_csv}: {e}")
+        tau_dev = row[:, 0].contiguous()
+        key = MX.format_threshold_key(args.dataset_name, "val", policy)
+        extra = {"thresholds": {key: rec["tau"]}, "threshold_records": {key: rec}}
+        record["val_threshold"] = rec
+        if rank == 0:
+            record.update(metric_records("val", val_logits, val_targets, splits["val"][2], device, args.metrics, tau=tau_dev))
+
     if "train" in loaders:
         for epoch in range(args.epochs):
             if isinstance(sampler, torch.utils.data.DistributedSampler):
@@ -198,24 +270,32 @@ def run(args):
             if "val" in loaders:
                 val_logits, val_targets, _ = evaluate_cls(model, loaders["val"], device, shard=False, return_probs=True)
                 record["val_loss"] = host_loss(val_logits, val_targets, pos_weight_host)
-                if args.metrics and rank == 0:
+                if selecting:
+                    select(record, epoch + 1)   # the record's epoch is the checkpoint's
+                elif args.metrics and rank == 0:
                     record.update(metric_records("val", val_logits, val_targets, splits["val"][2], device))
             log(record)
             save_cls_checkpoint(os.path.join(args.output_dir, "ckpts", f"finetune_e{epoch + 1}.pth"), epoch + 1, model, opt,
-                                loss=record.get("val_loss", stats.loss), pointer=os.path.join(args.output_dir, "ckpts", "last.pth"),
-                                loss_scaler=scaler)
+                                loss=record.get("val_loss", stats.loss), extra=extra,
+                                pointer=os.path.join(args.output_dir, "ckpts", "last.pth"), loss_scaler=scaler)
     elif "val" in loaders:
         val_logits, val_targets, _ = evaluate_cls(model, loaders["val"], device, shard=False, return_probs=True)
         record = {"val_loss": host_loss(val_logits, val_targets, pos_weight_host)}
-        if args.metrics and rank == 0:
+        if selecting:
+            select(record, 0)
+        elif args.metrics and rank == 0:
             record.update(metric_records("val", val_logits, val_targets, splits["val"][2], device))
         log(record)
     if "test" in loaders:
         test_logits, test_targets, _ = evaluate_cls(model, loaders["test"], device, shard=False, return_probs=True)
         record = {"test_loss": host_loss(test_logits, test_targets, pos_weight_host), "test_samples": int(test_logits.shape[0])}
-        if (args.metrics or args.bootstrap > 0) and rank == 0:
+        if (args.metrics or args.bootstrap > 0 or tau_dev is not None) and rank == 0:
             record.update(metric_records("test", test_logits, test_targets, splits["test"][2], device, args.metrics, args.bootstrap,
-                                         args.bootstrap_seed))
+                                         args.bootstrap_seed, tau=tau_dev))
+            if frozen is not None:   # where the tau comes from
+                record["test_threshold"] = {"policy": FROZEN_POLICY, "tau": frozen[0], "source_key": frozen[1],
+                                            "source_policy": frozen[2].get("policy"), "source_split": frozen[2].get("split"),
+                                            "source_checkpoint": str(args.threshold_from)}
         log(record)
     if world > 1:
         dist.destroy_process_group()

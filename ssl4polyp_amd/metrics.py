@@ -6,6 +6,10 @@ interval from a bootstrap that resamples whole clusters (cases) per label: class
 the clusters and the draws are made on the host exactly as the reference makes them (the same calls on a numpy Generator, so
 replicate r is the reference's replicate r) and every replicate is evaluated by one HIP launch sequence: a replicate is a weight
 per frame, nothing is gathered (DESIGN.md "Bootstrap intervals of the test metrics").  There is no host fallback.
+
+The threshold itself is chosen on the validation scores by the reference's policies (classification/metrics/thresholds.py), here by
+one launch over the same sorted order: select_threshold / threshold_record (pm_select_tau; DESIGN.md "Threshold selection on the
+device").
 """
 from __future__ import annotations
 
@@ -124,6 +128,82 @@ def binary_metrics(probs, labels, tau, device=None) -> dict:
     out = bootstrap_binary_metrics(probs, labels, tau, np.zeros(n, dtype=np.int32), np.zeros((1, 1), dtype=np.int32), n_clusters=1,
                                    device=device)
     return dict(zip(METRIC_KEYS, out[0, 0].tolist()))
+
+
+TAU_KEYS = ("tau", "n_candidates", "degenerate", "objective", "tp", "fp", "tn", "fn", "recall", "precision", "f1", "tpr", "fpr",
+            "youden_j", "n_unique", "index")   # the columns of pm_select_tau's `out`
+TAU_METRIC_KEYS = TAU_KEYS[4:14]                # thresholds._compute_metrics_for_tau
+POLICIES = {"f1_opt_on_val": 0, "youden_on_val": 1, "val_opt_youden": 2, "youden": 3}   # pm_select_tau's `policy`
+MAX_CANDIDATES = 200                            # thresholds._MAX_THRESHOLD_CANDIDATES
+
+
+def format_threshold_key(dataset: str, split: str, policy: str) -> str:
+    """thresholds.format_threshold_key: the name a threshold is kept under in a checkpoint."""
+    return f"{dataset.lower()}_{split.lower()}_{policy.lower()}"
+
+
+def select_threshold(probs, labels, policy, previous_tau=None, return_candidates=False, device=None):
+    """The decision threshold of every run under one of the reference's policies (POLICIES; classification/metrics/thresholds.py
+    compute_policy_threshold and compute_youden_j_threshold): f64 [M, 16] on the device in TAU_KEYS order, by one launch of
+    pm_select_tau after the sort.  Nothing is read back: `[:, 0]` goes to bootstrap_binary_metrics(tau=...) as it is.
+
+    probs [M, N] (or [N]): P(class 1) in [0, 1] as positive_probs returns it -- values outside [0, 1] or NaN are outside the
+    contract; labels [N] 0 / 1; previous_tau: None, a float or one per run (NaN = none), used only when the labels hold one class.
+    With return_candidates the result is (rows, candidates f64 [M, 200], NaN beyond the list).  A run with one class only has
+    degenerate = 1; for `youden` its tau is NaN and threshold_record raises the reference's error."""
+    name = str(policy).strip().lower()
+    if name not in POLICIES:
+        raise ValueError(f"Unsupported threshold policy '{policy}' (one of {', '.join(POLICIES)})")
+    if device is None:
+        device = probs.device if isinstance(probs, torch.Tensor) and probs.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = lambda x, dt: torch.as_tensor(x).to(device=device, dtype=dt).contiguous()
+    score = dev(probs, torch.float64)
+    if score.ndim == 1:
+        score = score[None]
+    M, N = score.shape
+    label = dev(labels, torch.uint8)
+    if label.shape != (N,):
+        raise ValueError(f"shapes: probs {tuple(score.shape)}, labels {tuple(label.shape)}")
+    if previous_tau is None:
+        prev = torch.full((M,), float("nan"), dtype=torch.float64, device=device)
+    else:
+        prev = dev(torch.full((M,), float(previous_tau), dtype=torch.float64) if np.ndim(previous_tau) == 0 else previous_tau, torch.float64)
+    if prev.shape != (M,):
+        raise ValueError(f"previous_tau: one value or one per run ({M}), got {tuple(prev.shape)}")
+    order = torch.sort(score, dim=1, descending=True, stable=True).indices.to(torch.int32).contiguous()
+    lib = _lib.load()
+    need = ctypes.c_size_t(0)
+    _lib.check(lib.pm_select_tau_workspace(N, M, ctypes.byref(need)), "pm_select_tau_workspace")
+    ws = torch.empty(need.value, dtype=torch.uint8, device=device)
+    out = torch.empty((M, len(TAU_KEYS)), dtype=torch.float64, device=device)
+    cand = torch.empty((M, MAX_CANDIDATES), dtype=torch.float64, device=device) if return_candidates else None
+    _lib.check(lib.pm_select_tau(score.data_ptr(), order.data_ptr(), label.data_ptr(), prev.data_ptr(), POLICIES[name], out.data_ptr(),
+                                 cand.data_ptr() if return_candidates else None, N, M, ws.data_ptr(), ws.numel(),
+                                 torch.cuda.current_stream(device).cuda_stream), "pm_select_tau")
+    return (out, cand) if return_candidates else out
+
+
+def threshold_record(row, policy, split_name, epoch, candidates=None) -> dict:
+    """One row of select_threshold as the reference's record (thresholds._build_policy_record, :275-296, plus `metrics` =
+    _compute_metrics_for_tau): policy, tau, split, n_candidates, tiebreakers, epoch, degenerate_val, notes, metrics.  With
+    `candidates` (that run's row of the candidate tensor) the list is added under `candidates`.  This reads the row back."""
+    name = str(policy).strip().lower()
+    if name not in POLICIES:
+        raise ValueError(f"Unsupported threshold policy '{policy}'")
+    v = dict(zip(TAU_KEYS, (row.detach().cpu() if isinstance(row, torch.Tensor) else np.asarray(row)).tolist()))
+    degenerate = bool(v["degenerate"])
+    if degenerate and name == "youden":
+        raise ValueError("Youden's J threshold requires both positive and negative samples")
+    notes = {}
+    if degenerate:   # thresholds.py:326-332; the row's index says which: -2 previous_tau carried forward, -1 the default
+        notes = {"carried_forward": True} if v["index"] == -2.0 else {"default_tau": 0.5}
+    record = {"policy": name, "tau": float(v["tau"]), "split": split_name, "n_candidates": int(v["n_candidates"]),
+              "tiebreakers": ["higher_recall", "lower_tau"], "epoch": int(epoch), "degenerate_val": degenerate, "notes": notes,
+              "metrics": {k: float(v[k]) for k in TAU_METRIC_KEYS}}
+    if candidates is not None:
+        c = np.asarray(candidates.detach().cpu() if isinstance(candidates, torch.Tensor) else candidates, dtype=np.float64)
+        record["candidates"] = c[~np.isnan(c)].tolist()
+    return record
 
 
 def positive_probs(logits: torch.Tensor) -> torch.Tensor:
