@@ -198,6 +198,60 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Column sums in two stages (bias, gamma, beta and mask-token gradients): a first-stage kernel leaves one partial row per
+// (column strip, row split) workgroup, reduce_partial_rows adds them up in a fixed order -- run-to-run deterministic.
+// ---------------------------------------------------------------------------------------------
+// Tail of a first-stage kernel of 4 waves x 64 lanes x 4 columns (blockIdx.x: 256-column strip, blockIdx.y: row split): the
+// waves' sums are combined as (w0 + w1) + (w2 + w3), then the workgroup stores its row of `partials` -- or, without one, adds
+// to `out` with one float atomic per column.
+__device__ __forceinline__ void block_colsum_tail(f32x4 acc, float* __restrict__ out, float* __restrict__ partials, int N) {
+  __shared__ float red[4][256];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) red[wave][lane * 4 + e] = acc[e];
+  __syncthreads();
+  const int t = threadIdx.x;
+  const int n = blockIdx.x * 256 + t;
+  if (n < N) {
+    const float s = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+    if (partials) partials[(long)blockIdx.y * N + n] = s;
+    else atomicAdd(out + n, s);
+  }
+}
+
+// dst[n] += sum over r < rows of partials[r * stride + v * N + n], where dst is dst0 / dst1 / dst2 for v = blockIdx.y (a NULL
+// destination is skipped).  64 columns per 1024-thread workgroup; each of the 16 waves sums every 16th partial row in order, U loads
+// in flight (strided_sum), then one sequential combine over the waves 0..15: the order of the additions is a function of `rows`
+// alone, whatever U is.  (Internal linkage, like every kernel here: each translation unit that launches it holds its own copy.)
+namespace {
+template <int U>
+__global__ __launch_bounds__(1024) void reduce_partial_rows(const float* __restrict__ partials, long stride, int rows, int N,
+                                                            float* dst0, float* dst1, float* dst2) {
+  __shared__ float red[16][64];
+  const int lane = threadIdx.x & 63, rg = threadIdx.x >> 6;
+  const int n = blockIdx.x * 64 + lane;
+  const int v = blockIdx.y;
+  float* dst = v == 0 ? dst0 : (v == 1 ? dst1 : dst2);
+  if (!dst) return;
+  red[rg][lane] = n < N ? strided_sum<U>(partials + (long)v * N + n, stride, rg, 16, rows) : 0.f;
+  __syncthreads();
+  if (rg == 0 && n < N) {
+    float t = 0.f;
+#pragma unroll
+    for (int g = 0; g < 16; ++g) t += red[g][lane];
+    dst[n] += t;
+  }
+}
+}  // namespace
+
+inline int cap_grid(long work_items, int per_block, int cap) {
+  long g = (work_items + per_block - 1) / per_block;
+  if (g < 1) g = 1;
+  if (g > cap) g = cap;
+  return (int)g;
+}
+
 // erf-GELU (timm Mlp act_layer=nn.GELU, exact erf form) and its derivative.
 // Phi(x) = 0.5 (1 + erf(x / sqrt 2)) with erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, i.e. f32
 // round-off level): one v_exp + one v_rcp + 6 FMAs instead of libm's branchy erff; the exponential

@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256, NV <= 3 ? 4 : 1) void ln_bwd_kernel(const TDy*
       float* dst = wave == 0 ? dgamma : (wave == 1 ? dbeta : dcolsum);
       if (dst) {
         const f32x4 t = (acc[wave][0][c] + acc[wave][1][c]) + (acc[wave][2][c] + acc[wave][3][c]);
-        if (partials) {  // two-stage: plain store of this block's partial row, summed by ln_bwd_reduce_kernel
+        if (partials) {  // two-stage: plain store of this block's partial row, summed by reduce_partial_rows
           *reinterpret_cast<f32x4*>(partials + ((long)blockIdx.x * 3 + wave) * D + 4 * c) = t;
         } else {         // no workspace: one atomic per column per block (contended when the grid is large)
 #pragma unroll
@@ -200,29 +200,6 @@ __global__ __launch_bounds__(256, NV <= 3 ? 4 : 1) void ln_bwd_kernel(const TDy*
         }
       }
     }
-  }
-}
-
-// dst_v[d] += sum over blocks of partials[b][v][d], fixed order (deterministic)
-__global__ __launch_bounds__(1024) void ln_bwd_reduce_kernel(const float* __restrict__ partials, float* dgamma, float* dbeta,
-                                                             float* dcolsum, int nblocks, int D) {
-  // 64 columns per block, 16 row groups (one per wave) each summing every 16th partial row with 4 independent
-  // accumulators; the order of additions is fixed by (nblocks) only -> run-to-run deterministic.
-  __shared__ float red[16][64];
-  const int lane = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const int d = blockIdx.x * 64 + lane;
-  const int v = blockIdx.y;
-  float* dst = v == 0 ? dgamma : (v == 1 ? dbeta : dcolsum);
-  if (!dst) return;
-  float s0 = 0.f;
-  if (d < D) s0 = strided_sum<16>(partials + (long)v * D + d, 3L * D, rg, 16, nblocks);
-  red[rg][lane] = s0;
-  __syncthreads();
-  if (rg == 0 && d < D) {
-    float t = 0.f;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) t += red[g][lane];
-    dst[d] += t;
   }
 }
 
@@ -264,7 +241,7 @@ extern "C" int pm_layernorm_bwd(const void* dy, int dy_dtype, const float* x, lo
     cap = kLnBwdBlocks;
   }
   // the parent kernel's grid and row assignment (wave gw of 4 * grid takes rows gw, gw + 4 * grid, ...): with the fixed order inside
-  // a wave, a workgroup and ln_bwd_reduce_kernel, the column sums come out bit for bit as before the rows went in flight
+  // a wave, a workgroup and reduce_partial_rows, the column sums come out bit for bit as before the rows went in flight
   const int grid = (M + 3) / 4 < cap ? (M + 3) / 4 : cap;
   hipStream_t s = pm_stream(stream);
   const int nv = (D + 255) / 256;  // f32x4 slots per lane: 3 for D = 768, 2 for 512
@@ -279,7 +256,7 @@ extern "C" int pm_layernorm_bwd(const void* dy, int dy_dtype, const float* x, lo
     else if (nv == 4) PM_LN_BWD(T, 4); else PM_LN_BWD(T, 5);
   });
 #undef PM_LN_BWD
-  if (partials)
-    hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((D + 63) / 64, 3), dim3(1024), 0, s, partials, dgamma, dbeta, dcolsum, grid, D);
+  if (partials)  // dst_v[d] += sum over blocks of partials[b][v][d]
+    hipLaunchKernelGGL(reduce_partial_rows<16>, dim3((D + 63) / 64, 3), dim3(1024), 0, s, partials, 3L * D, grid, D, dgamma, dbeta, dcolsum);
   return pm_check_launch();
 }

@@ -99,12 +99,10 @@ __global__ __launch_bounds__(256) void unshuffle_bwd_kernel(const float* __restr
 }
 
 // dmask_token[d] += sum over masked positions (j >= keep) of dout[b, 1 + ids_shuffle[b,j], d]
-// `partials` != NULL: block row blockIdx.y stores its sums there and mask_token_reduce_kernel adds the rows in a fixed
-// order (deterministic); NULL: one float atomic per column per block.
+// first stage (pm_common.h block_colsum_tail) over the masked positions
 __global__ __launch_bounds__(256) void mask_token_grad_kernel(const float* __restrict__ dout, const int* __restrict__ ids_shuffle,
                                                               float* __restrict__ dmask_token, float* __restrict__ partials,
                                                               int B, int L, int keep, int D) {
-  __shared__ float red[4][256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.x * 256 + lane * 4;
   const int nm = L - keep;
@@ -117,30 +115,7 @@ __global__ __launch_bounds__(256) void mask_token_grad_kernel(const float* __res
       acc += *reinterpret_cast<const f32x4*>(dout + ((long)b * (L + 1) + srow) * D + c);
     }
   }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) red[wave][lane * 4 + e] = acc[e];
-  __syncthreads();
-  const int t = threadIdx.x, cc = blockIdx.x * 256 + t;
-  if (cc < D) {
-    const float v = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-    if (partials) partials[(long)blockIdx.y * D + cc] = v;
-    else atomicAdd(dmask_token + cc, v);
-  }
-}
-
-__global__ __launch_bounds__(1024) void mask_token_reduce_kernel(const float* __restrict__ partials, float* __restrict__ out,
-                                                                 int rows, int D) {
-  __shared__ float red[16][64];
-  const int lane = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const int n = blockIdx.x * 64 + lane;
-  red[rg][lane] = n < D ? strided_sum<8>(partials + n, D, rg, 16, rows) : 0.f;
-  __syncthreads();
-  if (rg == 0 && n < D) {
-    float t = 0.f;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) t += red[g][lane];
-    out[n] += t;
-  }
+  block_colsum_tail(acc, dmask_token, partials, D);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -296,13 +271,6 @@ __global__ __launch_bounds__(256) void loss_bwd_kernel(const float* __restrict__
   }
 }
 
-inline int cap_grid(long work_items, int per_block, int cap) {
-  long g = (work_items + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (int)g;
-}
-
 }  // namespace
 
 extern "C" int pm_mae_noise(float* noise, long n, unsigned long long seed, unsigned int stream_id, void* stream) {
@@ -347,8 +315,8 @@ extern "C" int pm_mae_unshuffle_bwd(const float* dout, const int* ids_shuffle, v
     hipLaunchKernelGGL(mask_token_grad_kernel, dim3((D + 255) / 256, rows), dim3(256), 0, pm_stream(stream), dout, ids_shuffle,
                        dmask_token, partials, B, L, keep, D);
     if (partials)
-      hipLaunchKernelGGL(mask_token_reduce_kernel, dim3((D + 63) / 64), dim3(1024), 0, pm_stream(stream), partials, dmask_token,
-                         rows, D);
+      hipLaunchKernelGGL(reduce_partial_rows<8>, dim3((D + 63) / 64), dim3(1024), 0, pm_stream(stream), partials, (long)D, rows, D,
+                         dmask_token, (float*)nullptr, (float*)nullptr);
   }
   return pm_check_launch();
 }

@@ -9,44 +9,17 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // column sums: out[n] += sum_m x[m][n]   (bias gradients)
 // ---------------------------------------------------------------------------------------------
-// `partials` != NULL: each (column strip, row split) block stores its partial row [blockIdx.y][N]; colsum_reduce_kernel
-// then sums the splits in a fixed order (deterministic).  NULL: one float atomic per column per block.
+// first stage (pm_common.h block_colsum_tail): wave w of row split blockIdx.y takes rows 4 blockIdx.y + w, + 4 gridDim.y, ...
 template <typename T>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, long ldx, float* __restrict__ out,
                                                      float* __restrict__ partials, int M, int N) {
-  __shared__ float red[4][256];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = blockIdx.x * 256 + lane * 4;
   f32x4 acc = {0.f, 0.f, 0.f, 0.f};
   if (n < N) {
     for (long m = (long)blockIdx.y * 4 + wave; m < M; m += (long)gridDim.y * 4) acc += load4<T>(x + m * ldx + n);
   }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) red[wave][lane * 4 + e] = acc[e];
-  __syncthreads();
-  const int t = threadIdx.x;
-  const int nn = blockIdx.x * 256 + t;
-  if (nn < N) {
-    const float s = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
-    if (partials) partials[(long)blockIdx.y * N + nn] = s;
-    else atomicAdd(out + nn, s);
-  }
-}
-
-__global__ __launch_bounds__(1024) void colsum_reduce_kernel(const float* __restrict__ partials, float* __restrict__ out,
-                                                             int splits, int N) {
-  // 64 columns per block; the 16 waves each sum every 16th split (fixed order, 8 loads in flight), then one LDS combine
-  __shared__ float red[16][64];
-  const int lane = threadIdx.x & 63, rg = threadIdx.x >> 6;
-  const int n = blockIdx.x * 64 + lane;
-  red[rg][lane] = n < N ? strided_sum<8>(partials + n, N, rg, 16, splits) : 0.f;
-  __syncthreads();
-  if (rg == 0 && n < N) {
-    float t = 0.f;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) t += red[g][lane];
-    out[n] += t;
-  }
+  block_colsum_tail(acc, out, partials, N);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -393,14 +366,6 @@ __global__ void loss_scale_update_kernel(float* __restrict__ state, const float*
   }
 }
 
-inline int cap_grid(long work_items, int per_block, int cap) {
-  long g = (work_items + per_block - 1) / per_block;
-  if (g < 1) g = 1;
-  if (g > cap) g = cap;
-  return (int)g;
-}
-
-
 // ---------------------------------------------------------------------------------------------
 // Row gather / scatter for the classifier's top block (engine.py BlockStack.backward, sparse_top): with out_token "cls" the head's
 // backward leaves a gradient in ONE row per sample, and the MLP branch of the last block (dfc2 + dGELU, dfc1, LayerNorm backward,
@@ -439,7 +404,9 @@ extern "C" int pm_colsum_ws(const void* x, long ldx, int dtype, float* out, int 
   float* partials = (workspace && ws_bytes >= (size_t)splits * N * sizeof(float)) ? reinterpret_cast<float*>(workspace) : nullptr;
   hipStream_t s = pm_stream(stream);
   PM_DISPATCH_ACT(dtype, T, hipLaunchKernelGGL(colsum_kernel<T>, grid, dim3(256), 0, s, (const T*)x, ldx, out, partials, M, N));
-  if (partials) hipLaunchKernelGGL(colsum_reduce_kernel, dim3((N + 63) / 64), dim3(1024), 0, s, partials, out, splits, N);
+  if (partials)
+    hipLaunchKernelGGL(reduce_partial_rows<8>, dim3((N + 63) / 64), dim3(1024), 0, s, partials, (long)N, splits, N, out, (float*)nullptr,
+                       (float*)nullptr);
   return pm_check_launch();
 }
 

@@ -51,6 +51,40 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _stream_key(stream: Optional["torch.cuda.Stream"] = None) -> Tuple[int, int]:
+    """(device index, hipStream_t) of `stream`; by default of torch's current stream, the one a launch goes to."""
+    if stream is not None:
+        return stream.device.index, stream.cuda_stream
+    if _raw_stream is not None:
+        dev = _cur_device()
+        return dev, _raw_stream(dev)
+    st = torch.cuda.current_stream()
+    return st.device.index, st.cuda_stream
+
+
+class ScratchArena:
+    """One byte buffer per key that only ever grows.  The engine keys it by stream: kernels on one stream run one after the other,
+    and every launch that fills scratch is followed by the launch that reads it on the same stream inside the same C call, so one
+    buffer per stream is always enough -- and two streams never share one.  Growing a buffer (first step of a new shape) drains
+    the device first: a launch still in flight may be using the old one.  (Not while a graph is being captured: nothing executes
+    then, and a capture runs on a stream of its own, so its first step sizes that stream's buffer.)"""
+
+    FLOOR = 1 << 16
+
+    def __init__(self):
+        self.bufs: Dict[object, torch.Tensor] = {}
+        self.generation = 0   # bumped whenever a buffer is created or replaced: whoever keeps a pointer compares it
+
+    def get(self, key, nbytes: int, device) -> torch.Tensor:
+        buf = self.bufs.get(key)
+        if buf is None or buf.numel() < nbytes:
+            if buf is not None and buf.is_cuda and not torch.cuda.is_current_stream_capturing():
+                torch.cuda.synchronize(device)
+            buf = self.bufs[key] = torch.empty(max(nbytes, self.FLOOR), dtype=torch.uint8, device=device)
+            self.generation += 1
+        return buf
+
+
 _STREAMS: Dict[Tuple[int, str], "torch.cuda.Stream"] = {}
 # The second weight-gradient stream (busy in the backward only) IS the second forward chain's stream (busy in the forward only):
 # two engine streams + the main stream = three busy streams, each on a hardware queue of its own under the runtime's default of four,
@@ -120,7 +154,7 @@ class Kernels:
         self._need_cache: Dict[tuple, object] = {}      # what the library answered per shape: workspace bytes, grouping plans
         self._opts_cache: Optional[tuple] = None        # ((WGRAD_BLOCKS, gemm_variant), weight-gradient pm_gemm_opts, the others')
         self._side = self._side2 = None                 # the two weight-gradient streams, once a backward has asked for them
-        self._scratch_bufs: Dict[str, torch.Tensor] = {}  # "_ws", "_ws_front", "_ws_group", "_ws_ln", "_ws_cs_main", "_ws_cs_side"
+        self._arena = ScratchArena()                    # split-K slabs and partial rows: one buffer per (device, stream)
 
     # -- helpers ------------------------------------------------------------------------------
     def layernorm_fwd(self, x, gamma, beta, y, mean, rstd, M, D):
@@ -128,29 +162,36 @@ class Kernels:
                                              _ptr(mean), _ptr(rstd), M, D, self.eps, _stream()), "pm_layernorm_fwd")
 
     def layernorm_bwd(self, dy, x, gamma, mean, rstd, dres, dx, dx_act, dgamma, dbeta, dcolsum, M, D):
-        ws = self._scratch("_ws_ln", self._need(("ln", M, D), lambda: self.lib.pm_workspace_bytes(_lib.WS_LAYERNORM_BWD, M, D)),
-                           x.device)
+        need = self._ln_bwd_bytes(M, D)
+        ws = self._scratch(need, x.device)
         _lib.check(self.lib.pm_layernorm_bwd(_ptr(dy), _lib.dtype_code(dy.dtype), _ptr(x), D, _ptr(gamma), _ptr(mean),
                                              _ptr(rstd), _ptr(dres), D, _ptr(dx), D, _ptr(dx_act), self.act,
-                                             _ptr(dgamma), _ptr(dbeta), _ptr(dcolsum), M, D, _ptr(ws), ws.numel(), _stream()),
+                                             _ptr(dgamma), _ptr(dbeta), _ptr(dcolsum), M, D, _ptr(ws), need, _stream()),
                    "pm_layernorm_bwd")
 
-    # -- scratch buffers: sized by the library's own queries (pm_gemm_workspace_bytes / pm_workspace_bytes), cached per
-    #    shape; a buffer only ever grows, and growing it (first step of a new shape) drains the device first because the
-    #    side stream may still be using the old one
+    # -- scratch: sized by the library's own queries (pm_gemm_workspace_bytes / pm_workspace_bytes, cached per shape), taken
+    #    from the arena of the stream the launch goes to; the library is told the size it asked for, not the arena's
     def _need(self, key, query) -> int:
         n = self._need_cache.get(key)
         if n is None:
             n = self._need_cache[key] = int(query())
         return n
 
-    def _scratch(self, name: str, nbytes: int, device) -> torch.Tensor:
-        ws = self._scratch_bufs.get(name)
-        if ws is None or ws.device != device or ws.numel() < nbytes:
-            if ws is not None and ws.device == device:
-                torch.cuda.synchronize(device)
-            ws = self._scratch_bufs[name] = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, device=device)
-        return ws
+    def _ln_bwd_bytes(self, M: int, D: int) -> int:
+        return self._need(("ln", M, D), lambda: self.lib.pm_workspace_bytes(_lib.WS_LAYERNORM_BWD, M, D))
+
+    def _scratch(self, nbytes: int, device, stream: Optional["torch.cuda.Stream"] = None) -> torch.Tensor:
+        """At least `nbytes` of the scratch of `stream` (default: the current one, where the launch goes)."""
+        return self._arena.get(_stream_key(stream), nbytes, device)
+
+    @staticmethod
+    def _shape_items(dims):
+        """The pm_wgrad_item array of (n_out, n_in[, has dbias]) gradients for the library's plan and workspace queries: shapes
+        only, every pointer a stand-in that passes the alignment checks."""
+        arr = (_lib.WgradItem * len(dims))()
+        for j, (o, i, *bias) in enumerate(dims):
+            arr[j] = _lib.WgradItem(64, o, 64, i, 64, i, o, i, 0, 64 if bias and bias[0] else None)
+        return arr
 
     # The side streams are shared by every Kernels object of the process (one set per device): the HIP runtime multiplexes
     # streams onto a handful of hardware queues (GPU_MAX_HW_QUEUES, 4 by default), and two streams on one queue run their
@@ -179,20 +220,22 @@ class Kernels:
             o = self._opts_cache = (key, _lib.GemmOpts(self.WGRAD_BLOCKS, self.gemm_variant), _lib.GemmOpts(0, self.gemm_variant))
         return o[1] if wgrad else o[2]
 
-    def gemm(self, A, lda, a_kmajor, B, ldb, b_kmajor, bias, C, ldc, epilogue, M, N, K, aux=None, resid=None, ws_name="_ws"):
+    def gemm(self, A, lda, a_kmajor, B, ldb, b_kmajor, bias, C, ldc, epilogue, M, N, K, aux=None, resid=None):
         in_dtype = _lib.dtype_code(A.dtype)
         if _lib.dtype_code(B.dtype) != in_dtype:
             raise _lib.PolypMaeError("pm_gemm: operand dtypes differ")
         wgrad = bool(a_kmajor and b_kmajor)
         opts = self._opts(wgrad)
-        ws = None
+        ws, need = None, 0
         if wgrad:
+            # a weight gradient always gets a workspace pointer, with 0 bytes where no split fits: that the caller HAS one is what
+            # sends a long reduction to the weight-gradient ring kernel (plan_gemm: `splittable`), whatever the split count
             need = self._need(("gemm", in_dtype, M, N, K, opts.max_blocks, opts.variant),
                               lambda: self.lib.pm_gemm_workspace_bytes(1, 1, in_dtype, M, N, K, ctypes.byref(opts)))
-            ws = self._scratch(ws_name, need, A.device)
+            ws = self._scratch(need, A.device)
         _lib.check(self.lib.pm_gemm_ex(_ptr(A), lda, int(a_kmajor), _ptr(B), ldb, int(b_kmajor), in_dtype, _ptr(bias),
                                        _ptr(C), ldc, _lib.dtype_code(C.dtype), epilogue, _ptr(aux), _ptr(resid), M, N, K,
-                                       _ptr(ws), ws.numel() if ws is not None else 0, ctypes.byref(opts), _stream()), "pm_gemm")
+                                       _ptr(ws), need, ctypes.byref(opts), _stream()), "pm_gemm")
 
     def linear_fwd(self, x, W, bias, out, M, N, K, epilogue=EPI_STORE, aux=None, resid=None):
         """out[M,N] = x[M,K] @ W[N,K]^T + bias  (nn.Linear forward)."""
@@ -216,9 +259,9 @@ class Kernels:
         dt = _lib.dtype_code(items[0][0].dtype)
         key = ("group", K, dt, tuple((tuple(it[2].shape), len(it) > 4 and it[4] is not None) for it in items))
         need = 0 if whole_k else self._need(key, lambda: self.lib.pm_wgrad_group_workspace_bytes(arr, n, K, dt))
-        ws = self._scratch("_ws_group", need, items[0][0].device) if need else None
+        ws = self._scratch(need, items[0][0].device) if need else None
         blocks = _lib.PM_GROUP_WHOLE_K if whole_k else (self.GROUP_BLOCKS_SLICED if need else self.GROUP_BLOCKS)
-        st = self.lib.pm_wgrad_group(arr, n, K, dt, blocks, _ptr(ws), ws.numel() if ws is not None else 0, _stream())
+        st = self.lib.pm_wgrad_group(arr, n, K, dt, blocks, _ptr(ws), need, _stream())
         if st == _lib.PM_ESHAPE:
             return False
         _lib.check(st, "pm_wgrad_group")
@@ -233,12 +276,8 @@ class Kernels:
         hit = cache.get(key)
         if hit is not None:
             return hit
-        n = len(dims)
-        arr = (_lib.WgradItem * n)()
-        for j, (o, i) in enumerate(dims):
-            arr[j] = _lib.WgradItem(64, o, 64, i, 64, i, o, i, 0, None)  # (shapes only: the pointers are checked for alignment)
         tiles, slices = ctypes.c_int(0), ctypes.c_int(0)
-        st = self.lib.pm_wgrad_group_plan(arr, n, K, self.act, None, ctypes.byref(tiles), ctypes.byref(slices))
+        st = self.lib.pm_wgrad_group_plan(self._shape_items(dims), len(dims), K, self.act, None, ctypes.byref(tiles), ctypes.byref(slices))
         # >= 64 tiles of 256x256 (ViT-B block: 108): one full-K tile per workgroup.  Fewer (the 512-wide MAE decoder block:
         # 48) group as well when the library's plan cuts every tile into k-slices (48 tiles x 4 slices of >= 128 k-steps);
         # otherwise the gradients keep the per-GEMM split-K path (PM_GROUP_MIN_TILES=0 forces grouping: whole-K 256x128 tiles).
@@ -258,31 +297,22 @@ class Kernels:
         if hit is None:
             ok = True
             for first, part in ((True, dims[:2]), (False, dims[2:])):
-                arr = (_lib.WgradItem * 2)()
-                for j, (o, i) in enumerate(part):
-                    arr[j] = _lib.WgradItem(64, o, 64, i, 64, i, o, i, 0, None)
                 slices = ctypes.c_int(0)
-                st = self.lib.pm_wgrad_group_plan(arr, 2, K, self.act, None, None, ctypes.byref(slices))
+                st = self.lib.pm_wgrad_group_plan(self._shape_items(part), 2, K, self.act, None, None, ctypes.byref(slices))
                 ok = ok and st == 0 and (slices.value == 1 or not first)
             hit = cache[key] = ok
         return hit
 
-    def linear_wgrad(self, dy, x, dW, M, N_out, K_in, accumulate, ws_name="_ws"):
-        """dW[N_out,K_in] (+)= dy[M,N_out]^T @ x[M,K_in]  (both operands k-major, f32 output).  ws_name: the split-K slab
-        scratch -- "_ws" belongs to the weight-gradient side stream; a launch on another stream that may run beside it names
-        its own."""
-        self.gemm(dy, N_out, 1, x, K_in, 1, None, dW, K_in, EPI_ACCUM if accumulate else EPI_STORE, N_out, K_in, M, ws_name=ws_name)
-
-    def _colsum_workspace(self, device, M: int, N: int):
-        # partial rows: one scratch per stream (main / wgrad side stream) so concurrent column sums never share it
-        on_side = self._side is not None and torch.cuda.current_stream() == self._side
-        need = self._need(("cs", M, N), lambda: self.lib.pm_workspace_bytes(_lib.WS_COLSUM, M, N))
-        return self._scratch("_ws_cs_side" if on_side else "_ws_cs_main", need, device)
+    def linear_wgrad(self, dy, x, dW, M, N_out, K_in, accumulate):
+        """dW[N_out,K_in] (+)= dy[M,N_out]^T @ x[M,K_in]  (both operands k-major, f32 output; split-K slabs in the current
+        stream's scratch)."""
+        self.gemm(dy, N_out, 1, x, K_in, 1, None, dW, K_in, EPI_ACCUM if accumulate else EPI_STORE, N_out, K_in, M)
 
     def colsum(self, x, out, M, N):
-        ws = self._colsum_workspace(x.device, M, N)
-        _lib.check(self.lib.pm_colsum_ws(_ptr(x), N, _lib.dtype_code(x.dtype), _ptr(out), M, N, _ptr(ws), ws.numel(),
-                                         _stream()), "pm_colsum")
+        need = self._need(("cs", M, N), lambda: self.lib.pm_workspace_bytes(_lib.WS_COLSUM, M, N))
+        ws = self._scratch(need, x.device)
+        _lib.check(self.lib.pm_colsum_ws(_ptr(x), N, _lib.dtype_code(x.dtype), _ptr(out), M, N, _ptr(ws), need, _stream()),
+                   "pm_colsum")
 
     def attention_fwd(self, qkv, out, lse, B, N, H, dh):
         _lib.check(self.lib.pm_attention_fwd(_ptr(qkv), _ptr(out), _ptr(lse), B, N, H, dh, self.act, _stream()),
@@ -294,11 +324,11 @@ class Kernels:
 
     def mae_unshuffle_bwd(self, dx, ids_shuffle, demb, dmask_token, B, L, keep, D):
         """Backward of pm_mae_unshuffle: dx f32 [B (L + 1), D] -> demb act [B (keep + 1), D], the masked rows summed into dmask_token
-        (f32 [D], += ; None: frozen) in a fixed order through partial rows in the main stream's column-sum scratch."""
-        ws = self._scratch("_ws_cs_main", self._need(("unshuf", D), lambda: self.lib.pm_workspace_bytes(_lib.WS_UNSHUFFLE_BWD, 1, D)),
-                           dx.device)
+        (f32 [D], += ; None: frozen) in a fixed order through partial rows."""
+        need = self._need(("unshuf", D), lambda: self.lib.pm_workspace_bytes(_lib.WS_UNSHUFFLE_BWD, 1, D))
+        ws = self._scratch(need, dx.device)
         _lib.check(self.lib.pm_mae_unshuffle_bwd(_ptr(dx), _ptr(ids_shuffle), _ptr(demb), self.act, _ptr(dmask_token), B, L, keep, D,
-                                                 _ptr(ws), ws.numel(), _stream()), "pm_mae_unshuffle_bwd")
+                                                 _ptr(ws), need, _stream()), "pm_mae_unshuffle_bwd")
 
     def gather_rows(self, src: torch.Tensor, idx: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """dst[r] = src[idx[r]] for a 2-D (or 1-D) contiguous src; idx int32 on the device; out: a contiguous [R, width] destination."""
@@ -564,17 +594,21 @@ class BlockStack:
             v(p["attn.qkv.bias"]), v(p["attn.proj.bias"]), v(p["mlp.fc1.bias"]), v(p["mlp.fc2.bias"]),
             (b1 - b0) * N, b1 - b0, N, D, Hd, g.heads, k.act, k.gemm_variant, k.eps)
 
-    def _bwd_desc(self, ws, bw, p, gr, xin, dx, dx_act, dmid, dmid_act, din, din_act, d_hidden, d_qkv, below_bias, acc, side, main):
-        """(pm_block_bwd_desc, done event, objects to keep alive) of one block: the events are created once and reused."""
+    def _block_scratch_bytes(self, M: int) -> Tuple[int, int]:
+        """What pm_vit_block_bwd takes scratch for: the LayerNorm partial rows (main stream) and the slabs of a k-sliced grouped
+        weight gradient (side stream; 0 when the library does not slice the group)."""
+        k, D, Hd = self.k, self.g.dim, self.g.hidden
+        return k._ln_bwd_bytes(M, D), k._need(("groupws", M, k.act, D, Hd), lambda: k.lib.pm_wgrad_group_workspace_bytes(
+            k._shape_items(((D, Hd, False), (Hd, D, True), (D, D, False), (3 * D, D, True))), 4, M, k.act))
+
+    def _bwd_desc(self, ws, bw, p, gr, xin, dx, dx_act, dmid, dmid_act, din, din_act, d_hidden, d_qkv, below_bias, acc, side, main,
+                  ws_ln, ws_group):
+        """(pm_block_bwd_desc, done event, objects to keep alive) of one block: the events are created once and reused.  ws_ln /
+        ws_group: the main / side stream's scratch (ws_group None: the group is not k-sliced)."""
         k, g = self.k, self.g
         M, D, Hd = ws.M, g.dim, g.hidden
         v = lambda t: t.data_ptr() if t is not None else None
-        ws_ln = k._scratch("_ws_ln", k._need(("ln", M, D), lambda: k.lib.pm_workspace_bytes(_lib.WS_LAYERNORM_BWD, M, D)), dx.device)
-        items = (_lib.WgradItem * 4)()
-        for j, (n_out, n_in, bias) in enumerate(((D, Hd, False), (Hd, D, True), (D, D, False), (3 * D, D, True))):
-            items[j] = _lib.WgradItem(64, n_out, 64, n_in, 64, n_in, n_out, n_in, 0, 64 if bias else None)  # (sizes only)
-        need = k._need(("groupws", M, k.act, D, Hd), lambda: k.lib.pm_wgrad_group_workspace_bytes(items, 4, M, k.act))
-        ws_group = k._scratch("_ws_group", need, dx.device) if need else None
+        need_ln, need = self._block_scratch_bytes(M)
         mk = lambda: torch.cuda.Event(enable_timing=bool(k.TIME_BLOCK_EVENTS))
         ev_fork, ev_done = mk(), mk()
         ev_fork.record(main)   # (materialises the hipEvent_t handles; re-recorded by every call)
@@ -594,7 +628,7 @@ class BlockStack:
             v(gr["norm1.weight"]), v(gr["norm1.bias"]), v(gr["norm2.weight"]), v(gr["norm2.bias"]), v(gr["attn.qkv.weight"]),
             v(gr["attn.proj.weight"]), v(gr["mlp.fc1.weight"]), v(gr["mlp.fc2.weight"]), v(gr["attn.qkv.bias"]),
             v(gr["attn.proj.bias"]), v(gr["mlp.fc1.bias"]), v(below_bias),
-            v(ws_ln), ws_ln.numel(), v(ws_group), ws_group.numel() if ws_group is not None else 0,
+            v(ws_ln), need_ln, v(ws_group), need,
             side.cuda_stream, None, ev_fork.cuda_event, ev_done.cuda_event,
             ws.B, ws.N, D, Hd, g.heads, k.act, k.gemm_variant, k.GROUP_BLOCKS_SLICED if need else k.GROUP_BLOCKS, acc,
             int(two), side2.cuda_stream if two else None, ev_fork2.cuda_event if two else None, ev_done2.cuda_event if two else None)
@@ -633,6 +667,8 @@ class BlockStack:
         dims = ((D, Hd), (Hd, D), (D, D), (3 * D, D))  # (n_out, n_in) of fc2, fc1, proj, qkv
         bcache = ws._bwd_descs
         ptr_of = lambda t: t.data_ptr() if t is not None else 0
+        if fast:  # what a block call takes scratch for, from the arenas of the stream each launch goes to
+            arena, main_key, (need_ln, need_group) = k._arena, _stream_key(main), self._block_scratch_bytes(M)
         for i in reversed(range(g.depth)):
             if i < lowest and not need_input_grad:
                 join(0)
@@ -674,14 +710,16 @@ class BlockStack:
                 # descriptor built once per block and kept (every buffer it names is persistent)
                 acc = (int(accumulate("attn.qkv.weight", i)) | int(accumulate("attn.proj.weight", i)) << 1 |
                        int(accumulate("mlp.fc1.weight", i)) << 2 | int(accumulate("mlp.fc2.weight", i)) << 3)
+                ws_ln = arena.get(main_key, need_ln, main.device)
+                ws_group = arena.get(_stream_key(side), need_group, main.device) if need_group else None
                 key = (dx.data_ptr(), dx_act.data_ptr(), xin.data_ptr(), gr["attn.qkv.weight"].data_ptr(),
                        p["attn.qkv.weight"].data_ptr(), gr["norm1.weight"].data_ptr(),
                        below_bias.data_ptr() if below_bias is not None else 0, acc, k.gemm_variant, k.GROUP_BLOCKS, k.GROUP_BLOCKS_SLICED, k.TWO_GROUPS, k.TIME_BLOCK_EVENTS,
-                       ptr_of(k._scratch_bufs.get("_ws_ln")), ptr_of(k._scratch_bufs.get("_ws_group")))  # (scratch is replaced when it grows)
+                       ws_ln.data_ptr(), ptr_of(ws_group))  # (scratch is replaced when it grows)
                 ent = bcache.get(i)
                 if ent is None or ent[0] != key:
                     ent = bcache[i] = (key,) + self._bwd_desc(ws, bw, p, gr, xin, dx, dx_act, dmid, dmid_act, din, din_act,
-                                                              d_hidden, d_qkv, below_bias, acc, side, main)
+                                                              d_hidden, d_qkv, below_bias, acc, side, main, ws_ln, ws_group)
                 _, desc, evs_done, keep = ent
                 _lib.check(k.lib.pm_vit_block_bwd(ctypes.byref(desc), _stream()), "pm_vit_block_bwd")
                 pending[i] = evs_done
@@ -769,7 +807,7 @@ class BlockStack:
         """The dgrad chain of a block's MLP branch over M rows, dense or compact: dfc2 + dGELU (dy_act -> d_hidden), dfc1 (-> d_ln),
         LayerNorm2' (+ the residual gradient dy -> dmid f32, dmid_act).  gr: the block's gradient tensors, None when it is frozen
         (LayerNorm2' then leaves out d gamma, d beta and the proj bias gradient it carries).  behind_dfc2(): the caller's weight
-        gradients that read d_hidden, enqueued between dfc2 and dfc1 -- on which stream and through which scratch is its business."""
+        gradients that read d_hidden, enqueued between dfc2 and dfc1 -- on which stream is its business."""
         k, D, Hd = self.k, self.g.dim, self.g.hidden
         k.linear_dgrad(dy_act, p["mlp.fc2.weight"], d_hidden, M, D, Hd, EPI_DGELU, aux=h_pre)
         if behind_dfc2 is not None:
@@ -808,15 +846,15 @@ class BlockStack:
         d_hidden_c, d_ln_c, dmid_c, dmid_act_c, d_attn_c = e(R, Hd), e(R, D), e(R, D, dt=torch.float32), e(R, D), e(R, D)
 
         def wgrad_behind_dfc2():
-            k.linear_wgrad(dxac, tc["h_act"], gr["mlp.fc2.weight"], R, D, Hd, acc("mlp.fc2.weight"), ws_name="_ws_front")
-            k.linear_wgrad(d_hidden_c, tc["ln2"], gr["mlp.fc1.weight"], R, Hd, D, acc("mlp.fc1.weight"), ws_name="_ws_front")
+            k.linear_wgrad(dxac, tc["h_act"], gr["mlp.fc2.weight"], R, D, Hd, acc("mlp.fc2.weight"))
+            k.linear_wgrad(d_hidden_c, tc["ln2"], gr["mlp.fc1.weight"], R, Hd, D, acc("mlp.fc1.weight"))
             k.colsum(d_hidden_c, gr["mlp.fc1.bias"], R, Hd)
 
         self._mlp_dgrad(p, gr if tr else None, R, dxc, dxac, tc["h_pre"], d_hidden_c, d_ln_c, tc["x_mid"], tc["mean2"], tc["rstd2"],
                         dmid_c, dmid_act_c, wgrad_behind_dfc2 if tr else None)
         # ---- proj on the live rows, then dense again for the attention backward
         if tr:
-            k.linear_wgrad(dmid_act_c, tc["attn"], gr["attn.proj.weight"], R, D, D, acc("attn.proj.weight"), ws_name="_ws_front")
+            k.linear_wgrad(dmid_act_c, tc["attn"], gr["attn.proj.weight"], R, D, D, acc("attn.proj.weight"))
         k.linear_dgrad(dmid_act_c, p["attn.proj.weight"], d_attn_c, R, D, D)
         k.scatter_rows_zero(dmid_c, tc["inv"], dmid.view(M, D))
         k.scatter_rows_zero(d_attn_c, tc["inv"], ws.d_attn.view(M, D))

@@ -243,16 +243,16 @@ def _padded_operand(rt: "_Runtime", name: str, shape, padded) -> torch.Tensor:
     return rt.k.pad_cast(rt.flat.param_view(name).view(*shape), *padded)
 
 
-def _padded_wgrad(rt: "_Runtime", dy, x, name: str, shape, padded, M: int, accumulate: bool, ws_name: str = "_ws") -> None:
+def _padded_wgrad(rt: "_Runtime", dy, x, name: str, shape, padded, M: int, accumulate: bool) -> None:
     """d W of Linear `name` (+)= dy[M, out]^T x[M, in]: straight into the flat gradient when nothing is padded, else through a
     temporary in the padded layout whose valid part pm_unpad_add moves (or adds) there."""
     k = rt.k
     dw = rt.flat.grad_view(name).view(*shape)
     if padded == shape:
-        k.linear_wgrad(dy, x, dw, M, shape[0], shape[1], accumulate, ws_name=ws_name)
+        k.linear_wgrad(dy, x, dw, M, shape[0], shape[1], accumulate)
     else:
         tmp = torch.empty(*padded, dtype=torch.float32, device=dy.device)
-        k.linear_wgrad(dy, x, tmp, M, padded[0], padded[1], False, ws_name=ws_name)
+        k.linear_wgrad(dy, x, tmp, M, padded[0], padded[1], False)
         k.unpad_add(tmp, dw, accumulate)
 
 
@@ -317,8 +317,8 @@ class _EncoderFrontMixin:
             _lib.check(k.lib.pm_assemble_tokens_bwd(_ptr(dx0), _ptr(ids_keep), _ptr(demb), k.act, _ptr(dcls), _ptr(dpos), B,
                                                     keep, D, _stream()), "pm_assemble_tokens_bwd")
         if need("patch_embed.proj.weight"):
-            # (its own split-K scratch: the last blocks' weight gradients may still be running on the side stream)
-            _padded_wgrad(rt, demb, cols, "patch_embed.proj.weight", (D, PE), (D, PEp), B * keep, accumulate, ws_name="_ws_front")
+            # (the last blocks' weight gradients may still be running on the side stream: scratch is per stream)
+            _padded_wgrad(rt, demb, cols, "patch_embed.proj.weight", (D, PE), (D, PEp), B * keep, accumulate)
         if need("patch_embed.proj.bias"):
             k.colsum(demb, f.grad_view("patch_embed.proj.bias"), B * keep, D)
 

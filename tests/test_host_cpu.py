@@ -366,3 +366,23 @@ def test_stack_workspace_declares_its_state():
     ws = StackWorkspace(StackGeom(64, 2, 2, 256), 2, 5, torch.float32, torch.device("cpu"), True)
     assert ws._fwd_descs == {} and ws._bwd_descs == {} and ws._top_c is None and ws._deferred_join == [] and ws.cls_top is False
     assert {"_fwd_descs", "_bwd_descs", "_top_c", "_deferred_join", "cls_top"} <= set(vars(ws))
+
+
+def test_scratch_arena_grows_per_key_and_never_shrinks():
+    """engine.ScratchArena, as Kernels keys it by stream: distinct keys get distinct buffers, a smaller request returns the same
+    buffer, a larger one a larger buffer and a new generation, nothing shrinks, and no buffer is below 64 KiB."""
+    from ssl4polyp_amd.engine import ScratchArena
+    a, cpu = ScratchArena(), torch.device("cpu")
+    assert a.generation == 0
+    b1, b2 = a.get(1, 100, cpu), a.get(2, 100, cpu)
+    assert b1.data_ptr() != b2.data_ptr() and b1.dtype == torch.uint8
+    assert b1.numel() == b2.numel() == 1 << 16 == ScratchArena.FLOOR and a.generation == 2
+    assert a.get(1, 0, cpu) is b1 and a.get(1, 1 << 16, cpu) is b1 and a.get(2, 7, cpu) is b2 and a.generation == 2
+    big = a.get(1, (1 << 16) + 1, cpu)
+    assert big is not b1 and big.numel() >= (1 << 16) + 1 and a.generation == 3
+    assert a.get(1, 5, cpu) is big and a.get(1, 1 << 16, cpu) is big and a.generation == 3   # nothing ever shrinks
+    assert a.get(2, 100, cpu) is b2                                                          # and key 2 was left alone
+    sizes = []
+    for n in (10, 1 << 20, 3, 1 << 18, (1 << 20) + 8):
+        sizes.append(a.get(3, n, cpu).numel())
+    assert sizes == sorted(sizes) and sizes[0] == 1 << 16 and sizes[-1] >= (1 << 20) + 8 and a.generation == 6

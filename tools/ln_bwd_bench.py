@@ -1,4 +1,4 @@
-"""Stand-alone time of pm_layernorm_bwd (ln_bwd_kernel + ln_bwd_reduce_kernel) with HIP events, optionally beside a parent build.
+"""Stand-alone time of pm_layernorm_bwd (ln_bwd_kernel + its reduce launch) with HIP events, optionally beside a parent build.
 
     python tools/ln_bwd_bench.py [--parent DIR] [--shapes M,D ...] [--precision bf16] [--calls 20] [--windows 5]
 
