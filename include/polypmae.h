@@ -567,6 +567,30 @@ int pm_adamw_tick(float* hyper, int n_groups, void* stream);
 int pm_adamw_dev(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, long n,
                  const float* hyper, void* stream);
 
+/* The whole update of a step as ONE call, for an update that runs on a side stream beside the next forward:
+ *   [wait for `wait_event` ->] pm_adamw_tick(hyper, n_groups) -> per segment: the pm_adamw_dev update [-> record done_event]
+ * all on `stream`.  A segment is one pm_adamw_dev argument list (its `hyper` points at the record of its group inside the
+ * `hyper` array) plus an optional hipEvent_t of the caller that is recorded behind its launch, so that a consumer on another
+ * stream can wait for exactly the ranges it reads.  max_blocks bounds the workgroups of every launch (pm_adamw_grid): 0 = the
+ * full grid of pm_adamw_dev.  The results do not depend on it: every element is updated by the same expression whatever the
+ * grid.  Every argument is checked before the first enqueue (PM_EINVAL: a NULL pointer or an unknown shadow dtype; PM_ESHAPE:
+ * no segments, n <= 0, n % 4 != 0, max_blocks < 0), so a refusal leaves the stream untouched. */
+typedef struct pm_adamw_segment {
+  float* p;
+  const float* g;
+  float *m, *v;
+  void* shadow;        /* optional act-typed copy of p, refreshed by the same launch */
+  int shadow_dtype;
+  long n;
+  const float* hyper;  /* this segment's 16-float record */
+  void* done_event;    /* optional hipEvent_t */
+} pm_adamw_segment;
+int pm_adamw_segments(const pm_adamw_segment* segs, int n_segs, float* hyper, int n_groups, void* wait_event, void* stream,
+                      int max_blocks);
+/* Workgroups one update launch over n elements uses under the bound max_blocks (host arithmetic only; PM_ESHAPE for n <= 0,
+ * n % 4 != 0 or max_blocks < 0). */
+int pm_adamw_grid(long n, int max_blocks);
+
 /* Dynamic loss scaling of precision mode fp16, on the device: GradScaler.step() + update() of the reference's AMP loop
  * (train_classification.py:4533-4546; engine_pretrain.py:65-72 via mae/util/misc.py:252-282) without the host read-back.
  * state: f32[8] = [0] scale [1] growth tracker [2] found_inf of the last step [3] skipped steps [4] steps [5] 1/scale used.

@@ -79,6 +79,8 @@ SIGNATURES = {
     "pm_adamw": [P, P, P, P, P, I, L, F, F, F, F, F, I, F, P],
     "pm_adamw_tick": [P, I, P],
     "pm_adamw_dev": [P, P, P, P, P, I, L, P, P],
+    "pm_adamw_segments": [P, I, P, I, P, P, I],
+    "pm_adamw_grid": [L, I],
     "pm_grad_stats": [P, L, P, P],
     "pm_loss_scale_update": [P, P, P, I, F, F, I, P],
     "pm_dgelu": [P, P, P, I, L, P],
@@ -121,6 +123,12 @@ class WgradItem(ctypes.Structure):
     """pm_wgrad_item of include/polypmae.h."""
     _fields_ = [("dY", c_void_p), ("lddy", c_long), ("X", c_void_p), ("ldx", c_long), ("dW", c_void_p), ("lddw", c_long),
                 ("n_out", c_int), ("n_in", c_int), ("accumulate", c_int), ("dbias", c_void_p)]
+
+
+class AdamwSegment(ctypes.Structure):
+    """pm_adamw_segment of include/polypmae.h."""
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("shadow", c_void_p), ("shadow_dtype", c_int),
+                ("n", c_long), ("hyper", c_void_p), ("done_event", c_void_p)]
 
 
 class BlockBwdDesc(ctypes.Structure):

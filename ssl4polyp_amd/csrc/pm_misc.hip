@@ -262,33 +262,75 @@ __global__ void adamw_tick_kernel(float* __restrict__ hyper, int n_groups) {
   h[8] = (float)(1.0 / sqrt(1.0 - pow((double)h[2], (double)step)));
 }
 
+// The device-hyper-parameter update as a streaming kernel whose footprint the caller bounds (pm_adamw_grid): a workgroup walks
+// chunks of kAdamwUnroll x 256 vectors, and a whole chunk is written as all of a lane's loads of p, g, m, v (64 VGPRs of payload)
+// followed by the arithmetic and the stores, so that a grid of a few hundred workgroups keeps the ~10 MB in flight that HBM rate
+// needs (256 workgroups run the ViT-B update as fast as 4096; 128 do not).  The compiler's own order -- the first vector's loads and
+// stores, then the other thirteen loads in flight over the rest -- is left alone: fenced into sixteen loads up front the step was
+// slower (docs/EXPERIMENT_LOG.md, "AdamW footprint").  There are no cross-element sums: every output is the per-element
+// expression of adamw_kernel above, whatever the map.
+constexpr int kAdamwUnroll = 4;
+constexpr int kAdamwChunk = kAdamwUnroll * 256;  // vectors per workgroup and loop trip
+
+struct AdamwHyper {
+  float lr, beta1, beta2, eps, wd, gscale, bc1, rsqrt_bc2;
+};
+
+// p, g, m and v are touched once per step and not again before the next one: their loads and stores carry the non-temporal
+// hint (the shadow, which the next forward reads, is stored normally).  Measured, not derived: the update alone runs at 5.4 instead
+// of 4.8 TB/s with it, and the step beside it gains more than that difference.  The hint changes no value.
+__device__ __forceinline__ f32x4 ld_stream(const float* a) { return __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(a)); }
+__device__ __forceinline__ void st_stream(float* a, f32x4 x) { __builtin_nontemporal_store(x, reinterpret_cast<f32x4*>(a)); }
+
+template <typename T>
+__device__ __forceinline__ void adamw_dev_vec(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v, T* __restrict__ shadow,
+                                              long i, f32x4 pp, const f32x4 gg, f32x4 mm, f32x4 vv, const AdamwHyper& h) {
+  const float lr = h.lr, beta1 = h.beta1, beta2 = h.beta2, eps = h.eps, wd = h.wd, gscale = h.gscale;
+  const float bc1 = h.bc1, rsqrt_bc2 = h.rsqrt_bc2;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float gr = gg[e] * gscale;
+    pp[e] *= (1.0f - lr * wd);
+    mm[e] = beta1 * mm[e] + (1.0f - beta1) * gr;
+    vv[e] = beta2 * vv[e] + (1.0f - beta2) * gr * gr;
+    const float denom = sqrtf(vv[e]) * rsqrt_bc2 + eps;
+    pp[e] -= (lr / bc1) * (mm[e] / denom);
+  }
+  st_stream(p + 4 * i, pp);
+  st_stream(m + 4 * i, mm);
+  st_stream(v + 4 * i, vv);
+  if (shadow) store4<T>(shadow + 4 * i, pp);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, T* __restrict__ shadow, long n,
                                                         const float* __restrict__ hyper) {
   if (hyper[9] != 0.f) return;  // non-finite gradients under loss scaling: the update is skipped, nothing is touched
-  const float lr = hyper[0], beta1 = hyper[1], beta2 = hyper[2], eps = hyper[3], wd = hyper[4];
-  const float gscale = hyper[5] * (hyper[10] != 0.f ? hyper[10] : 1.0f);
-  const float bc1 = hyper[7], rsqrt_bc2 = hyper[8];
+  AdamwHyper h;
+  h.lr = hyper[0], h.beta1 = hyper[1], h.beta2 = hyper[2], h.eps = hyper[3], h.wd = hyper[4];
+  h.gscale = hyper[5] * (hyper[10] != 0.f ? hyper[10] : 1.0f);
+  h.bc1 = hyper[7], h.rsqrt_bc2 = hyper[8];
   const long nvec = n >> 2;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nvec; i += (long)gridDim.x * 256) {
-    f32x4 pp = *reinterpret_cast<const f32x4*>(p + 4 * i);
-    const f32x4 gg = *reinterpret_cast<const f32x4*>(g + 4 * i);
-    f32x4 mm = *reinterpret_cast<const f32x4*>(m + 4 * i);
-    f32x4 vv = *reinterpret_cast<const f32x4*>(v + 4 * i);
+  for (long c = (long)blockIdx.x * kAdamwChunk; c < nvec; c += (long)gridDim.x * kAdamwChunk) {
+    const long i0 = c + threadIdx.x;
+    if (c + kAdamwChunk <= nvec) {  // a whole chunk (uniform over the workgroup): all loads, then the arithmetic and the stores
+      f32x4 pp[kAdamwUnroll], gg[kAdamwUnroll], mm[kAdamwUnroll], vv[kAdamwUnroll];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float gr = gg[e] * gscale;
-      pp[e] *= (1.0f - lr * wd);
-      mm[e] = beta1 * mm[e] + (1.0f - beta1) * gr;
-      vv[e] = beta2 * vv[e] + (1.0f - beta2) * gr * gr;
-      const float denom = sqrtf(vv[e]) * rsqrt_bc2 + eps;
-      pp[e] -= (lr / bc1) * (mm[e] / denom);
+      for (int k = 0; k < kAdamwUnroll; ++k) {
+        const long i = i0 + k * 256;
+        pp[k] = ld_stream(p + 4 * i);
+        gg[k] = ld_stream(g + 4 * i);
+        mm[k] = ld_stream(m + 4 * i);
+        vv[k] = ld_stream(v + 4 * i);
+      }
+#pragma unroll
+      for (int k = 0; k < kAdamwUnroll; ++k) adamw_dev_vec<T>(p, m, v, shadow, i0 + k * 256, pp[k], gg[k], mm[k], vv[k], h);
+    } else {  // the ragged last chunk of the range
+      for (long i = i0; i < nvec; i += 256)
+        adamw_dev_vec<T>(p, m, v, shadow, i, ld_stream(p + 4 * i), ld_stream(g + 4 * i),
+                         ld_stream(m + 4 * i), ld_stream(v + 4 * i), h);
     }
-    *reinterpret_cast<f32x4*>(p + 4 * i) = pp;
-    *reinterpret_cast<f32x4*>(m + 4 * i) = mm;
-    *reinterpret_cast<f32x4*>(v + 4 * i) = vv;
-    if (shadow) store4<T>(shadow + 4 * i, pp);
   }
 }
 
@@ -546,15 +588,60 @@ extern "C" int pm_adamw_tick(float* hyper, int n_groups, void* stream) {
   return pm_check_launch();
 }
 
-extern "C" int pm_adamw_dev(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, long n,
-                            const float* hyper, void* stream) {
+// Workgroups of one adamw_dev_kernel launch over n elements.  max_blocks = 0: the full grid (one workgroup per 256 vectors, at
+// most 4096: fastest when the update runs alone); max_blocks > 0: one workgroup per chunk of kAdamwChunk vectors, at most
+// max_blocks (the footprint an update beside other kernels is held to).
+extern "C" int pm_adamw_grid(long n, int max_blocks) {
+  if (n <= 0 || (n & 3) || max_blocks < 0) return PM_ESHAPE;
+  return max_blocks == 0 ? cap_grid(n >> 2, 256, 4096) : cap_grid(n >> 2, kAdamwChunk, max_blocks);
+}
+
+static int adamw_dev_check(const float* p, const float* g, const float* m, const float* v, const void* shadow, int shadow_dtype,
+                           long n, const float* hyper) {
   if (!p || !g || !m || !v || !hyper) return PM_EINVAL;
   if (n <= 0 || (n & 3)) return PM_ESHAPE;
-  const dim3 grid(cap_grid(n >> 2, 256, 4096));
+  if (shadow && shadow_dtype != PM_BF16 && shadow_dtype != PM_F16 && shadow_dtype != PM_F32) return PM_EINVAL;
+  return PM_OK;
+}
+
+static int adamw_dev_launch(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, long n, const float* hyper,
+                            int max_blocks, void* stream) {
+  const dim3 grid(pm_adamw_grid(n, max_blocks));
   if (!shadow) shadow_dtype = PM_BF16;
   PM_DISPATCH_ACT(shadow_dtype, T, hipLaunchKernelGGL(adamw_dev_kernel<T>, grid, dim3(256), 0, pm_stream(stream), p, g, m, v, (T*)shadow,
                                                       n, hyper));
   return pm_check_launch();
+}
+
+extern "C" int pm_adamw_dev(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, long n,
+                            const float* hyper, void* stream) {
+  const int st = adamw_dev_check(p, g, m, v, shadow, shadow_dtype, n, hyper);
+  if (st != PM_OK) return st;
+  return adamw_dev_launch(p, g, m, v, shadow, shadow_dtype, n, hyper, 0, stream);
+}
+
+// The whole update in one call: [wait_event ->] tick -> per segment (launch [-> done_event]).  Everything is checked before the
+// first enqueue, so a refusal leaves the stream untouched.
+extern "C" int pm_adamw_segments(const pm_adamw_segment* segs, int n_segs, float* hyper, int n_groups, void* wait_event, void* stream,
+                                 int max_blocks) {
+  if (!segs || !hyper) return PM_EINVAL;
+  if (n_segs <= 0 || n_groups <= 0 || max_blocks < 0) return PM_ESHAPE;
+  for (int i = 0; i < n_segs; ++i) {
+    const pm_adamw_segment& s = segs[i];
+    const int st = adamw_dev_check(s.p, s.g, s.m, s.v, s.shadow, s.shadow_dtype, s.n, s.hyper);
+    if (st != PM_OK) return st;
+  }
+  hipStream_t q = pm_stream(stream);
+  if (wait_event && hipStreamWaitEvent(q, (hipEvent_t)wait_event, 0) != hipSuccess) return PM_ELAUNCH;
+  int st = pm_adamw_tick(hyper, n_groups, stream);
+  if (st != PM_OK) return st;
+  for (int i = 0; i < n_segs; ++i) {
+    const pm_adamw_segment& s = segs[i];
+    st = adamw_dev_launch(s.p, s.g, s.m, s.v, s.shadow, s.shadow_dtype, s.n, s.hyper, max_blocks, stream);
+    if (st != PM_OK) return st;
+    if (s.done_event && hipEventRecord((hipEvent_t)s.done_event, q) != hipSuccess) return PM_ELAUNCH;
+  }
+  return PM_OK;
 }
 
 extern "C" int pm_loss_scale_update(float* state, const float* stats, float* hyper, int n_groups, float growth_factor,

@@ -183,9 +183,10 @@ class FusedAdamW(torch.optim.Optimizer):
             work = sorted(split, key=lambda w: (w[1] != "vec", w[2]))
             main = torch.cuda.current_stream(f.device)
             side = rt.k.side_stream(f.device)
-            ev = torch.cuda.Event()
+            ev = self._event(-1, side)
             ev.record(main)
-            side.wait_event(ev)
+            if scaled or not work:
+                side.wait_event(ev)
             stream_ctx = torch.cuda.stream(side)
         else:
             stream_ctx = contextlib.nullcontext()
@@ -199,6 +200,14 @@ class FusedAdamW(torch.optim.Optimizer):
                                                     loss_scaler.growth_factor, loss_scaler.backoff_factor,
                                                     loss_scaler.growth_interval, _stream()), "pm_loss_scale_update")
                 self._scaler_used = True
+            if overlap and work:
+                # the whole update in ONE C call: [wait for the main stream's event,] tick, then launch + done event per segment
+                segs, events = self._segment_array(f, work, side)
+                _lib.check(lib.pm_adamw_segments(segs, len(work), _ptr(self._hyper), len(self.param_groups),
+                                                 None if scaled else ev.cuda_event, _stream(), self.OVERLAP_MAX_BLOCKS),
+                           "pm_adamw_segments")
+                rt.pending_updates += [(r, lo, hi, done) for (_, r, lo, hi), done in zip(work, events)]
+                return loss
             _lib.check(lib.pm_adamw_tick(_ptr(self._hyper), len(self.param_groups), _stream()), "pm_adamw_tick")
             for gi, r, lo, hi in work:
                 shadow = f.S[lo:hi] if (r == "mat" and f.S is not None) else None
@@ -206,11 +215,40 @@ class FusedAdamW(torch.optim.Optimizer):
                                             _ptr(self._V[r][lo:hi]), _ptr(shadow),
                                             _lib.dtype_code(shadow.dtype) if shadow is not None else 0, hi - lo,
                                             _ptr(self._hyper[gi]), _stream()), "pm_adamw_dev")
-                if overlap:
-                    done = torch.cuda.Event()
-                    done.record(side)
-                    rt.pending_updates.append((r, lo, hi, done))
         return loss
+
+    # -- the overlapped update's launcher arguments (pm_adamw_segments) -----------------------------------------
+    # Workgroups per launch of the overlapped update (pm_adamw_grid; 0 = the full grid, which the inline path keeps).  Chosen by
+    # step rate from 64 / 128 / 256 / 512 / 1024 / unbounded on the cls headline and on MAE, the parent alternating in the same
+    # job (docs/EXPERIMENT_LOG.md, "AdamW footprint"): 256 is the smallest grid that still runs the update at HBM rate alone
+    # (64 and 128 fall below it and lose 4 % / 2 % of the step), and the best or equal-best on both workloads.
+    OVERLAP_MAX_BLOCKS = 256
+
+    def _event(self, i, side):
+        """Event number i of the overlapped path, created once (-1: the main stream's fork event; i >= 0: segment i's done event).
+        step() waits for every pending update before it records any of them again."""
+        cache = self.__dict__.setdefault("_events", {})
+        e = cache.get(i)
+        if e is None:
+            e = cache[i] = torch.cuda.Event()
+            e.record(side)  # (materialises the hipEvent_t handle)
+        return e
+
+    def _segment_array(self, f, work, side):
+        """(pm_adamw_segment array, done events) of `work`, rebuilt only when the segments or the buffers behind them change."""
+        S = f.S
+        key = (tuple(work), S.dtype if S is not None else None, self._hyper.data_ptr(), _ptr(S)) + \
+            tuple(t[r].data_ptr() for r in ("mat", "vec") for t in (f.P, f.G, self._M, self._V))
+        if getattr(self, "_seg_key", None) != key:
+            events = [self._event(i, side) for i in range(len(work))]
+            segs = (_lib.AdamwSegment * len(work))()
+            for i, (gi, r, lo, hi) in enumerate(work):
+                shadow = S[lo:hi] if (r == "mat" and S is not None) else None
+                segs[i] = _lib.AdamwSegment(_ptr(f.P[r][lo:hi]), _ptr(f.G[r][lo:hi]), _ptr(self._M[r][lo:hi]), _ptr(self._V[r][lo:hi]),
+                                            _ptr(shadow), _lib.dtype_code(shadow.dtype) if shadow is not None else 0, hi - lo,
+                                            _ptr(self._hyper[gi]), events[i].cuda_event)
+            self._seg_key, self._seg_args = key, (segs, events)
+        return self._seg_args
 
     def sync(self) -> None:
         """Make the current stream wait for an overlapped update (no-op otherwise)."""
