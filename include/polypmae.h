@@ -658,6 +658,36 @@ int pm_boot_metrics(const double* score, const int* order, const unsigned char* 
                     const double* tau, double* out, int N, int M, int R, int K, int C, int sorted_ready, void* workspace,
                     size_t ws_bytes, void* stream);
 
+/* ---- the same replicates per group of frames: perturbation tags, morphology strata ------------------------------------------
+ * Replaces one pm_boot_metrics call per group on a gathered subset (the reference's per-tag metrics, train_classification.py:5256-5483,
+ * and morphology strata, :3041-3089, exp3_report.compute_strata_metrics).  A group is a set of frames; groups may overlap (every
+ * stratum holds every negative).  The memberships are expanded into E entries, one per (group, frame) pair, laid out as G segments:
+ *   score   f64 [M, N]  as pm_boot_metrics takes it
+ *   member  i32 [M, E]  per run, the frame index of every entry: segment g = entries seg[g] .. seg[g + 1] - 1 holds the frames of
+ *                       group g in descending score order (ties in any order; the bits below hold for the order stated there).
+ *                       An entry outside [0, N) (-1 = padding) has weight zero
+ *   seg     i32 [G + 1] segment offsets, ON THE DEVICE, non-decreasing from 0 to at most E.  Values are clamped to [0, E] and a
+ *                       segment whose start >= its end is empty, so no table can send an access outside the buffers
+ *   label, cluster, draws, tau  as pm_boot_metrics takes them (clusters and draws are those of the whole set: a group's replicate
+ *                       is the replicate of the set restricted to the group)
+ *   out     f64 [R, M, G, 16] in pm_boot_metrics' key order.  One workgroup per (replicate, run, group) scans its own segment only:
+ *           the work is proportional to E, not to G * N.  A tie group ends at the segment's end whatever score the next segment
+ *           starts with, and scan tiles are laid from the segment's start, so group g's 16 values are, bit for bit, what
+ *           pm_boot_metrics returns for the frames of g alone (gathered in the order of their entries' score ties) with the same
+ *           cluster and draws -- and a group that lists every frame gives pm_boot_metrics' own bits.  An empty group, or one no
+ *           frame of which was drawn, gives the empty replicate's row (counts 0, the rest NaN).
+ * Limits (PM_ESHAPE before any launch): 1 <= N, K, C <= 2^20, 1 <= E <= 2^22, 1 <= G <= 2^16, M <= 256, R <= 4096 per call,
+ * E * K < 2^31 (a segment's total weight fits 31 bits), R * M * G < 2^31 (one launch).
+ * workspace: 16-byte aligned, at least pm_group_metrics_workspace(N, M, E, G, R, K, C, &bytes) bytes (PM_EINVAL otherwise, as for
+ * a missing buffer; PM_EALIGN for a misaligned one).  Its head holds the prepared view of the entries [M, E] (score, per-frame
+ * loss, cluster << 1 | label), then the counters mult [R, C].  sorted_ready as for pm_boot_metrics: 0 builds the view (one memset
+ * and three launches on `stream`), != 0 states that an earlier call with the same score, member, label, cluster, N, M, E and C
+ * built it here and reuses it (one memset and two launches).  The launcher reads no device data and does not synchronise. */
+int pm_group_metrics_workspace(int N, int M, int E, int G, int R, int K, int C, size_t* bytes);
+int pm_group_metrics(const double* score, const int* member, const int* seg, const unsigned char* label, const int* cluster,
+                     const int* draws, const double* tau, double* out, int N, int M, int E, int G, int R, int K, int C,
+                     int sorted_ready, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- the decision threshold of a run, chosen on its validation scores ------------------------------------------------------
  * Replaces the reference's classification/metrics/thresholds.py: compute_policy_threshold (:299-390) for policy 0 f1_opt_on_val,
  * 1 youden_on_val, 2 val_opt_youden (the same objective as 1), and compute_youden_j_threshold (:68-110: scikit-learn's roc_curve

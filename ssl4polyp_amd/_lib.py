@@ -86,6 +86,8 @@ SIGNATURES = {
     "pm_dgelu": [P, P, P, I, L, P],
     "pm_boot_metrics_workspace": [I, I, I, I, I, P],
     "pm_boot_metrics": [P, P, P, P, P, P, P, I, I, I, I, I, I, P, ctypes.c_size_t, P],
+    "pm_group_metrics_workspace": [I, I, I, I, I, I, I, P],
+    "pm_group_metrics": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, ctypes.c_size_t, P],
     "pm_select_tau_workspace": [I, I, P],
     "pm_select_tau": [P, P, P, P, I, P, P, I, I, P, ctypes.c_size_t, P],
 }

@@ -1,4 +1,5 @@
-// pm_metrics.hip -- cluster-bootstrap replicates of the binary test metrics (include/polypmae.h: pm_boot_metrics).
+// pm_metrics.hip -- cluster-bootstrap replicates of the binary test metrics (include/polypmae.h: pm_boot_metrics), of the whole set
+// and per group of frames (pm_group_metrics).
 //
 // A replicate is a multiset of frames: frame i appears w_i = (times its cluster was drawn) times, and every metric of the
 // reference's compute_binary_metrics (classification/analysis/common_metrics.py:100-183) is a function of (score, label, w).
@@ -10,6 +11,8 @@
 //                        (positives, negatives) pair packed into one 64-bit integer, a carried running maximum that names the
 //                        prefix at the previous tie-group end, f64 terms added per thread in tile order and reduced by a fixed
 //                        tree at the end.  Integer counts are exact; the result does not depend on how R is cut into calls.
+//   group_scan_kernel    one workgroup per (replicate, run, group): the same scan (scan_segment) over the group's segment of the
+//                        entry list alone -- tiles from the segment's start, ties end at its end.
 #include "pm_common.h"
 
 namespace {
@@ -45,20 +48,21 @@ int boot_shape(int N, int M, int R, int K, int C) {
   return PM_OK;
 }
 
-// The sorted view of run m: position j holds frame order[m][j].  An index outside [0, N) or a cluster outside [0, C) gives the
-// position weight zero (cl = -1) instead of an access outside the buffers.
+// The sorted view of run m: position j of its E positions holds frame order[m][j] (pm_boot_metrics: E = N, every frame once;
+// pm_group_metrics: the entry list).  An index outside [0, N) or a cluster outside [0, C) gives the position weight zero (cl = -1)
+// instead of an access outside the buffers.
 __global__ __launch_bounds__(kThreads) void boot_prepare_kernel(const double* __restrict__ score, const int* __restrict__ order,
                                                                 const unsigned char* __restrict__ label,
-                                                                const int* __restrict__ cluster, int N, int M, int C,
+                                                                const int* __restrict__ cluster, int N, int E, int M, int C,
                                                                 double* __restrict__ s_sorted, double* __restrict__ l_sorted,
                                                                 int* __restrict__ cl_sorted) {
   const long long idx = (long long)blockIdx.x * kThreads + threadIdx.x;
-  if (idx >= (long long)M * N) return;
+  if (idx >= (long long)M * E) return;
   const int i = order[idx];
   double s = 0.0, l = 0.0;
   int cl = -1;
   if ((unsigned)i < (unsigned)N) {
-    const long long m = idx / N;
+    const long long m = idx / E;
     s = score[m * N + i];
     const int c = cluster[i];
     const int y = label[i] != 0;
@@ -103,19 +107,16 @@ __device__ inline u64 u64_max(u64 a, u64 b) { return a > b ? a : b; }
 // Weighted counts travel as one 64-bit integer: positives in the high half, negatives in the low half.  Both halves stay below
 // 2^31 (boot_shape), so sums never carry across, and -- both being non-decreasing along the order -- the packed prefix is
 // non-decreasing too: the maximum over earlier tie-group ends IS the prefix at the previous group end.
-__global__ __launch_bounds__(kThreads) void boot_scan_kernel(const double* __restrict__ s_sorted, const double* __restrict__ l_sorted,
-                                                             const int* __restrict__ cl_sorted, const unsigned* __restrict__ mult,
-                                                             const double* __restrict__ tau, int N, int M, int C,
-                                                             double* __restrict__ out) {
+//
+// scan_segment: the n positions s[0 .. n) of one run's view, weights mu[cluster], threshold t -> the 16 values at o.  Called by every
+// thread of the workgroup with the same arguments.  Nothing beyond position n - 1 is read: the look-ahead of the last position is
+// replaced by "the tie group ends here", so a segment that is followed by another one (pm_group_metrics) ends its last tie group
+// whatever score comes next.  n = 0 gives the empty sample's row.
+__device__ inline void scan_segment(const double* __restrict__ s, const double* __restrict__ ls, const int* __restrict__ cls,
+                                    const unsigned* __restrict__ mu, const double t, const int N, double* __restrict__ o) {
   __shared__ u64 sh_sum[kWaves], sh_max[kWaves], sh_conf[kWaves], sh_roc[kWaves];
   __shared__ double sh_ap[kWaves], sh_loss[kWaves];
   const int tid = threadIdx.x, lane = tid & (PM_WAVE - 1), wave = tid / PM_WAVE;
-  const long long r = blockIdx.x / M, m = blockIdx.x % M;
-  const double* s = s_sorted + m * N;
-  const double* ls = l_sorted + m * N;
-  const int* cls = cl_sorted + m * N;
-  const unsigned* mu = mult + r * C;
-  const double t = tau[m];
 
   u64 carry = 0, last_end = 0;      // the same in every thread: prefix before this tile, prefix at the last group end before it
   u64 conf = 0, roc = 0;            // per thread: weighted (tp, fp) at tau; the AUROC numerator
@@ -214,7 +215,6 @@ __global__ __launch_bounds__(kThreads) void boot_scan_kernel(const double* __res
   const long long P = (long long)(carry >> 32), Nn = (long long)(carry & 0xffffffffu), n = P + Nn;
   const long long tp = (long long)(conf >> 32), fp = (long long)(conf & 0xffffffffu), tn = Nn - fp, fn = P - tp;
   const double nan = __builtin_nan("");
-  double* o = out + (long long)blockIdx.x * kOut;
   o[0] = (double)n;
   o[1] = (double)P;
   o[2] = (double)Nn;
@@ -244,6 +244,69 @@ __global__ __launch_bounds__(kThreads) void boot_scan_kernel(const double* __res
   o[15] = loss / (double)n;
 }
 
+__global__ __launch_bounds__(kThreads) void boot_scan_kernel(const double* __restrict__ s_sorted, const double* __restrict__ l_sorted,
+                                                             const int* __restrict__ cl_sorted, const unsigned* __restrict__ mult,
+                                                             const double* __restrict__ tau, int N, int M, int C,
+                                                             double* __restrict__ out) {
+  const long long r = blockIdx.x / M, m = blockIdx.x % M;
+  scan_segment(s_sorted + m * N, l_sorted + m * N, cl_sorted + m * N, mult + r * C, tau[m], N, out + (long long)blockIdx.x * kOut);
+}
+
+// block = (r * M + m) * G + g.  The offsets are clamped to [0, E] and a segment whose start is not below its end is empty, so a
+// wrong table gives wrong numbers and never an access outside the view.
+__global__ __launch_bounds__(kThreads) void group_scan_kernel(const double* __restrict__ s_sorted, const double* __restrict__ l_sorted,
+                                                              const int* __restrict__ cl_sorted, const unsigned* __restrict__ mult,
+                                                              const double* __restrict__ tau, const int* __restrict__ seg, int E,
+                                                              int M, int G, int C, double* __restrict__ out) {
+  const long long g = blockIdx.x % G, rm = blockIdx.x / G, r = rm / M, m = rm % M;
+  const int lo = min(max(seg[g], 0), E), hi = min(max(seg[g + 1], 0), E);
+  const int n = hi > lo ? hi - lo : 0;
+  const long long at = m * E + lo;
+  scan_segment(s_sorted + at, l_sorted + at, cl_sorted + at, mult + r * C, tau[m], n, out + (long long)blockIdx.x * kOut);
+}
+
+constexpr int kMaxE = 1 << 22, kMaxG = 1 << 16;
+
+int group_shape(int N, int M, int E, int G, int R, int K, int C) {
+  if (E < 1 || G < 1 || E > kMaxE || G > kMaxG) return PM_ESHAPE;
+  const int st = boot_shape(N, M, R, K, C);
+  if (st != PM_OK) return st;
+  if ((long long)E * K > 0x7fffffffLL) return PM_ESHAPE;      // a segment's total weight <= E * K: the 32-bit halves of the scan
+  if ((long long)R * M * G > 0x7fffffffLL) return PM_ESHAPE;  // one workgroup per (replicate, run, group): the grid's x limit
+  return PM_OK;
+}
+
+struct BootView {
+  double *score, *loss;
+  int* cl;
+  unsigned* mult;
+};
+
+// What both entry points do before their scan, after their shape check: the buffers, the workspace and the alignment, then the
+// counters (a memset and boot_mult_kernel) and -- unless the caller states it is there -- the view of E positions per run.
+int boot_prepare(const double* score, const int* order, const unsigned char* label, const int* cluster, const int* draws,
+                 const double* tau, double* out, int N, int E, int M, int R, int K, int C, int sorted_ready, void* workspace,
+                 size_t ws_bytes, hipStream_t s, BootView* v) {
+  if (!score || !order || !label || !cluster || !draws || !tau || !out || !workspace) return PM_EINVAL;
+  const BootWs ws = boot_ws(E, M, R, C);
+  if (ws_bytes < ws.bytes) return PM_EINVAL;
+  if (((uintptr_t)workspace & 15) || ((uintptr_t)score & 7) || ((uintptr_t)tau & 7) || ((uintptr_t)out & 7)) return PM_EALIGN;
+  unsigned char* wsb = static_cast<unsigned char*>(workspace);
+  v->score = reinterpret_cast<double*>(wsb + ws.score);
+  v->loss = reinterpret_cast<double*>(wsb + ws.loss);
+  v->cl = reinterpret_cast<int*>(wsb + ws.cl);
+  v->mult = reinterpret_cast<unsigned*>(wsb + ws.mult);
+  if (hipMemsetAsync(v->mult, 0, (size_t)R * C * sizeof(unsigned), s) != hipSuccess) return PM_ELAUNCH;
+  const long long me = (long long)M * E, rk = (long long)R * K;
+  if (!sorted_ready)  // the view does not depend on the replicates: later calls of a series reuse it
+    hipLaunchKernelGGL(boot_prepare_kernel, dim3((unsigned)((me + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, score, order,
+                       label, cluster, N, E, M, C, v->score, v->loss, v->cl);
+  long long mult_blocks = (rk + kThreads - 1) / kThreads;
+  if (mult_blocks > 4096) mult_blocks = 4096;
+  hipLaunchKernelGGL(boot_mult_kernel, dim3((unsigned)mult_blocks), dim3(kThreads), 0, s, draws, rk, K, C, v->mult);
+  return PM_OK;
+}
+
 }  // namespace
 
 extern "C" int pm_boot_metrics_workspace(int N, int M, int R, int K, int C, size_t* bytes) {
@@ -257,27 +320,36 @@ extern "C" int pm_boot_metrics_workspace(int N, int M, int R, int K, int C, size
 extern "C" int pm_boot_metrics(const double* score, const int* order, const unsigned char* label, const int* cluster, const int* draws,
                                const double* tau, double* out, int N, int M, int R, int K, int C, int sorted_ready, void* workspace,
                                size_t ws_bytes, void* stream) {
-  const int st = boot_shape(N, M, R, K, C);
+  int st = boot_shape(N, M, R, K, C);
   if (st != PM_OK) return st;
-  if (!score || !order || !label || !cluster || !draws || !tau || !out || !workspace) return PM_EINVAL;
-  const BootWs ws = boot_ws(N, M, R, C);
-  if (ws_bytes < ws.bytes) return PM_EINVAL;
-  if (((uintptr_t)workspace & 15) || ((uintptr_t)score & 7) || ((uintptr_t)tau & 7) || ((uintptr_t)out & 7)) return PM_EALIGN;
   hipStream_t s = pm_stream(stream);
-  unsigned char* wsb = static_cast<unsigned char*>(workspace);
-  double* s_sorted = reinterpret_cast<double*>(wsb + ws.score);
-  double* l_sorted = reinterpret_cast<double*>(wsb + ws.loss);
-  int* cl_sorted = reinterpret_cast<int*>(wsb + ws.cl);
-  unsigned* mult = reinterpret_cast<unsigned*>(wsb + ws.mult);
-  if (hipMemsetAsync(mult, 0, (size_t)R * C * sizeof(unsigned), s) != hipSuccess) return PM_ELAUNCH;
-  const long long mn = (long long)M * N, rk = (long long)R * K;
-  if (!sorted_ready)  // the view does not depend on the replicates: later calls of a series reuse it
-    hipLaunchKernelGGL(boot_prepare_kernel, dim3((unsigned)((mn + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, score, order,
-                       label, cluster, N, M, C, s_sorted, l_sorted, cl_sorted);
-  long long mult_blocks = (rk + kThreads - 1) / kThreads;
-  if (mult_blocks > 4096) mult_blocks = 4096;
-  hipLaunchKernelGGL(boot_mult_kernel, dim3((unsigned)mult_blocks), dim3(kThreads), 0, s, draws, rk, K, C, mult);
-  hipLaunchKernelGGL(boot_scan_kernel, dim3((unsigned)(R * M)), dim3(kThreads), 0, s, s_sorted, l_sorted, cl_sorted, mult, tau, N, M, C,
-                     out);
+  BootView v;
+  st = boot_prepare(score, order, label, cluster, draws, tau, out, N, N, M, R, K, C, sorted_ready, workspace, ws_bytes, s, &v);
+  if (st != PM_OK) return st;
+  hipLaunchKernelGGL(boot_scan_kernel, dim3((unsigned)(R * M)), dim3(kThreads), 0, s, v.score, v.loss, v.cl, v.mult, tau, N, M, C, out);
+  return pm_check_launch();
+}
+
+extern "C" int pm_group_metrics_workspace(int N, int M, int E, int G, int R, int K, int C, size_t* bytes) {
+  const int st = group_shape(N, M, E, G, R, K, C);
+  if (st != PM_OK) return st;
+  if (!bytes) return PM_EINVAL;
+  *bytes = boot_ws(E, M, R, C).bytes;  // the view is per entry
+  return PM_OK;
+}
+
+extern "C" int pm_group_metrics(const double* score, const int* member, const int* seg, const unsigned char* label, const int* cluster,
+                                const int* draws, const double* tau, double* out, int N, int M, int E, int G, int R, int K, int C,
+                                int sorted_ready, void* workspace, size_t ws_bytes, void* stream) {
+  int st = group_shape(N, M, E, G, R, K, C);
+  if (st != PM_OK) return st;
+  if (!seg) return PM_EINVAL;
+  if (((uintptr_t)seg & 3) || ((uintptr_t)member & 3)) return PM_EALIGN;
+  hipStream_t s = pm_stream(stream);
+  BootView v;
+  st = boot_prepare(score, member, label, cluster, draws, tau, out, N, E, M, R, K, C, sorted_ready, workspace, ws_bytes, s, &v);
+  if (st != PM_OK) return st;
+  hipLaunchKernelGGL(group_scan_kernel, dim3((unsigned)((long long)R * M * G)), dim3(kThreads), 0, s, v.score, v.loss, v.cl, v.mult, tau, seg,
+                     E, M, G, C, out);
   return pm_check_launch();
 }

@@ -19,7 +19,15 @@ the val scores after every epoch (`val_tau`, `val_threshold` = the reference's r
 `thresholds` / `threshold_records[<dataset>_val_<policy>]`, and the test record reports `test_tau`, `test_metrics_at_tau` and the
 bootstrap intervals at that tau; sun_val_frozen takes the tau from `--threshold_from`, such a checkpoint with exactly one
 threshold.  Without the flag nothing changes: tau = 0.5 and the records and checkpoints of before.  `run(args)` returns the model
-and the last val logits.  Not here: sharded evaluation through the prefetcher.
+and the last val logits.  `--group_metrics morphology|perturbation` (repeatable) adds the reference's per-group blocks to the test
+record at the tau in force: `test_strata` (overall / flat_plus_negs / polypoid_plus_negs from the rows' `morphology`) and
+`test_perturbation_metrics` (`per_tag` in the reference's order of report, `per_case` recall / F1 / count per tag and case_id), with
+`--bootstrap R` also `test_strata_ci` / `test_perturbation_ci` (`ci_lower`, `ci_upper` per group and reported metric, from the draws
+of the overall interval; metrics.bootstrap_group_metrics, one device call per chunk whatever the number of groups).
+`--threshold_policy f1-morph` selects tau on val as the reference's _compute_f1_morph_threshold does and falls back to `youden` where
+that gives none (`val_threshold` = policy, tau, split, epoch, fallback).  `--curve_export POINTS` writes the ROC and PR curve files of
+val and test under --output_dir and names them in the records (`val_curves`, `test_curves`).  Not here: sharded evaluation through
+the prefetcher.
 """
 from __future__ import annotations
 
@@ -39,6 +47,8 @@ from .train import FINETUNE_MODES, cls_cosine_lambda, configure_finetune_paramet
 
 SELECTING_POLICIES = ("f1_opt_on_val", "youden_on_val", "val_opt_youden", "youden")   # metrics.POLICIES
 FROZEN_POLICY = "sun_val_frozen"
+MORPH_POLICY = "f1-morph"   # metrics.f1_morph_threshold: a grid search over two strata, not one of pm_select_tau's policies
+GROUP_KINDS = ("morphology", "perturbation")
 
 
 def get_args_parser():
@@ -77,12 +87,18 @@ def get_args_parser():
     p.add_argument("--bootstrap", default=0, type=int, metavar="R",
                    help="R > 0: 95 %% intervals of the test metrics from R cluster-bootstrap replicates (clusters: case_id per label)")
     p.add_argument("--bootstrap_seed", default=12345, type=int)
-    p.add_argument("--threshold_policy", default="none", choices=["none", *SELECTING_POLICIES, FROZEN_POLICY],
+    p.add_argument("--threshold_policy", default="none", choices=["none", *SELECTING_POLICIES, MORPH_POLICY, FROZEN_POLICY],
                    help="how the decision threshold tau is chosen (the reference's threshold_policy): on the val split after every "
-                        "epoch, on the device; sun_val_frozen reuses the tau of --threshold_from")
+                        "epoch, on the device; f1-morph needs a `morphology` column and falls back to youden; sun_val_frozen reuses the "
+                        "tau of --threshold_from")
     p.add_argument("--dataset_name", default="dataset", help="names the val split in the threshold record and its checkpoint key")
     p.add_argument("--threshold_from", default=None, metavar="CKPT",
                    help="with --threshold_policy sun_val_frozen: a checkpoint of this command that holds exactly one threshold")
+    p.add_argument("--group_metrics", action="append", default=[], choices=list(GROUP_KINDS),
+                   help="per-group test metrics at the tau in force (repeatable): morphology = the strata overall / flat_plus_negs / "
+                        "polypoid_plus_negs, perturbation = per perturbation tag and per (tag, case); with --bootstrap their intervals")
+    p.add_argument("--curve_export", default=0, type=int, metavar="POINTS",
+                   help="POINTS >= 2: write <output_dir>/curves_<split>_roc_curve.csv and _pr_curve.csv for val and test over that many thresholds")
     return p
 
 
@@ -155,6 +171,47 @@ def metric_records(prefix: str, logits: torch.Tensor, targets: torch.Tensor, row
     return out
 
 
+def group_records(logits: torch.Tensor, targets: torch.Tensor, rows, device, kinds, bootstrap: int = 0, seed: int = 0, tau=None) -> dict:
+    """The entries `--group_metrics` adds to the test record, at tau (f64 [1] on the device) or 0.5.  morphology: test_strata
+    {stratum: the 16 values}, a stratum without a positive left out as the reference's test() leaves it out.  perturbation:
+    test_perturbation_metrics {per_tag: {tag: the 16 values} in the reference's order of report, per_case: {tag: {case_id: recall,
+    f1, count}} when the rows have case ids}.  bootstrap > 0: test_strata_ci / test_perturbation_ci = {ci_lower, ci_upper: {group:
+    {reported metric: bound}}} from the replicates metric_records draws for the overall interval (same clusters, same seed).
+    Values that are not finite are null."""
+    import numpy as np
+    from . import metrics as MX
+    if logits.shape[0] == 0:
+        return {}
+    probs = MX.positive_probs(logits.to(device))
+    at = METRICS_TAU if tau is None else tau
+    labels = targets.tolist()
+    out, sets = {}, {}
+    if "morphology" in kinds:
+        sets["test_strata"] = MX.morphology_groups(rows, labels)
+        out["test_strata"] = {g: dict(zip(v, strict(v.values()))) for g, v in MX.group_metrics(probs, targets, at, sets["test_strata"], device=device).items()}
+    if "perturbation" in kinds:
+        groups = sets["test_perturbation"] = MX.perturbation_groups(rows)
+        block = {"per_tag": {g: dict(zip(v, strict(v.values()))) for g, v in MX.group_metrics(probs, targets, at, groups, device=device).items()}}
+        case_ids = [str(r.get("case_id") or "") for r in rows]
+        if any(case_ids):
+            names = sorted(set(case_ids))
+            index = {c: i for i, c in enumerate(names)}
+            per = {k: v.tolist() for k, v in MX.group_case_metrics(probs, targets, at, groups, [index[c] for c in case_ids], len(names), device=device).items()}
+            block["per_case"] = {tag: {c: {"recall": per["recall"][g][i], "f1": per["f1"][g][i], "count": float(per["count"][g][i])}
+                                       for i, c in enumerate(names) if per["count"][g][i] > 0} for g, tag in enumerate(groups.names)}
+        out["test_perturbation_metrics"] = block
+    if bootstrap > 0:
+        clusters = MX.build_cluster_set(rows, labels)
+        draws = MX.draw_cluster_samples(clusters, np.random.default_rng(seed), bootstrap)
+        first = len(MX.METRIC_KEYS) - len(MX.REPORTED_KEYS)
+        for key, groups in sets.items():
+            reps = MX.bootstrap_group_metrics(probs, targets, at, groups, clusters.cluster, draws, n_clusters=clusters.n_clusters, device=device)
+            lo, hi = MX.percentile_ci(reps[:, 0, :, first:], 0.95)
+            out[key.replace("_metrics", "") + "_ci"] = {name: {g: dict(zip(MX.REPORTED_KEYS, strict(row))) for g, row in zip(groups.names, bound.tolist())}
+                                                        for name, bound in (("ci_lower", lo), ("ci_upper", hi))}
+    return out
+
+
 def frozen_threshold(path):
     """(tau, key, record) of the one threshold a checkpoint of this command holds (`thresholds` / `threshold_records`, written by a
     run with a selecting --threshold_policy): what `--threshold_policy sun_val_frozen --threshold_from` reuses."""
@@ -181,8 +238,12 @@ def run(args):
         raise SystemExit("--metrics / --bootstrap report the binary metrics: they need --num_classes 2")
     if args.fused_decode and args.decode != "device":
         raise SystemExit("--fused_decode needs --decode device")
+    if args.group_metrics and args.num_classes != 2:
+        raise SystemExit("--group_metrics reports the binary metrics per group: it needs --num_classes 2")
+    if args.curve_export and (args.curve_export < 2 or args.num_classes != 2):
+        raise SystemExit("--curve_export takes at least two grid points and needs --num_classes 2")
     policy = args.threshold_policy
-    selecting = policy in SELECTING_POLICIES
+    selecting = policy in SELECTING_POLICIES or policy == MORPH_POLICY
     if policy != "none" and args.num_classes != 2:
         raise SystemExit("--threshold_policy chooses a binary decision threshold: it needs --num_classes 2")
     if selecting and not args.val_csv:
@@ -244,17 +305,33 @@ def run(args):
         `thresholds` / `threshold_records`; the tau stays on the device and is the next epoch's previous_tau."""
         nonlocal tau_dev, extra
         from . import metrics as MX
-        row = MX.select_threshold(MX.positive_probs(val_logits.to(device)), val_targets, policy, previous_tau=tau_dev, device=device)
-        try:
-            rec = MX.threshold_record(row[0], policy, f"{args.dataset_name}/val", epoch)
-        except ValueError as e:
-            raise SystemExit(f"--threshold_policy {policy} on {args.val_csv}: {e}")
-        tau_dev = row[:, 0].contiguous()
+        probs = MX.positive_probs(val_logits.to(device))
+        found = MX.f1_morph_threshold(probs, val_targets, [r.get("morphology") for r in splits["val"][2]], device=device) \
+            if policy == MORPH_POLICY else None
+        if found is not None:
+            rec = {"policy": policy, "tau": found, "split": f"{args.dataset_name}/val", "epoch": int(epoch), "fallback": None}
+            tau_dev = torch.tensor([found], dtype=torch.float64, device=device)
+        else:   # a selecting policy, or f1-morph without both kinds of positives: the reference then takes Youden's J (tc.py:7281-7285)
+            by = "youden" if policy == MORPH_POLICY else policy
+            row = MX.select_threshold(probs, val_targets, by, previous_tau=tau_dev, device=device)
+            try:
+                rec = MX.threshold_record(row[0], by, f"{args.dataset_name}/val", epoch)
+            except ValueError as e:
+                raise SystemExit(f"--threshold_policy {policy} on {args.val_csv}: {e}")
+            if policy == MORPH_POLICY:
+                rec = {"policy": policy, "tau": rec["tau"], "split": rec["split"], "epoch": rec["epoch"], "fallback": by}
+            tau_dev = row[:, 0].contiguous()
         key = MX.format_threshold_key(args.dataset_name, "val", policy)
         extra = {"thresholds": {key: rec["tau"]}, "threshold_records": {key: rec}}
         record["val_threshold"] = rec
         if rank == 0:
             record.update(metric_records("val", val_logits, val_targets, splits["val"][2], device, args.metrics, tau=tau_dev))
+
+    def curves(record, split, logits, targets):
+        if args.curve_export and rank == 0 and logits.shape[0] > 0:
+            from . import metrics as MX
+            record[f"{split}_curves"] = MX.export_curves(os.path.join(args.output_dir, "curves"), split, MX.positive_probs(logits.to(device)),
+                                                         targets, args.curve_export, device=device)
 
     if "train" in loaders:
         for epoch in range(args.epochs):
@@ -274,6 +351,7 @@ def run(args):
                     select(record, epoch + 1)   # the record's epoch is the checkpoint's
                 elif args.metrics and rank == 0:
                     record.update(metric_records("val", val_logits, val_targets, splits["val"][2], device))
+                curves(record, "val", val_logits, val_targets)
             log(record)
             save_cls_checkpoint(os.path.join(args.output_dir, "ckpts", f"finetune_e{epoch + 1}.pth"), epoch + 1, model, opt,
                                 loss=record.get("val_loss", stats.loss), extra=extra,
@@ -285,6 +363,7 @@ def run(args):
             select(record, 0)
         elif args.metrics and rank == 0:
             record.update(metric_records("val", val_logits, val_targets, splits["val"][2], device))
+        curves(record, "val", val_logits, val_targets)
         log(record)
     if "test" in loaders:
         test_logits, test_targets, _ = evaluate_cls(model, loaders["test"], device, shard=False, return_probs=True)
@@ -296,6 +375,10 @@ def run(args):
                 record["test_threshold"] = {"policy": FROZEN_POLICY, "tau": frozen[0], "source_key": frozen[1],
                                             "source_policy": frozen[2].get("policy"), "source_split": frozen[2].get("split"),
                                             "source_checkpoint": str(args.threshold_from)}
+        if args.group_metrics and rank == 0:
+            record.update(group_records(test_logits, test_targets, splits["test"][2], device, args.group_metrics, args.bootstrap,
+                                        args.bootstrap_seed, tau=tau_dev))
+        curves(record, "test", test_logits, test_targets)
         log(record)
     if world > 1:
         dist.destroy_process_group()
