@@ -64,11 +64,12 @@ def test_library_exports_every_declared_symbol(built):
     assert handle.pm_wgrad_group_workspace_bytes(group(dec, ()), 4, 2112, _lib.PM_BF16) == 0
 
 
-def _gemm_plan(handle, a_kmajor, b_kmajor, in_dtype, has_bias, c_dtype, epilogue, M, N, K, max_blocks=0, variant=0, ws_bytes=0):
+def _gemm_plan(handle, a_kmajor, b_kmajor, in_dtype, has_bias, c_dtype, epilogue, M, N, K, max_blocks=0, variant=0, ws_bytes=0,
+               ldc_is_n=1):
     """pm_gemm_plan -> (status, (family, cfg, tile_m, tile_n, split_k, band, ws_bytes))."""
     from ssl4polyp_amd import _lib
     opts, info = _lib.GemmOpts(max_blocks, variant), _lib.GemmPlanInfo()
-    st = handle.pm_gemm_plan(a_kmajor, b_kmajor, in_dtype, has_bias, c_dtype, 1, epilogue, M, N, K, ws_bytes, ctypes.byref(opts),
+    st = handle.pm_gemm_plan(a_kmajor, b_kmajor, in_dtype, has_bias, c_dtype, ldc_is_n, epilogue, M, N, K, ws_bytes, ctypes.byref(opts),
                              ctypes.byref(info))
     return st, (info.family, info.cfg, info.tile_m, info.tile_n, info.split_k, info.band, info.ws_bytes)
 
@@ -139,6 +140,88 @@ def test_gemm_dispatch_table(built):
     assert _gemm_plan(handle, 0, 0, BF16, 0, BF16, E.EPI_STORE, 0, 264, 64)[0] == _lib.PM_ESHAPE
     assert _gemm_plan(handle, 0, 0, BF16, 0, BF16, E.EPI_STORE, 128, 264, 36)[0] == _lib.PM_EALIGN
     assert _gemm_plan(handle, 0, 0, BF16, 0, BF16, E.EPI_RESIDUAL, 128, 264, 64)[0] == _lib.PM_EINVAL  # f32 residual stream only
+
+
+def test_gemm_case_table_reaches_every_plan(built):
+    """tests/gemm_cases.py (what tests/test_gpu_gemm_edges.py runs and tests/test_gemm_ref_cpu.py emulates) against pm_gemm_plan: each
+    case plans to the family / cfg / tile / k-slices / band it claims, and the table reaches every combination the plan can name --
+    every family with every operand type and layout pair the launcher dispatches for it, every ring configuration with each W layout
+    it is built for (found by asking the plan for every variant value, so a new cfg without cases fails here), both weight-gradient
+    tiles, one slice / ragged slices / the cap of 16, band 0 and band 6, the 8-wide and the 4-wide stores of a 16-bit C by both
+    triggers, and each epilogue on each family that accepts it."""
+    import gemm_cases as G
+    from ssl4polyp_amd import _lib
+    handle = _lib.load()
+    DT = {"bf16": _lib.PM_BF16, "fp16": _lib.PM_F16, "fp32": _lib.PM_F32}
+    EPI = {"store": _lib.EPI_STORE, "gelu": _lib.EPI_GELU, "resid": _lib.EPI_RESIDUAL, "dgelu": _lib.EPI_DGELU, "accum": _lib.EPI_ACCUM}
+    FAM = {_lib.GEMM_GENERIC: "generic", _lib.GEMM_LDS128: "lds128", _lib.GEMM_RING: "ring", _lib.GEMM_RING_WGRAD: "wgrad"}
+    assert len({G.case_id(c) for c in G.CASES}) == len(G.CASES)
+    for c in G.CASES:
+        st, plan = _gemm_plan(handle, int(G.a_kmajor(c)), int(G.b_kmajor(c)), DT[c.in_dt], int(c.bias), DT[c.c_dt], EPI[c.epi], c.M,
+                              c.N, c.K, c.max_blocks, c.variant, G.ws_bytes(c), int(c.pc == 0))
+        assert st == 0, (G.case_id(c), st)
+        assert (FAM[plan[0]], plan[1], (plan[2], plan[3]), plan[4], plan[5]) == (c.family, c.cfg, c.tile, c.split, c.band), \
+            (G.case_id(c), plan)
+        if c.split > 1:
+            assert plan[6] == c.split * c.M * c.N * 4 <= G.ws_bytes(c), (G.case_id(c), plan)
+
+    def reached(family, *fields):
+        return {tuple(getattr(c, f) if isinstance(f, str) else f(c) for f in fields) for c in G.CASES if c.family == family}
+    # the two 128 x 128 kernels: PM_DISPATCH_ACT x with_layouts, and every epilogue with every C type the plan accepts for it
+    small = {(lay, dt, epi, c_dt) for lay in G.LAYOUTS for dt in G.DTYPES for epi in G.EPILOGUES for c_dt in G.c_dtypes(dt, epi)}
+    for fam in ("generic", "lds128"):
+        assert reached(fam, "layout", "in_dt", "epi", "c_dt") >= small, (fam, small - reached(fam, "layout", "in_dt", "epi", "c_dt"))
+        for lay in G.LAYOUTS:   # per layout and operand type: 1, 2 and 3 k-steps, the ragged pair of tiles and the 4-column problem
+            for dt in G.DTYPES:
+                sel = [c for c in G.CASES if (c.family, c.layout, c.in_dt, c.split, c.ws) == (fam, lay, dt, 1, 0)]
+                ke = 64 if dt != "fp32" else 32
+                assert {-(-c.K // ke) for c in sel} == {1, 2, 3} and {c.M > 128 and c.N > 128 for c in sel} == {True, False}
+                assert any(c.pa for c in sel) and any(c.pb for c in sel) and any(c.pc for c in sel)
+    assert min(c.K for c in G.CASES if c.family == "generic" and c.in_dt != "fp32") == 8      # less than one k-step
+    assert any(c.N == 4 for c in G.CASES if c.family == "lds128") and any(c.N == 4 for c in G.CASES if c.family == "generic")
+    # split-K behind the LDS-DMA kernel: ragged slices and the fall-back to one slice, STORE and ACCUM, every operand type
+    for dt in G.DTYPES:
+        for epi in ("store", "accum"):
+            sel = [c for c in G.CASES if (c.family, c.in_dt, c.epi) == ("lds128", dt, epi) and c.ws]
+            nk = lambda c: c.K // (64 if dt != "fp32" else 32)
+            assert {c.split for c in sel if nk(c) % -(-nk(c) // c.split)} == {2, 5}          # the last slice is shorter
+            assert any(c.split == 1 and 0 < c.ws < 2 * c.M * c.N * 4 for c in sel)           # no slab fits: one slice
+    # ring: what the plan accepts as a forced variant is what RING_PAIRS mirrors, with the W layouts it is built for
+    from test_gpu_ops import RING_PAIRS
+    nameable = set()
+    for cfg in range(2, 64):
+        for wk in (0, 1):
+            if _gemm_plan(handle, 0, wk, _lib.PM_BF16, 0, _lib.PM_BF16, _lib.EPI_STORE, 1031, 264, 64, 0, cfg)[0] == 0:
+                nameable.add((cfg, "nn" if wk else "nt"))
+    assert {cfg for cfg, _ in nameable} == set(RING_PAIRS) - {1}
+    assert nameable == {(cfg, lay) for cfg, pairs in RING_PAIRS.items() if cfg != 1 for lay, _ in pairs}
+    assert reached("ring", "cfg", "layout", "in_dt") == {(cfg, lay, dt) for cfg, lay in nameable for dt in ("bf16", "fp16")}
+    assert reached("ring", "cfg", "layout", "epi") == {(cfg, lay, epi) for cfg, ps in RING_PAIRS.items() if cfg != 1 for lay, epi in ps}
+    for cfg, pairs in RING_PAIRS.items():
+        if cfg == 1:
+            continue
+        sel = [c for c in G.CASES if c.family == "ring" and c.cfg == cfg]
+        assert {c.K for c in sel} == {64, 128, 192, 320} and {c.band for c in sel} == {0, 6}
+        assert any(c.pa == 8 for c in sel) and any(c.pb for c in sel)
+        for lay, epi in pairs:
+            if epi not in ("store", "gelu", "dgelu"):
+                continue
+            for dt in ("bf16", "fp16"):   # a 16-bit C: 16-byte stores, and the 4-wide fallback by N & 7 and by ldc & 7
+                widths = {(G.store_width(c), c.N % 8 != 0, c.pc % 8 != 0) for c in sel if (c.layout, c.epi, c.in_dt) == (lay, epi, dt)}
+                want = {(8, False, False), (4, False, True)} | ({(4, True, False)} if lay == "nt" else set())  # (k-major W: N % 8 == 0)
+                assert widths >= want, (cfg, lay, epi, dt, widths)
+    # ring weight gradients: both tiles, forced and chosen; one slice, even slices, ragged slices, a lowered split, the cap
+    for dt in ("bf16", "fp16"):
+        for epi in ("store", "accum"):
+            sel = [c for c in G.CASES if (c.family, c.in_dt, c.epi) == ("wgrad", dt, epi)]
+            assert {(c.variant >> 6, c.tile) for c in sel} >= {(1, (256, 128)), (2, (256, 256)), (0, (256, 128)), (0, (256, 256))}
+            for tile in ((256, 128), (256, 256)):
+                assert {c.split for c in sel if c.tile == tile} >= {4} and {c.M for c in sel if c.tile == tile} == {264, 520}
+            assert {c.split for c in sel} == {1, 2, 4, 16}
+            assert any(c.split == 2 and 0 < c.ws < 4 * c.M * c.N * 4 for c in sel)                     # lowered by the workspace
+            assert any(c.split > 1 and (c.K // 32) % -(-(c.K // 32) // c.split) for c in sel)          # a ragged last slice
+            assert any(c.split == 16 and (c.K // 32) // 16 > 16 for c in sel)                          # the cap, not the k-step rule
+    assert set(FAM.values()) == {c.family for c in G.CASES}
 
 
 def _attention_plan(handle, backward, B, N, H, dh, dtype):
