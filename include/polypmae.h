@@ -604,6 +604,42 @@ int pm_loss_scale_update(float* state, const float* stats, float* hyper, int n_g
  * (the device-side counterpart of tc.py:1437-1454 _compute_grad_norm and misc.py:387-400 detect_grad_anomalies). */
 int pm_grad_stats(const float* g, long n, float* out, void* stream);
 
+/* Per-group gradient norms and clipping by global norm, deterministic (no float atomics): the reference's per-group norms after
+ * scaler.unscale_ (train_classification.py:4534-4544, _compute_grad_norm :1437-1454) and its clip_grad_norm_ between unscale_ and
+ * step (mae/util/misc.py:268-279), without touching the update kernels: the clip coefficient goes into slot [10] of the AdamW
+ * records, the factor pm_adamw_dev already multiplies every gradient by ([10] = 1 / loss scale x clip coefficient; 0 = neither).
+ *
+ * pm_grad_norms: one pass over `n_segs` flat f32 gradient ranges (n % 4 == 0, 16-byte aligned; padding holds zeros), each
+ * belonging to one of `n_groups` groups.  Every value is squared and accumulated in f64 by a fixed map and fixed trees; the grid
+ * depends on the segment sizes only, so the bits do not depend on stream, overlap or capture.  Writes
+ *   sumsq f64 [n_groups]  sum(g^2) per group (0 for a group without a segment)
+ *   stats f32 [3]         [sum(g^2), #NaN, #Inf] over everything, pm_grad_stats' layout (overwritten, not accumulated): what
+ *                         pm_loss_scale_update reads, so this pass REPLACES the pm_grad_stats pass of a loss-scaled step.
+ * workspace: caller-owned, 8-byte aligned, at least pm_grad_norms_workspace(n_segs, n_groups) bytes; fully rewritten.
+ *
+ * pm_grad_clip: one small launch.  With s_g = record_g[5] x (scaled && record_g[10] != 0 ? record_g[10] : 1) -- `scaled` says
+ * that pm_loss_scale_update wrote [10] THIS step; without it [10] counts as 1 whatever an earlier clip left there --
+ *   total = sqrt(sum_g sumsq[g] s_g^2),  coef = min(1, max_norm / (total + 1e-6))   (torch.nn.utils.clip_grad_norm_, in f64)
+ * and, when `clip` is set, record_g[10] = (scaled && [10] != 0 ? [10] : 1) x coef for every group (one f32 rounding; coef and the
+ * product are held to >= FLT_MIN so that [10] never becomes the 0 that means "no scaling").  A non-finite total gives a
+ * non-finite coef, as torch does: under loss scaling the skip flag [9] is set then and the update touches nothing; without a
+ * scaler the update applies NaN, exactly like clip_grad_norm_ + step.  clip == 0: norms only, coef = 1, `hyper` is left alone.
+ *   record f64 [n_groups + 3]  sqrt(sumsq[g]) s_g per group, total, coef, max_norm (+inf when clip == 0)
+ * Launch order on one stream:
+ *   pm_grad_norms, [pm_loss_scale_update(stats),] pm_grad_clip, pm_adamw_tick, pm_adamw_dev ... (or pm_adamw_segments)
+ * Refusals return before any stream call: PM_EINVAL (a NULL pointer, a group index outside [0, n_groups), a short workspace,
+ * clip with max_norm <= 0 or NaN), PM_ESHAPE (no segments or groups, n <= 0, n % 4 != 0), PM_EALIGN. */
+typedef struct pm_grad_segment {
+  const float* g;
+  long n;
+  int group;
+} pm_grad_segment;
+int pm_grad_norms_workspace(int n_segs, int n_groups, size_t* bytes);
+int pm_grad_norms(const pm_grad_segment* segs, int n_segs, int n_groups, void* workspace, size_t ws_bytes, double* sumsq,
+                  float* stats, void* stream);
+int pm_grad_clip(const double* sumsq, float* hyper, int n_groups, double max_norm, int clip, int scaled, double* record,
+                 void* stream);
+
 /* Scratch sizes.  Every workspace is caller-owned; these return the byte count that enables the deterministic
  * (two-stage, fixed-order) form of the op for the given shape, 0 when the op needs none.
  *   pm_gemm_workspace_bytes: the split-K slabs pm_gemm_ws / pm_gemm_ex would use for this GEMM under `opts`.

@@ -83,6 +83,9 @@ SIGNATURES = {
     "pm_adamw_grid": [L, I],
     "pm_grad_stats": [P, L, P, P],
     "pm_loss_scale_update": [P, P, P, I, F, F, I, P],
+    "pm_grad_norms_workspace": [I, I, P],
+    "pm_grad_norms": [P, I, I, P, ctypes.c_size_t, P, P, P],
+    "pm_grad_clip": [P, P, I, ctypes.c_double, I, I, P, P],
     "pm_dgelu": [P, P, P, I, L, P],
     "pm_boot_metrics_workspace": [I, I, I, I, I, P],
     "pm_boot_metrics": [P, P, P, P, P, P, P, I, I, I, I, I, I, P, ctypes.c_size_t, P],
@@ -131,6 +134,11 @@ class AdamwSegment(ctypes.Structure):
     """pm_adamw_segment of include/polypmae.h."""
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("shadow", c_void_p), ("shadow_dtype", c_int),
                 ("n", c_long), ("hyper", c_void_p), ("done_event", c_void_p)]
+
+
+class GradSegment(ctypes.Structure):
+    """pm_grad_segment of include/polypmae.h."""
+    _fields_ = [("g", c_void_p), ("n", c_long), ("group", c_int)]
 
 
 class BlockBwdDesc(ctypes.Structure):

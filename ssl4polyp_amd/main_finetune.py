@@ -82,6 +82,10 @@ def get_args_parser():
     p.add_argument("--output_dir", default="./output_dir")
     p.add_argument("--seed", default=0, type=int)
     p.add_argument("--log_every", default=20, type=int)
+    p.add_argument("--clip_grad", type=float, default=None, metavar="NORM",
+                   help="clip the gradient by global norm inside the optimizer step (default: no clipping); the log records then "
+                        "carry grad_norm_groups, grad_norm and clip_coef")
+    p.add_argument("--group_grad_norms", action="store_true", help="log one gradient norm per param group")
     p.add_argument("--metrics", action="store_true",
                    help="log the binary metrics of val and test at tau = 0.5 (AUPRC, AUROC, recall, precision, F1, balanced accuracy, MCC, loss)")
     p.add_argument("--bootstrap", default=0, type=int, metavar="R",
@@ -342,7 +346,7 @@ def run(args):
                 g["lr"] = args.lr * factor
             stats = train_epoch_cls(ddp, loaders["train"], opt, device, pos_weight=pos_weight, log_every=args.log_every,
                                     printer=(lambda r: print(f"epoch {epoch} {json.dumps(r)}", flush=True)) if rank == 0 else None,
-                                    loss_scaler=scaler)
+                                    loss_scaler=scaler, clip_grad=args.clip_grad, group_grad_norms=args.group_grad_norms)
             record = {"epoch": epoch, "train_loss": stats.loss, "lr": stats.lr, "samples_per_sec": stats.samples_per_sec}
             if "val" in loaders:
                 val_logits, val_targets, _ = evaluate_cls(model, loaders["val"], device, shard=False, return_probs=True)

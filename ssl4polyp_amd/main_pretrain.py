@@ -69,6 +69,8 @@ def get_args_parser():
     p.add_argument("--synthetic", default=0, type=int, help="number of synthetic batches per epoch (instead of --data_path)")
     p.add_argument("--save_every", default=1, type=int)
     p.add_argument("--log_every", default=20, type=int)
+    p.add_argument("--clip_grad", type=float, default=None, metavar="NORM",
+                   help="clip the gradient by global norm inside the optimizer step (default: no clipping)")
     return p
 
 

@@ -6,13 +6,17 @@ decay / no-decay groups from timm ``add_weight_decay``, betas (0.9, 0.95)), but 
 contiguous flat segment instead of ~150 tensors, and the same launch refreshes the bf16 shadow weights the
 MFMA GEMMs read.  ``grad_stats`` replaces the per-parameter host-synchronising loops of
 train_classification.py:1437-1454 (_compute_grad_norm) and mae/util/misc.py:387-400 (detect_grad_anomalies)
-with one pass that stays on the device.
+with one pass that stays on the device.  ``step(max_norm=...)`` clips by global norm where the reference calls
+``clip_grad_norm_`` between ``unscale_`` and ``step`` (mae/util/misc.py:268-279), and ``grad_norms`` returns the
+per-group norms of train_classification.py:4534-4544: one deterministic f64 pass, the coefficient folded into the factor
+the update already multiplies every gradient by.
 """
 from __future__ import annotations
 
 from typing import Dict, Iterable, List, Optional
 
 import contextlib
+import ctypes
 
 import torch
 
@@ -139,13 +143,96 @@ class FusedAdamW(torch.optim.Optimizer):
                 self._hyper[:, :6].copy_(torch.tensor(rows, dtype=torch.float32))
             self._hyper_host = rows
 
+    # -- clipping by global norm and per-group norms (pm_grad_norms / pm_grad_clip) -------------------------------
+    def _clip_buffers(self, f, n_segs):
+        """Workspace, f64 sums, f32 triple and f64 record of the norm kernels: allocated once (outside capture: a GraphedStep runs
+        its eager warm-up steps first), at fixed addresses, so that a captured step replays them."""
+        G = len(self.param_groups)
+        size = ctypes.c_size_t(0)
+        _lib.check(self._rt.k.lib.pm_grad_norms_workspace(n_segs, G, ctypes.byref(size)), "pm_grad_norms_workspace")
+        b = getattr(self, "_clip_buf", None)
+        if b is None or b["ws"].device != f.device or b["ws"].numel() * 8 < size.value or b["sumsq"].numel() != G:
+            b = self._clip_buf = {"ws": torch.zeros((size.value + 7) // 8, dtype=torch.float64, device=f.device),
+                                  "sumsq": torch.zeros(G, dtype=torch.float64, device=f.device),
+                                  "stats": torch.zeros(3, dtype=torch.float32, device=f.device),
+                                  "record": torch.zeros(G + 3, dtype=torch.float64, device=f.device),
+                                  "norms": torch.zeros(G + 3, dtype=torch.float64, device=f.device)}
+        return b
+
+    def _grad_segment_array(self, f, stat_segs):
+        """pm_grad_segment array of [(group, region, lo, hi)], rebuilt only when the segments or the gradient buffers change."""
+        key = (tuple(stat_segs),) + tuple(f.G[r].data_ptr() for r in ("mat", "vec"))
+        if getattr(self, "_gseg_key", None) != key:
+            arr = (_lib.GradSegment * len(stat_segs))()
+            for i, (gi, r, lo, hi) in enumerate(stat_segs):
+                arr[i] = _lib.GradSegment(_ptr(f.G[r][lo:hi]), hi - lo, gi)
+            self._gseg_key, self._gseg_args = key, arr
+        return self._gseg_args
+
+    def _grad_norms_pass(self, f, stat_segs, stats=None):
+        """The statistics pass on the current stream: per-group f64 sums into the optimizer's buffer, the f32 triple into `stats`
+        (default: the optimizer's own).  Returns the buffers."""
+        b = self._clip_buffers(f, len(stat_segs))
+        _lib.check(self._rt.k.lib.pm_grad_norms(self._grad_segment_array(f, stat_segs), len(stat_segs), len(self.param_groups),
+                                                _ptr(b["ws"]), b["ws"].numel() * 8, _ptr(b["sumsq"]),
+                                                _ptr(stats if stats is not None else b["stats"]), _stream()), "pm_grad_norms")
+        return b
+
+    @property
+    def last_clip(self) -> Optional[torch.Tensor]:
+        """Device record of the last step taken with `max_norm`, f64 [G + 3]: the norm of each group's gradient as the update
+        consumed it (times grad_scale, divided by the loss scale), the total norm before clipping, the clip coefficient,
+        max_norm.  None before the first clipped step.  The tensor is rewritten by every clipped step: clone it to keep a value."""
+        b = getattr(self, "_clip_buf", None)
+        if b is None or not getattr(self, "_clip_seen", False):
+            return None
+        if getattr(self, "_clip_ev", None) is not None:  # written by an overlapped step, on the side stream
+            torch.cuda.current_stream(b["record"].device).wait_event(self._clip_ev)
+        return b["record"]
+
     @torch.no_grad()
-    def step(self, closure=None, loss_scaler: "Optional[LossScaler]" = None):
+    def grad_norms(self, loss_scaler: "Optional[LossScaler]" = None) -> torch.Tensor:
+        """f64 device tensor [G + 1]: the gradient norm of every param group, then the global norm (no host sync) -- of the
+        gradient as the update will consume it: times grad_scale (so on N ranks it is the norm of the averaged gradient), and
+        divided by `loss_scaler`'s current scale when one is given.  What the reference's `_compute_grad_norm(group["params"])`
+        returns after scaler.unscale_ (train_classification.py:4534-4544).  A group without gradients reports 0."""
+        f = self._ensure_state()
+        self._rt.wait_updates()
+        if self.grad_sync is not None:
+            self.grad_sync.wait()
+        G = len(self.param_groups)
+        capturing = f.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+        if not capturing or getattr(self, "_hyper", None) is None:
+            self.sync_hyper()
+        stat_segs = [(gi, r, lo, hi) for gi, group in enumerate(self.param_groups) for r, lo, hi in self._segments(f, group)]
+        if not stat_segs:
+            return torch.zeros(G + 1, dtype=torch.float64, device=f.device)
+        b = self._grad_norms_pass(f, stat_segs)
+        _lib.check(self._rt.k.lib.pm_grad_clip(_ptr(b["sumsq"]), _ptr(self._hyper), G, 0.0, 0, 0, _ptr(b["norms"]), _stream()),
+                   "pm_grad_clip")
+        out = b["norms"][:G + 1].clone()
+        if loss_scaler is not None and loss_scaler.enabled:
+            state, _ = loss_scaler._device_state(f.device)
+            out /= state[0].double()
+        return out
+
+    @torch.no_grad()
+    def step(self, closure=None, loss_scaler: "Optional[LossScaler]" = None, max_norm: Optional[float] = None):
         """loss_scaler: the gradients carry its loss scale (precision mode fp16).  The update then starts with one statistics
         pass over them and `pm_loss_scale_update` -- found_inf, the skip flag and 1/scale go into the device-side hyper records,
         the scale moves (GradScaler.step + update, train_classification.py:4545-4546) -- and `pm_adamw_dev` unscales inside
-        the update or returns untouched on a non-finite step: no host read-back anywhere."""
+        the update or returns untouched on a non-finite step: no host read-back anywhere.
+        max_norm: clip the gradients by global norm first, `torch.nn.utils.clip_grad_norm_(params, max_norm)` between unscale_ and
+        step (mae/util/misc.py:268-279), on the device: one deterministic statistics pass (`pm_grad_norms`; under a loss scaler
+        it replaces the `pm_grad_stats` pass, the gradients are read once), `pm_loss_scale_update`, `pm_grad_clip` -- which folds
+        min(1, max_norm / (norm + 1e-6)) into the factor the unchanged update kernels multiply every gradient by -- then the
+        update as without it.  The norm is that of the gradient the update consumes (times grad_scale, divided by the loss
+        scale); `last_clip` holds the per-group norms, the total, the coefficient.  The flat gradients themselves are not
+        rewritten.  A non-finite norm without a loss scaler gives NaN parameters, as clip_grad_norm_ + step does.  max_norm is a
+        kernel argument: a GraphedStep replays the value it was captured with."""
         loss = None
+        if max_norm is not None and not float(max_norm) > 0.0:
+            raise _lib.PolypMaeError(f"FusedAdamW.step: max_norm must be positive, got {max_norm}")
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
@@ -165,10 +252,13 @@ class FusedAdamW(torch.optim.Optimizer):
             for r, lo, hi in self._segments(f, group):
                 work.append((gi, r, lo, hi))
         scaled = loss_scaler is not None and loss_scaler.enabled
-        stat_segs = [(r, lo, hi) for _, r, lo, hi in work] if scaled else []
-        if not scaled and getattr(self, "_scaler_used", False):  # a scaler was dropped: clear its skip flag / unscale factor
+        clip = max_norm is not None and bool(work)
+        stat_segs = list(work) if (scaled or clip) else []
+        if not scaled and (getattr(self, "_scaler_used", False) or (getattr(self, "_clip_used", False) and not clip)):
+            # a scaler or max_norm was dropped: clear the skip flag / the factor it left in [10]
             self._hyper[:, 9:11] = 0.0
             self._scaler_used = False
+        self._clip_used = clip
         if overlap:
             # forward order: vectors first, then the matrices by offset, cut at the block boundaries so that the next
             # forward can start on block 0 while the later blocks are still being updated
@@ -185,7 +275,7 @@ class FusedAdamW(torch.optim.Optimizer):
             side = rt.k.side_stream(f.device)
             ev = self._event(-1, side)
             ev.record(main)
-            if scaled or not work:
+            if scaled or clip or not work:
                 side.wait_event(ev)
             stream_ctx = torch.cuda.stream(side)
         else:
@@ -193,18 +283,32 @@ class FusedAdamW(torch.optim.Optimizer):
         with stream_ctx:
             if scaled:
                 state, stats = loss_scaler._device_state(f.device)
-                stats.zero_()
-                for r, lo, hi in stat_segs:
-                    _lib.check(lib.pm_grad_stats(_ptr(f.G[r][lo:hi]), hi - lo, _ptr(stats), _stream()), "pm_grad_stats")
+                if clip:  # one pass gives the per-group sums AND the triple the scale update reads
+                    self._grad_norms_pass(f, stat_segs, stats)
+                else:
+                    stats.zero_()
+                    for _, r, lo, hi in stat_segs:
+                        _lib.check(lib.pm_grad_stats(_ptr(f.G[r][lo:hi]), hi - lo, _ptr(stats), _stream()), "pm_grad_stats")
                 _lib.check(lib.pm_loss_scale_update(_ptr(state), _ptr(stats), _ptr(self._hyper), len(self.param_groups),
                                                     loss_scaler.growth_factor, loss_scaler.backoff_factor,
                                                     loss_scaler.growth_interval, _stream()), "pm_loss_scale_update")
                 self._scaler_used = True
+            elif clip:
+                self._grad_norms_pass(f, stat_segs)
+            if clip:
+                b = self._clip_buf
+                _lib.check(lib.pm_grad_clip(_ptr(b["sumsq"]), _ptr(self._hyper), len(self.param_groups), float(max_norm), 1,
+                                            1 if scaled else 0, _ptr(b["record"]), _stream()), "pm_grad_clip")
+                self._clip_seen = True
+                self._clip_ev = None
+                if overlap:  # the record is written on the side stream: `last_clip` makes its reader's stream wait for it
+                    self._clip_ev = self._event(-2, side)
+                    self._clip_ev.record(side)
             if overlap and work:
                 # the whole update in ONE C call: [wait for the main stream's event,] tick, then launch + done event per segment
                 segs, events = self._segment_array(f, work, side)
                 _lib.check(lib.pm_adamw_segments(segs, len(work), _ptr(self._hyper), len(self.param_groups),
-                                                 None if scaled else ev.cuda_event, _stream(), self.OVERLAP_MAX_BLOCKS),
+                                                 None if (scaled or clip) else ev.cuda_event, _stream(), self.OVERLAP_MAX_BLOCKS),
                            "pm_adamw_segments")
                 rt.pending_updates += [(r, lo, hi, done) for (_, r, lo, hi), done in zip(work, events)]
                 return loss
@@ -374,7 +478,10 @@ class LossScaler:
         return _ScaleLossFn.apply(loss, state[0:1])
 
     def unscale_(self, optimizer) -> None:
-        """No-op: FusedAdamW unscales inside its update (see the class comment)."""
+        """No-op: FusedAdamW unscales inside its update (see the class comment), so the flat gradients are STILL multiplied by the
+        loss scale after this call.  Do not follow it with `torch.nn.utils.clip_grad_norm_`: that would clip scaled gradients
+        without any error.  Clip with `scaler.step(optimizer, max_norm=...)` (FusedAdamW.step), which clips the unscaled
+        gradient on the device; `optimizer.grad_norms(scaler)` gives the unscaled per-group norms."""
 
     def step(self, optimizer, *args, **kwargs):
         if not isinstance(optimizer, FusedAdamW):

@@ -111,6 +111,8 @@ class EpochStats:
     seconds: float = 0.0
     lr: float = 0.0
     history: List[Dict[str, float]] = field(default_factory=list)
+    grad_norm_groups: Dict[str, float] = field(default_factory=dict)  # last logged per-group norms (clip_grad / group_grad_norms)
+    clip_coef: float = float("nan")     # last logged clip coefficient
 
     @property
     def samples_per_sec(self) -> float:
@@ -121,8 +123,41 @@ def _world() -> int:
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
-def _flush(stats: EpochStats, acc: torch.Tensor, gstats: Optional[torch.Tensor], step: int, lr: float, printer):
-    """One host read-back (+ one tiny all-reduce) per log interval: acc = [sum(loss), n_steps]."""
+def _group_names(optimizer) -> List[str]:
+    """train_classification.py:4537-4539: a param group is logged under its "name", else under group<idx>."""
+    return [group.get("name") or f"group{idx}" for idx, group in enumerate(optimizer.param_groups)]
+
+
+def _clip_step(optimizer, loss_scaler, clip_grad):
+    """optimizer.step / loss_scaler.step + update, with `max_norm=clip_grad` when clipping is on (FusedAdamW only: the clip runs
+    inside its device kernels)."""
+    kw = {}
+    if clip_grad is not None:
+        if not hasattr(optimizer, "last_clip"):
+            raise TypeError("clip_grad needs ssl4polyp_amd.optim.FusedAdamW (the clip runs inside its device kernels)")
+        kw["max_norm"] = float(clip_grad)
+    if loss_scaler is not None:
+        return lambda: (loss_scaler.step(optimizer, **kw), loss_scaler.update())
+    return (lambda: optimizer.step(**kw)) if kw else optimizer.step
+
+
+def _logged_norms(optimizer, loss_scaler, clipped: bool) -> torch.Tensor:
+    """f64 device tensor [G + 2] for _flush (no host sync).  clipped: call AFTER the step, copies what the clipped step recorded;
+    otherwise call BEFORE the step: one norms pass over the gradients, coefficient 1."""
+    if clipped:
+        return optimizer.last_clip[:-1].clone()
+    if not hasattr(optimizer, "grad_norms"):
+        raise TypeError("group_grad_norms needs ssl4polyp_amd.optim.FusedAdamW (the norms are computed by its device kernels)")
+    gn = optimizer.grad_norms(loss_scaler)
+    return torch.cat([gn, gn.new_ones(1)])
+
+
+def _flush(stats: EpochStats, acc: torch.Tensor, gstats: Optional[torch.Tensor], step: int, lr: float, printer,
+           norms: Optional[torch.Tensor] = None, names: Optional[List[str]] = None):
+    """One host read-back (+ one tiny all-reduce) per log interval: acc = [sum(loss), n_steps].
+    norms: f64 [G + 2] = per-group gradient norms, total norm, clip coefficient of the last logged step (FusedAdamW.last_clip /
+    grad_norms).  They are norms of the gradient the update consumed -- under data parallelism already the averaged gradient's,
+    equal on every rank -- so they are read as they are, never reduced or rescaled."""
     buf = torch.cat([acc, gstats if gstats is not None else acc.new_zeros(3)])
     if _world() > 1:
         dist.all_reduce(buf)
@@ -136,6 +171,11 @@ def _flush(stats: EpochStats, acc: torch.Tensor, gstats: Optional[torch.Tensor],
         rec.update(grad_norm=math.sqrt(max(vals[2], 0.0) / w) / w, grad_nan=int(vals[3]), grad_inf=int(vals[4]))
         stats.grad_norm, stats.grad_nan, stats.grad_inf = rec["grad_norm"], stats.grad_nan + rec["grad_nan"], \
             stats.grad_inf + rec["grad_inf"]
+    if norms is not None:
+        nv = norms.tolist()
+        G = len(nv) - 2
+        rec.update(grad_norm_groups=dict(zip(names, nv[:G])), grad_norm=nv[G], clip_coef=nv[G + 1])
+        stats.grad_norm, stats.grad_norm_groups, stats.clip_coef = rec["grad_norm"], rec["grad_norm_groups"], rec["clip_coef"]
     stats.history.append(rec)
     if printer is not None:
         printer(rec)
@@ -147,9 +187,14 @@ def train_one_epoch_mae(model, data_loader: Iterable, optimizer, device, epoch: 
     """engine_pretrain.py:22-100.  `model(samples, mask_ratio=...) -> (loss, pred, mask)`; `args` needs lr, min_lr,
     warmup_epochs, epochs, accum_iter, mask_ratio.  `model` may be a parallel.DataParallel wrapper.
     loss_scaler: optim.LossScaler for precision mode fp16 (engine_pretrain.py:65-72: loss_scaler.scale(loss).backward();
-    loss_scaler.step(optimizer); loss_scaler.update()) -- None for bf16 / fp32."""
+    loss_scaler.step(optimizer); loss_scaler.update()) -- None for bf16 / fp32.
+    args.clip_grad (optional, default off): clip by global norm inside the optimizer step (mae/util/misc.py:268-279); the log
+    records then also carry grad_norm_groups, grad_norm (the total before clipping) and clip_coef."""
     scale = loss_scaler.scale if loss_scaler is not None else (lambda x: x)
-    opt_step = (lambda: (loss_scaler.step(optimizer), loss_scaler.update())) if loss_scaler is not None else optimizer.step
+    clip_grad = getattr(args, "clip_grad", None)
+    opt_step = _clip_step(optimizer, loss_scaler, clip_grad)
+    names = _group_names(optimizer) if clip_grad is not None else None
+    nrm = None
     opt_stats = (lambda: loss_scaler.unscaled_grad_stats(optimizer)) if loss_scaler is not None else \
         getattr(optimizer, "grad_stats", None)
     model.train(True)
@@ -182,14 +227,16 @@ def train_one_epoch_mae(model, data_loader: Iterable, optimizer, device, epoch: 
             if grad_stats and opt_stats is not None and (it // accum + 1) % log_every == 0:
                 gs = opt_stats()
             opt_step()
+            if clip_grad is not None and (it // accum + 1) % log_every == 0:
+                nrm = _logged_norms(optimizer, loss_scaler, True)
             optimizer.zero_grad(set_to_none=True)
         stats.steps += 1
         stats.samples += samples.shape[0] * _world()
         if (it + 1) % (log_every * accum) == 0 or it + 1 == n_iter:
-            s, c = _flush(stats, acc, gs, it + 1, lr, printer)
+            s, c = _flush(stats, acc, gs, it + 1, lr, printer, nrm, names)
             total, count = total + s, count + c
             acc.zero_()
-            gs = None
+            gs = nrm = None
     torch.cuda.synchronize(device) if torch.device(device).type == "cuda" else None
     stats.seconds = time.perf_counter() - t0
     stats.loss = total / max(count, 1.0)
@@ -199,14 +246,22 @@ def train_one_epoch_mae(model, data_loader: Iterable, optimizer, device, epoch: 
 
 def train_epoch_cls(model, train_loader: Iterable, optimizer, device, pos_weight: Optional[torch.Tensor] = None,
                     class_weights: Optional[torch.Tensor] = None, max_batches: Optional[int] = None, log_every: int = 20,
-                    printer: Optional[Callable] = print, grad_stats: bool = True, loss_scaler=None) -> EpochStats:
+                    printer: Optional[Callable] = print, grad_stats: bool = True, loss_scaler=None,
+                    clip_grad: Optional[float] = None, group_grad_norms: bool = False) -> EpochStats:
     """tc.py:4446-4650 hot loop: zero_grad -> model(data) -> BCE/CE -> backward -> grad norm -> optimizer.step().
     Batches are (data, target) or (data, target, meta) as produced by the reference's pack_collate.
     loss_scaler: optim.LossScaler for precision mode fp16 (tc.py:4533-4546: scaler.scale(loss).backward(); scaler.unscale_;
-    grad norms; scaler.step(optimizer); scaler.update()) -- None for bf16 / fp32."""
+    grad norms; scaler.step(optimizer); scaler.update()) -- None for bf16 / fp32.
+    clip_grad: clip by global norm inside the optimizer step (engine_finetune.py:69 --clip_grad through misc.py:268-279).
+    group_grad_norms: log one gradient norm per param group (tc.py:4534-4544).  With either option a log record also carries
+    grad_norm_groups ({group name or group<idx>: norm}), grad_norm (the total norm before clipping) and clip_coef, of the
+    unscaled gradient, read back with the flush; with both off the records, launches and results are unchanged."""
     model.train(True)
     scale = loss_scaler.scale if loss_scaler is not None else (lambda x: x)
-    opt_step = (lambda: (loss_scaler.step(optimizer), loss_scaler.update())) if loss_scaler is not None else optimizer.step
+    opt_step = _clip_step(optimizer, loss_scaler, clip_grad)
+    want_norms = clip_grad is not None or group_grad_norms
+    names = _group_names(optimizer) if want_norms else None
+    nrm = None
     opt_stats = (lambda: loss_scaler.unscaled_grad_stats(optimizer)) if loss_scaler is not None else \
         getattr(optimizer, "grad_stats", None)
     stats = EpochStats()
@@ -227,19 +282,23 @@ def train_epoch_cls(model, train_loader: Iterable, optimizer, device, pos_weight
         scale(loss).backward()
         if grad_stats and opt_stats is not None and (it + 1) % log_every == 0:
             gs = opt_stats()
+        if want_norms and clip_grad is None and (it + 1) % log_every == 0:
+            nrm = _logged_norms(optimizer, loss_scaler, False)
         opt_step()
+        if clip_grad is not None and (it + 1) % log_every == 0:
+            nrm = _logged_norms(optimizer, loss_scaler, True)
         acc[0] += loss.detach()
         acc[1] += 1.0
         stats.steps += 1
         stats.samples += data.shape[0] * _world()
         n = it + 1
         if n % log_every == 0:
-            s, c = _flush(stats, acc, gs, n, optimizer.param_groups[0]["lr"], printer)
+            s, c = _flush(stats, acc, gs, n, optimizer.param_groups[0]["lr"], printer, nrm, names)
             total, count = total + s, count + c
             acc.zero_()
-            gs = None
+            gs = nrm = None
     if n % log_every != 0 and n > 0:
-        s, c = _flush(stats, acc, gs, n, optimizer.param_groups[0]["lr"], printer)
+        s, c = _flush(stats, acc, gs, n, optimizer.param_groups[0]["lr"], printer, nrm, names)
         total, count = total + s, count + c
     torch.cuda.synchronize(device) if torch.device(device).type == "cuda" else None
     stats.seconds = time.perf_counter() - t0
