@@ -216,8 +216,8 @@ int pm_unpad_add(const float* src, long lds, float* dst, long ldd, int rows, int
  * (models_mae.py:155-163; models.py:198-201 / 28-33).  emb f32 [B*keep, D]; x f32 [B, 1+keep, D]. */
 int pm_assemble_tokens(const float* emb, const float* cls, const float* pos, const int* ids_keep, float* x,
                        int B, int keep, int D, void* stream);
-/* Backward: demb[b*keep+j] = dx[b,1+j]; dcls += sum_b dx[b,0]; dpos (optional, learnable pos_embed)
- * += scatter of dx.  demb act-typed [B*keep, D]. */
+/* Backward: demb[b*keep+j] = dx[b,1+j]; dcls (optional) += sum_b dx[b,0]; dpos (optional, learnable pos_embed)
+ * += scatter of dx, row 0 (the cls position) included whether or not dcls is given.  demb act-typed [B*keep, D]. */
 int pm_assemble_tokens_bwd(const float* dx, const int* ids_keep, void* demb, int act_dtype, float* dcls, float* dpos,
                            int B, int keep, int D, void* stream);
 
@@ -241,15 +241,15 @@ int pm_mae_unshuffle_bwd(const float* dout, const int* ids_shuffle, void* demb, 
                          int B, int L, int keep, int D, void* workspace, size_t ws_bytes, void* stream);
 
 /* MAE reconstruction loss (models_mae.py:95-107,198-214): fused patchify + (optional norm_pix) + per-patch MSE.
- * pred f32 rows of `ldp` elements; row (b*(L+1)+1+l) holds patch l of sample b when has_cls_row=1 (the
+ * pred f32 rows of `ldp` elements (ldp >= p*p*C, a multiple of 4; anything else: PM_ESHAPE); row (b*(L+1)+1+l) holds patch l of sample b when has_cls_row=1 (the
  * decoder_pred output incl. the cls row), row b*L+l otherwise.  patch_loss f32 [B*L] = mean((pred-target)^2, -1).
  * pm_mae_loss_finish reduces deterministically (single block): sums = {sum(loss*mask), sum(mask)},
  * loss = sums[0]/sums[1]  (models_mae.py:213). */
 int pm_mae_loss_fwd(const float* imgs, const float* pred, long ldp, int has_cls_row, float* patch_loss, int B, int C,
                     int img, int p, int norm_pix, void* stream);
 int pm_mae_loss_finish(const float* patch_loss, const float* mask, long n, float* sums, float* loss, void* stream);
-/* Backward: dpred act-typed [B*(L+has_cls_row), lddp] (lddp >= p*p*C, a multiple of 4; columns beyond p*p*C zeroed),
- * same row order as pred (cls rows and kept patches zeroed); dloss f32 scalar on device. */
+/* Backward: dpred act-typed [B*(L+has_cls_row), lddp] (lddp >= p*p*C, a multiple of 4; columns beyond p*p*C zeroed;
+ * ldp < p*p*C or lddp < p*p*C: PM_ESHAPE), same row order as pred (cls rows and kept patches zeroed); dloss f32 scalar on device. */
 int pm_mae_loss_bwd(const float* imgs, const float* pred, long ldp, int has_cls_row, const float* mask,
                     const float* sums, const float* dloss, void* dpred, long lddp, int act_dtype, int B, int C, int img,
                     int p, int norm_pix, void* stream);

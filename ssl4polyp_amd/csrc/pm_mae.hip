@@ -325,6 +325,7 @@ extern "C" int pm_mae_loss_fwd(const float* imgs, const float* pred, long ldp, i
                                int C, int img, int p, int norm_pix, void* stream) {
   if (!imgs || !pred || !patch_loss) return PM_EINVAL;
   if (B <= 0 || C <= 0 || img <= 0 || p <= 0 || (img % p) || ((p * p * C) & 3) || p * p * C > 1024 || (ldp & 3)) return PM_ESHAPE;
+  if (ldp < (long)p * p * C) return PM_ESHAPE;  // a row of pred holds a whole patch
   const int L = (img / p) * (img / p);
   hipLaunchKernelGGL(loss_fwd_kernel, dim3(cap_grid((long)B * L, 4, 8192)), dim3(256), 0, pm_stream(stream), imgs, pred, ldp,
                      has_cls_row ? 1 : 0, patch_loss, B, L, C, img, p, norm_pix);
@@ -344,7 +345,7 @@ extern "C" int pm_mae_loss_bwd(const float* imgs, const float* pred, long ldp, i
                                int img, int p, int norm_pix, void* stream) {
   if (!imgs || !pred || !mask || !sums || !dloss || !dpred) return PM_EINVAL;
   if (B <= 0 || C <= 0 || img <= 0 || p <= 0 || (img % p) || ((p * p * C) & 3) || p * p * C > 1024 || (ldp & 3)) return PM_ESHAPE;
-  if (lddp < (long)p * p * C || (lddp & 3)) return PM_ESHAPE;
+  if (ldp < (long)p * p * C || lddp < (long)p * p * C || (lddp & 3)) return PM_ESHAPE;
   const int L = (img / p) * (img / p);
   const int hc = has_cls_row ? 1 : 0;
   const dim3 grid(cap_grid((long)B * (L + hc), 4, 8192));

@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void assemble_bwd_kernel(const float* __restri
   }
 }
 
-// dcls[d] += sum_b dx[b, 0, d]   (also dpos[0] when the positional table is learnable)
+// dcls[d] += sum_b dx[b, 0, d]   (also dpos[0] when the positional table is learnable; either pointer may be NULL, not both)
 // The rows are one sample apart (600 KB): a thread that walks all B of them serially pays B dependent-latency loads at the
 // very end of the backward pass, when nothing else runs (27 us at B = 64, 92 us at B = 256).  64 columns per block, the four
 // waves take every fourth sample with four independent accumulators each, partials combined in wave order: fixed order,
@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256) void cls_grad_kernel(const float* __restrict__
   __syncthreads();
   if (wave == 0 && d < D) {
     const float t = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
-    dcls[d] += t;
+    if (dcls) dcls[d] += t;
     if (dpos0) dpos0[d] += t;
   }
 }
@@ -506,7 +506,7 @@ extern "C" int pm_assemble_tokens_bwd(const float* dx, const int* ids_keep, void
   const dim3 grid(cap_grid((long)B * keep, 4, 4096));
   PM_DISPATCH_ACT(act_dtype, T, hipLaunchKernelGGL(assemble_bwd_kernel<T>, grid, dim3(256), 0, pm_stream(stream), dx, ids_keep,
                                                    (T*)demb, dpos, B, keep, D));
-  if (dcls)
+  if (dcls || dpos)  // dpos[0] gets the cls rows' sum whether or not the cls token itself is trained
     hipLaunchKernelGGL(cls_grad_kernel, dim3((D + 63) / 64), dim3(256), 0, pm_stream(stream), dx, dcls, dpos, B,
                        (long)(keep + 1) * D, D);
   return pm_check_launch();
