@@ -640,6 +640,29 @@ int pm_grad_norms(const pm_grad_segment* segs, int n_segs, int n_groups, void* w
 int pm_grad_clip(const double* sumsq, float* hyper, int n_groups, double max_norm, int clip, int scaled, double* record,
                  void* stream);
 
+/* Per-parameter steps (torch.optim.AdamW keeps state[p]["step"] per parameter; a parameter that first receives a gradient at
+ * optimizer step T starts its bias corrections at 1): a param group may own SEVERAL of the 16-float records above, one per
+ * "cohort" of its parameters that share a step history.  The caller writes the group's [0..5] into each of them; [6..8] are the
+ * cohort's own; pm_loss_scale_update takes the record count as its n_groups.  The update kernels are the same: a segment points
+ * at its cohort's record.  Two int lists describe the plan, each given twice: the device copy the kernel reads (fixed address,
+ * so a captured step replays it) and the caller's host copy of the same entries, which is what is checked before any enqueue.
+ *
+ * pm_adamw_tick_list: pm_adamw_tick (same skip rule, same f64 arithmetic, so a cohort at step t holds the bits a group at step t
+ *   holds) for the `n_list` records `list` names, out of `n_records`.  PM_EINVAL: a NULL pointer, an entry outside [0, n_records),
+ *   entries not strictly ascending; PM_ESHAPE: n_list <= 0 or > n_records.
+ * pm_adamw_segments_list: pm_adamw_segments with that tick in place of the tick over every record; every segment's `hyper` must
+ *   point at one of the n_records records (PM_EINVAL).  Checks, wait event, done events and max_blocks as pm_adamw_segments.
+ * pm_grad_clip_cohorts: pm_grad_clip where sumsq holds one sum per RECORD (pm_grad_norms with the segments tagged by record and
+ *   n_groups = n_records) and group_of[r] names record r's group.  A group's sum is the sum of its records' in ascending record
+ *   order, in f64; then pm_grad_clip's arithmetic, s_g read from the group's first record; the new [10] goes into all n_records
+ *   records; `record` is the same f64 [n_groups + 3].  With n_records == n_groups and group_of[r] == r the bits are pm_grad_clip's.
+ *   PM_EINVAL also for an entry of group_of outside [0, n_groups). */
+int pm_adamw_tick_list(float* hyper, int n_records, const int* list, const int* list_host, int n_list, void* stream);
+int pm_adamw_segments_list(const pm_adamw_segment* segs, int n_segs, float* hyper, int n_records, const int* list,
+                           const int* list_host, int n_list, void* wait_event, void* stream, int max_blocks);
+int pm_grad_clip_cohorts(const double* sumsq, float* hyper, int n_records, const int* group_of, const int* group_of_host,
+                         int n_groups, double max_norm, int clip, int scaled, double* record, void* stream);
+
 /* Scratch sizes.  Every workspace is caller-owned; these return the byte count that enables the deterministic
  * (two-stage, fixed-order) form of the op for the given shape, 0 when the op needs none.
  *   pm_gemm_workspace_bytes: the split-K slabs pm_gemm_ws / pm_gemm_ex would use for this GEMM under `opts`.

@@ -86,6 +86,9 @@ SIGNATURES = {
     "pm_grad_norms_workspace": [I, I, P],
     "pm_grad_norms": [P, I, I, P, ctypes.c_size_t, P, P, P],
     "pm_grad_clip": [P, P, I, ctypes.c_double, I, I, P, P],
+    "pm_adamw_tick_list": [P, I, P, P, I, P],
+    "pm_adamw_segments_list": [P, I, P, I, P, P, I, P, P, I],
+    "pm_grad_clip_cohorts": [P, P, I, P, P, I, ctypes.c_double, I, I, P, P],
     "pm_dgelu": [P, P, P, I, L, P],
     "pm_boot_metrics_workspace": [I, I, I, I, I, P],
     "pm_boot_metrics": [P, P, P, P, P, P, P, I, I, I, I, I, I, P, ctypes.c_size_t, P],

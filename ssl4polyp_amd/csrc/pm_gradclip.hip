@@ -166,6 +166,54 @@ __global__ void grad_clip_kernel(const double* __restrict__ sumsq, float* __rest
   record[n_groups + 2] = clip ? max_norm : (double)INFINITY;
 }
 
+// grad_clip_kernel over cohort records (per-parameter steps: a param group owns one AdamW record per cohort, pm_misc.hip).  sumsq
+// has one sum per RECORD; group g's sum is the sum of its records' in ascending record order, and from there on this is
+// grad_clip_kernel's arithmetic expression by expression: with n_records == n_groups and group_of[r] == r the bits are the same
+// (0.0 + x == x for the sums this pass produces, which are never -0).  s_g is read from the group's first record: sync_hyper and
+// pm_loss_scale_update write [5] and [10] alike into all records of a group.  A group without a record reports 0.
+// An entry of group_of outside [0, n_groups) belongs to no group (the host refuses such a map before the launch).
+__global__ void grad_clip_cohorts_kernel(const double* __restrict__ sumsq, float* __restrict__ hyper, int n_records,
+                                         const int* __restrict__ group_of, int n_groups, double max_norm, int clip, int scaled,
+                                         double* __restrict__ record) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  double tot = 0.0;
+  for (int g = 0; g < n_groups; ++g) {
+    double gs = 0.0;
+    int first = -1;
+    for (int r = 0; r < n_records; ++r) {
+      if (group_of[r] != g) continue;
+      if (first < 0) first = r;
+      gs += sumsq[r];
+    }
+    if (first < 0) {
+      record[g] = 0.0;
+      continue;
+    }
+    const float* h = hyper + (long)first * kHyperStride;
+    const float base = (scaled && h[10] != 0.f) ? h[10] : 1.0f;
+    const double s = (double)h[5] * (double)base;
+    record[g] = sqrt(gs) * s;
+    tot += gs * s * s;
+  }
+  const double total = sqrt(tot);
+  double coef = 1.0;
+  if (clip) {
+    coef = max_norm / (total + 1e-6);
+    if (coef > 1.0) coef = 1.0;
+    if (coef < (double)FLT_MIN) coef = (double)FLT_MIN;
+    for (int r = 0; r < n_records; ++r) {
+      float* h = hyper + (long)r * kHyperStride;
+      const float base = (scaled && h[10] != 0.f) ? h[10] : 1.0f;
+      float w = (float)((double)base * coef);
+      if (w < FLT_MIN) w = FLT_MIN;
+      h[10] = w;
+    }
+  }
+  record[n_groups] = total;
+  record[n_groups + 1] = coef;
+  record[n_groups + 2] = clip ? max_norm : (double)INFINITY;
+}
+
 // one row per workgroup of every launch: at most kMaxBlocks per batch of segments
 size_t grad_ws_bytes(int n_segs, int n_groups) {
   const size_t batches = ((size_t)n_segs + kBatch - 1) / kBatch;
@@ -228,5 +276,21 @@ extern "C" int pm_grad_clip(const double* sumsq, float* hyper, int n_groups, dou
   if (clip && !(max_norm > 0.0)) return PM_EINVAL;
   if (((uintptr_t)sumsq & 7) || ((uintptr_t)record & 7)) return PM_EALIGN;
   hipLaunchKernelGGL(grad_clip_kernel, dim3(1), dim3(64), 0, pm_stream(stream), sumsq, hyper, n_groups, max_norm, clip, scaled, record);
+  return pm_check_launch();
+}
+
+// `group_of` is what the kernel reads (device memory at a fixed address); `group_of_host` is the caller's host copy of the same
+// n_records entries, checked here so that a refusal needs no read-back and leaves the stream untouched.
+extern "C" int pm_grad_clip_cohorts(const double* sumsq, float* hyper, int n_records, const int* group_of, const int* group_of_host,
+                                    int n_groups, double max_norm, int clip, int scaled, double* record, void* stream) {
+  if (!sumsq || !hyper || !record || !group_of || !group_of_host) return PM_EINVAL;
+  if (n_groups <= 0 || n_records <= 0 || n_records > (1 << 16) || n_groups > (1 << 16)) return PM_ESHAPE;
+  if (clip && !(max_norm > 0.0)) return PM_EINVAL;
+  for (int r = 0; r < n_records; ++r) {
+    if (group_of_host[r] < 0 || group_of_host[r] >= n_groups) return PM_EINVAL;
+  }
+  if (((uintptr_t)sumsq & 7) || ((uintptr_t)record & 7) || ((uintptr_t)group_of & 3)) return PM_EALIGN;
+  hipLaunchKernelGGL(grad_clip_cohorts_kernel, dim3(1), dim3(64), 0, pm_stream(stream), sumsq, hyper, n_records, group_of, n_groups,
+                     max_norm, clip, scaled, record);
   return pm_check_launch();
 }

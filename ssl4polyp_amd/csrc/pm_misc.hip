@@ -262,6 +262,23 @@ __global__ void adamw_tick_kernel(float* __restrict__ hyper, int n_groups) {
   h[8] = (float)(1.0 / sqrt(1.0 - pow((double)h[2], (double)step)));
 }
 
+// The same tick for the records a device-resident list names (per-parameter steps: a param group owns one record per cohort of
+// parameters that share a step history, and only the cohorts with a gradient this step advance).  Same skip rule, same f64
+// arithmetic: a cohort at step t holds the bits a group at step t holds.  An index outside [0, n_records) is ignored (the host
+// refuses such a list before the launch; the list itself lives in device memory that later code could overwrite).
+__global__ void adamw_tick_list_kernel(float* __restrict__ hyper, int n_records, const int* __restrict__ list, int n_list) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_list) return;
+  const int r = list[i];
+  if (r < 0 || r >= n_records) return;
+  float* h = hyper + (long)r * kHyperStride;
+  if (h[9] != 0.f) return;
+  const float step = h[6] + 1.0f;
+  h[6] = step;
+  h[7] = (float)(1.0 - pow((double)h[1], (double)step));
+  h[8] = (float)(1.0 / sqrt(1.0 - pow((double)h[2], (double)step)));
+}
+
 // The device-hyper-parameter update as a streaming kernel whose footprint the caller bounds (pm_adamw_grid): a workgroup walks
 // chunks of kAdamwUnroll x 256 vectors, and a whole chunk is written as all of a lane's loads of p, g, m, v (64 VGPRs of payload)
 // followed by the arithmetic and the stores, so that a grid of a few hundred workgroups keeps the ~10 MB in flight that HBM rate
@@ -634,6 +651,53 @@ extern "C" int pm_adamw_segments(const pm_adamw_segment* segs, int n_segs, float
   hipStream_t q = pm_stream(stream);
   if (wait_event && hipStreamWaitEvent(q, (hipEvent_t)wait_event, 0) != hipSuccess) return PM_ELAUNCH;
   int st = pm_adamw_tick(hyper, n_groups, stream);
+  if (st != PM_OK) return st;
+  for (int i = 0; i < n_segs; ++i) {
+    const pm_adamw_segment& s = segs[i];
+    st = adamw_dev_launch(s.p, s.g, s.m, s.v, s.shadow, s.shadow_dtype, s.n, s.hyper, max_blocks, stream);
+    if (st != PM_OK) return st;
+    if (s.done_event && hipEventRecord((hipEvent_t)s.done_event, q) != hipSuccess) return PM_ELAUNCH;
+  }
+  return PM_OK;
+}
+
+// `list` is what the kernel reads (device memory, fixed address: a captured step replays it); `list_host` is the caller's host
+// copy of the same n_list indices, which is what can be checked here without a read-back: strictly ascending, inside [0, n_records).
+static int tick_list_check(const float* hyper, int n_records, const int* list, const int* list_host, int n_list) {
+  if (!hyper || !list || !list_host) return PM_EINVAL;
+  if (n_records <= 0 || n_list <= 0 || n_list > n_records) return PM_ESHAPE;
+  for (int i = 0; i < n_list; ++i) {
+    if (list_host[i] < 0 || list_host[i] >= n_records) return PM_EINVAL;
+    if (i && list_host[i] <= list_host[i - 1]) return PM_EINVAL;
+  }
+  if ((uintptr_t)list & 3) return PM_EALIGN;
+  return PM_OK;
+}
+
+extern "C" int pm_adamw_tick_list(float* hyper, int n_records, const int* list, const int* list_host, int n_list, void* stream) {
+  const int st = tick_list_check(hyper, n_records, list, list_host, n_list);
+  if (st != PM_OK) return st;
+  hipLaunchKernelGGL(adamw_tick_list_kernel, dim3((n_list + 63) / 64), dim3(64), 0, pm_stream(stream), hyper, n_records, list, n_list);
+  return pm_check_launch();
+}
+
+// pm_adamw_segments with the tick over a list: every check of both before the first enqueue.
+extern "C" int pm_adamw_segments_list(const pm_adamw_segment* segs, int n_segs, float* hyper, int n_records, const int* list,
+                                      const int* list_host, int n_list, void* wait_event, void* stream, int max_blocks) {
+  if (!segs || !hyper) return PM_EINVAL;
+  if (n_segs <= 0 || max_blocks < 0) return PM_ESHAPE;
+  int st = tick_list_check(hyper, n_records, list, list_host, n_list);
+  if (st != PM_OK) return st;
+  for (int i = 0; i < n_segs; ++i) {
+    const pm_adamw_segment& s = segs[i];
+    st = adamw_dev_check(s.p, s.g, s.m, s.v, s.shadow, s.shadow_dtype, s.n, s.hyper);
+    if (st != PM_OK) return st;
+    // a segment's record must be one of this array's, on a record boundary
+    if (s.hyper < hyper || s.hyper >= hyper + (long)n_records * kHyperStride || (s.hyper - hyper) % kHyperStride) return PM_EINVAL;
+  }
+  hipStream_t q = pm_stream(stream);
+  if (wait_event && hipStreamWaitEvent(q, (hipEvent_t)wait_event, 0) != hipSuccess) return PM_ELAUNCH;
+  st = pm_adamw_tick_list(hyper, n_records, list, list_host, n_list, stream);
   if (st != PM_OK) return st;
   for (int i = 0; i < n_segs; ++i) {
     const pm_adamw_segment& s = segs[i];

@@ -31,11 +31,20 @@ class GraphedStep:
         torch.cuda.synchronize()
         if optimizer is not None:
             optimizer.sync_hyper(force=True)
-        host_steps = [int(g.get("step", 0)) for g in optimizer.param_groups] if optimizer is not None else []
+        # per_parameter_steps: the host mirrors are per cohort record (optim.FusedAdamW, cohorts.CohortPlan); the plan -- which
+        # records exist, which of them a step advances -- is fixed while this graph lives, so a stage change needs a new GraphedStep
+        self._cohorts = optimizer is not None and getattr(optimizer, "per_parameter_steps", False)
+        if self._cohorts:
+            host_steps = optimizer._plan_cohorts().snapshot()
+        else:
+            host_steps = [int(g.get("step", 0)) for g in optimizer.param_groups] if optimizer is not None else []
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):  # records the launches; nothing executes during capture
             self.loss = step_fn()
-        if optimizer is not None:
+        if self._cohorts:
+            optimizer._plan_cohorts().restore(host_steps)
+            self._ticked = list(optimizer._tick_key[0]) if getattr(optimizer, "_tick_key", None) else []
+        elif optimizer is not None:
             for g, s in zip(optimizer.param_groups, host_steps):
                 g["step"] = s
         self.steps = 0
@@ -45,7 +54,11 @@ class GraphedStep:
         if opt is not None:
             opt.sync_hyper()  # picks up lr changes made by a scheduler since the last replay
         self.graph.replay()
-        if opt is not None:
+        if self._cohorts:
+            steps = opt._plan_cohorts().steps
+            for r in self._ticked:  # the records the captured step advances
+                steps[r] += 1
+        elif opt is not None:
             for g in opt.param_groups:  # keep the host mirror of the step counter honest (state_dict)
                 g["step"] = int(g.get("step", 0)) + 1
         self.steps += 1

@@ -28,6 +28,16 @@ of the overall interval; metrics.bootstrap_group_metrics, one device call per ch
 that gives none (`val_threshold` = policy, tau, split, epoch, fallback).  `--curve_export POINTS` writes the ROC and PR curve files of
 val and test under --output_dir and names them in the records (`val_curves`, `test_curves`).  Not here: sharded evaluation through
 the prefetcher.
+
+Staged fine-tuning (the reference's Exp-5C): `--finetune_schedule FILE` takes a YAML or JSON list in the shape of the reference's
+`protocol.finetune_schedule` (train.materialize_finetune_schedule / FinetuneScheduleRuntime), runs the optimizer with torch's
+per-parameter steps (FusedAdamW(per_parameter_steps=True)) and drives the lrs through torch's scheduler objects as the reference
+does (`--scheduler cosine|plateau|none`, train.create_scheduler) -- including the reference's behaviour that LambdaLR rewrites both
+group lrs from base_lrs x lambda after every epoch, so a stage's head_lr / backbone_lr hold for the first epoch of the stage only.
+`--early_stop_*` stops the run as the reference's patience tracker does (train.EarlyStopping; rank 0 decides, the others follow).
+Every epoch record then carries `stage`, `mode` and `lr_groups` (the lrs in force during the epoch), with early stopping also
+`monitor`, `best`, `no_improve` and `stopped`; the checkpoints carry the stage index, the scheduler state and the early-stopping
+counters, and `--resume CKPT` continues from them.  Without these options the records, checkpoints and bits are unchanged.
 """
 from __future__ import annotations
 
@@ -42,7 +52,8 @@ import torch.distributed as dist
 from . import models
 from .optim import FusedAdamW, LossScaler
 from .parallel import DataParallel
-from .train import FINETUNE_MODES, cls_cosine_lambda, configure_finetune_parameters, evaluate_cls, save_cls_checkpoint, train_epoch_cls
+from .train import (FINETUNE_MODES, FinetuneScheduleRuntime, cls_cosine_lambda, configure_finetune_parameters, create_scheduler, evaluate_cls,
+                    load_cls_checkpoint, save_cls_checkpoint, train_epoch_cls)
 
 
 SELECTING_POLICIES = ("f1_opt_on_val", "youden_on_val", "val_opt_youden", "youden")   # metrics.POLICIES
@@ -103,7 +114,88 @@ def get_args_parser():
                         "polypoid_plus_negs, perturbation = per perturbation tag and per (tag, case); with --bootstrap their intervals")
     p.add_argument("--curve_export", default=0, type=int, metavar="POINTS",
                    help="POINTS >= 2: write <output_dir>/curves_<split>_roc_curve.csv and _pr_curve.csv for val and test over that many thresholds")
+    p.add_argument("--finetune_schedule", default=None, metavar="FILE",
+                   help="staged fine-tuning: a YAML or JSON list in the shape of the reference's protocol.finetune_schedule (per stage: "
+                        "name, mode, epochs, lr, head_lr, backbone_lr, backbone_lr_scale); replaces --finetune_mode and turns the "
+                        "optimizer's per-parameter steps on")
+    p.add_argument("--scheduler", default="cosine", choices=["cosine", "plateau", "none"],
+                   help="the epoch scheduler (the reference's create_scheduler): cosine = the factor with warm-up of before")
+    p.add_argument("--min_lr", default=1e-6, type=float, help="--scheduler plateau: lower bound of the lr")
+    p.add_argument("--scheduler_patience", default=2, type=int, help="--scheduler plateau")
+    p.add_argument("--scheduler_factor", default=0.5, type=float, help="--scheduler plateau")
+    p.add_argument("--early_stop_monitor", default="val_loss", help="val_loss, or val_<key> for a key of metrics.METRIC_KEYS")
+    p.add_argument("--early_stop_mode", default=None, choices=["min", "max", "auto"], help="default: min for a loss, else max")
+    p.add_argument("--early_stop_patience", default=0, type=int, help="epochs without improvement before the run stops (0 = off)")
+    p.add_argument("--early_stop_min_delta", default=0.0, type=float)
+    p.add_argument("--early_stop_min_epochs", default=0, type=int)
+    p.add_argument("--resume", default=None, metavar="CKPT",
+                   help="continue from a checkpoint of this command (e.g. <output_dir>/ckpts/last.pth): model, optimizer, loss scaler, "
+                        "scheduler, the schedule's stage and the early-stopping counters")
     return p
+
+
+def load_finetune_schedule(args) -> list:
+    """The stages of --finetune_schedule (train.materialize_finetune_schedule over the file's list, base lr = --lr), [] without the
+    option.  The option replaces --finetune_mode: giving both is refused."""
+    if not args.finetune_schedule:
+        return []
+    if args.finetune_mode != "full":
+        raise SystemExit("--finetune_schedule sets the mode per stage: it cannot be combined with --finetune_mode")
+    if not os.path.exists(args.finetune_schedule):
+        raise SystemExit(f"--finetune_schedule {args.finetune_schedule}: no such file")
+    with open(args.finetune_schedule) as fh:
+        text = fh.read()
+    if str(args.finetune_schedule).lower().endswith(".json"):
+        spec = json.loads(text)
+    else:
+        import yaml
+        spec = yaml.safe_load(text)
+    if isinstance(spec, dict):   # a whole budget file: protocol.finetune_schedule, as in config/exp/exp5c/budgets/*.yaml
+        spec = (spec.get("protocol") or {}).get("finetune_schedule", spec.get("finetune_schedule"))
+    from .train import materialize_finetune_schedule
+    try:
+        stages = materialize_finetune_schedule(spec, float(args.lr))
+    except (TypeError, ValueError) as e:
+        raise SystemExit(f"--finetune_schedule {args.finetune_schedule}: {e}")
+    if not stages:
+        raise SystemExit(f"--finetune_schedule {args.finetune_schedule}: no stages")
+    return stages
+
+
+def early_stopping(args):
+    """train.EarlyStopping of the --early_stop_* options, None when --early_stop_patience is 0."""
+    if int(args.early_stop_patience or 0) <= 0:
+        return None
+    from . import metrics as MX
+    from .train import EarlyStopping
+    monitor = str(args.early_stop_monitor or "val_loss")
+    if monitor != "val_loss" and not (monitor.startswith("val_") and monitor[4:] in MX.METRIC_KEYS):
+        raise SystemExit(f"--early_stop_monitor {monitor}: expected val_loss or val_<key> with a key of {list(MX.METRIC_KEYS)}")
+    if not args.val_csv:
+        raise SystemExit("--early_stop_patience watches the val split: it needs --val_csv")
+    if monitor != "val_loss" and args.num_classes != 2:
+        raise SystemExit(f"--early_stop_monitor {monitor} is a binary metric: it needs --num_classes 2")
+    return EarlyStopping(monitor, args.early_stop_mode, args.early_stop_patience, args.early_stop_min_delta, args.early_stop_min_epochs)
+
+
+def monitor_value(name: str, record: dict, val_logits, val_targets, device) -> float:
+    """What early stopping and the plateau scheduler watch after an epoch: the record's val_loss, or the val metric `name[4:]` at
+    tau = 0.5 from the existing device metrics; 0.0 without a val split (tc.py:6807-6810)."""
+    if val_targets is None or val_logits is None:
+        return 0.0
+    if name == "val_loss":
+        return float(record["val_loss"])
+    from . import metrics as MX
+    return float(MX.binary_metrics(MX.positive_probs(val_logits.to(device)), val_targets, METRICS_TAU, device=device)[name[4:]])
+
+
+def broadcast_value(value: float, device, world: int) -> float:
+    """Rank 0's value on every rank (tc.py:6823-6829, 7211-7229)."""
+    if world <= 1:
+        return float(value)
+    t = torch.tensor([float(value)], dtype=torch.float64, device=device)
+    dist.broadcast(t, src=0)
+    return float(t.item())
 
 
 def parse_roots(specs) -> dict:
@@ -255,6 +347,10 @@ def run(args):
     frozen = frozen_threshold(args.threshold_from) if policy == FROZEN_POLICY else None
     if policy != FROZEN_POLICY and args.threshold_from:
         raise SystemExit("--threshold_from goes with --threshold_policy sun_val_frozen")
+    stages = load_finetune_schedule(args)
+    stopper = early_stopping(args)
+    if args.resume and not os.path.exists(args.resume):
+        raise SystemExit(f"--resume {args.resume}: no such file")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -275,16 +371,48 @@ def run(args):
                                            fused_decode=args.fused_decode)
     torch.manual_seed(args.seed)   # the same initialisation on every rank
     model = build_model(args)
-    configure_finetune_parameters(model, args.finetune_mode)
+    runtime = FinetuneScheduleRuntime(stages) if stages else None
+    # tc.py:5735-5740: the first stage's mode before the optimizer exists; the stage itself is applied after the scheduler (below)
+    configure_finetune_parameters(model, runtime.stage_for_epoch(1).mode if runtime else args.finetune_mode)
     ddp = DataParallel(model, device)
     head = list(model.lin_head.parameters())
     head_ids = {id(p) for p in head}
     groups = [{"params": head, "name": "head"},   # tc.py:5751-5768: every parameter, frozen ones are skipped for want of a gradient
               {"params": [p for p in model.parameters() if id(p) not in head_ids], "name": "backbone"}]
-    opt = FusedAdamW(model, groups, lr=args.lr, betas=(0.9, 0.999), weight_decay=args.weight_decay)
+    # a schedule changes the set of parameters with a gradient mid-run: torch's per-parameter steps (optim.FusedAdamW)
+    opt = FusedAdamW(model, groups, lr=args.lr, betas=(0.9, 0.999), weight_decay=args.weight_decay, per_parameter_steps=bool(stages))
     opt.grad_sync = ddp.sync
     opt.grad_scale = 1.0 / world
     scaler = LossScaler() if args.precision == "fp16" else None
+    # The epoch scheduler.  Without the new options the cosine factor is written into the groups before every epoch, as before; a
+    # schedule or another scheduler goes through torch's scheduler objects as the reference does (tc.py:5975), INCLUDING what
+    # follows from that: LambdaLR.step() rewrites both group lrs from base_lrs x lambda after every epoch, so a stage's head_lr /
+    # backbone_lr hold for the first epoch of the stage only.  `lr_groups` in every record shows the lrs in force.
+    staged = runtime is not None or args.scheduler != "cosine"
+    scheduler = create_scheduler(opt, args.scheduler, args.epochs, args.warmup_epochs, args.min_lr, args.scheduler_patience,
+                                 args.scheduler_factor) if staged else None
+    start_epoch = 0
+    if args.resume:
+        model._rt.ensure(device)   # the optimizer state loads into the flat storage
+        resumed = load_cls_checkpoint(args.resume, model, opt, scheduler, loss_scaler=scaler)
+        start_epoch = resumed.start_epoch - 1
+        if resumed.best_val_perf is None:
+            # load_cls_checkpoint restores optimizer, scheduler and loss scaler only beside a monitor value, as the reference does
+            # (tc.py:5976-5980); a checkpoint of a run without a val split has none, and --resume must not go on with fresh state
+            payload = torch.load(str(resumed.source), map_location="cpu", weights_only=False)
+            if "optimizer_state_dict" not in payload:
+                raise SystemExit(f"--resume {args.resume}: the checkpoint holds no optimizer state")
+            opt.load_state_dict(payload["optimizer_state_dict"])
+            if scheduler is not None and "scheduler_state_dict" in payload:
+                scheduler.load_state_dict(payload["scheduler_state_dict"])
+            if scaler is not None and payload.get("scaler_state_dict"):
+                scaler.load_state_dict(payload["scaler_state_dict"])
+        if runtime is not None:
+            runtime.restore(model, resumed.finetune_stage_index)
+        if stopper is not None and resumed.early_stop_state:
+            stopper.load_state_dict(resumed.early_stop_state)
+    elif runtime is not None:
+        runtime.apply_if_needed(model, opt, 1, printer=print if rank == 0 else None)   # tc.py:5984-5987
     pos_weight = pos_weight_host = None
     if "train" in splits and args.num_classes == 2:
         labels = splits["train"][1]
@@ -338,16 +466,24 @@ def run(args):
                                                          targets, args.curve_export, device=device)
 
     if "train" in loaders:
-        for epoch in range(args.epochs):
+        for epoch in range(start_epoch, args.epochs):
             if isinstance(sampler, torch.utils.data.DistributedSampler):
                 sampler.set_epoch(epoch)
-            factor = cls_cosine_lambda(epoch, args.warmup_epochs, args.epochs)
-            for g in opt.param_groups:
-                g["lr"] = args.lr * factor
+            stage = None
+            if not staged:
+                factor = cls_cosine_lambda(epoch, args.warmup_epochs, args.epochs)
+                for g in opt.param_groups:
+                    g["lr"] = args.lr * factor
+            elif runtime is not None:   # tc.py:6620-6623: the reference's epochs are 1-based
+                stage = runtime.apply_if_needed(model, opt, epoch + 1, printer=print if rank == 0 else None)
+            lr_groups = [float(g["lr"]) for g in opt.param_groups]   # the lrs in force during this epoch
             stats = train_epoch_cls(ddp, loaders["train"], opt, device, pos_weight=pos_weight, log_every=args.log_every,
                                     printer=(lambda r: print(f"epoch {epoch} {json.dumps(r)}", flush=True)) if rank == 0 else None,
                                     loss_scaler=scaler, clip_grad=args.clip_grad, group_grad_norms=args.group_grad_norms)
             record = {"epoch": epoch, "train_loss": stats.loss, "lr": stats.lr, "samples_per_sec": stats.samples_per_sec}
+            if staged or stopper is not None:
+                record.update(stage=stage.index if stage is not None else None,
+                              mode=stage.mode if stage is not None else args.finetune_mode, lr_groups=lr_groups)
             if "val" in loaders:
                 val_logits, val_targets, _ = evaluate_cls(model, loaders["val"], device, shard=False, return_probs=True)
                 record["val_loss"] = host_loss(val_logits, val_targets, pos_weight_host)
@@ -356,10 +492,35 @@ def run(args):
                 elif args.metrics and rank == 0:
                     record.update(metric_records("val", val_logits, val_targets, splits["val"][2], device))
                 curves(record, "val", val_logits, val_targets)
+            monitor = None
+            if stopper is not None or args.scheduler == "plateau":
+                monitor = monitor_value(args.early_stop_monitor or "val_loss", record, val_logits, val_targets if "val" in loaders else None,
+                                        device)
+            if scheduler is not None and stats.steps > 0:   # tc.py:6816-6833
+                if args.scheduler == "plateau":
+                    scheduler.step(broadcast_value(monitor, device, world))
+                else:
+                    scheduler.step()
+            stop = False
+            state = {}
+            if stopper is not None:   # tc.py:6840-6846, 7182-7192, 7211-7243: rank 0 decides, every rank follows
+                stop = stopper.update(monitor, epoch + 1)
+                stop = bool(broadcast_value(1.0 if stop else 0.0, device, world))
+                record.update(monitor=None if not math.isfinite(monitor) else monitor, best=stopper.best, no_improve=stopper.no_improve,
+                              stopped=stop)
+                state["early_stop_state"] = stopper.state_dict()
+            if staged or stopper is not None:
+                state["finetune_stage_index"] = runtime.state_dict()["stage_index"] if runtime is not None else None
+                state["monitor_value"] = record.get("val_loss", stats.loss)   # load_cls_checkpoint restores the optimizer with it
             log(record)
             save_cls_checkpoint(os.path.join(args.output_dir, "ckpts", f"finetune_e{epoch + 1}.pth"), epoch + 1, model, opt,
-                                loss=record.get("val_loss", stats.loss), extra=extra,
+                                scheduler=scheduler, loss=record.get("val_loss", stats.loss),
+                                extra={**(extra or {}), **state} if state else extra,
                                 pointer=os.path.join(args.output_dir, "ckpts", "last.pth"), loss_scaler=scaler)
+            if stop:
+                if rank == 0:
+                    print("Early stopping triggered after reaching patience limit.", flush=True)
+                break
     elif "val" in loaders:
         val_logits, val_targets, _ = evaluate_cls(model, loaders["val"], device, shard=False, return_probs=True)
         record = {"val_loss": host_loss(val_logits, val_targets, pos_weight_host)}

@@ -21,6 +21,7 @@ import ctypes
 import torch
 
 from . import _lib
+from .cohorts import CohortPlan
 from .engine import _ptr, _stream
 
 
@@ -39,15 +40,25 @@ def add_weight_decay(model, weight_decay=1e-5, skip_list=()):
 
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, model, params=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
-                 overlap_forward: bool = False):
+                 overlap_forward: bool = False, per_parameter_steps: bool = False):
         """`model`: an ssl4polyp_amd module (owns the flat storage).  `params`: iterable of parameters or of
         torch-style param-group dicts (default: all parameters of the model).
+        per_parameter_steps: by default (False) the parameters of a param group SHARE ONE STEP: every step() advances every
+        group's bias corrections, whether its parameters had a gradient or not.  That equals torch.optim.AdamW as long as the set of
+        parameters with a gradient never changes, which holds for one --finetune_mode per run.  True: torch's rule -- a parameter's
+        step counts the optimizer steps in which it had a gradient and that the loss scaler did not skip; a parameter that is
+        unfrozen mid-run starts its bias corrections at 1, one that is frozen and unfrozen again continues, one that was never
+        updated has no state.  A group then owns one device record per cohort of parameters with a common history (cohorts.py); the
+        update kernels are the same, and with a constant gradient pattern so are the bits.  The plan is fixed while a GraphedStep
+        lives: take one eager step in a new stage, then capture again.
         overlap_forward: run the update on the engine's side stream, block by block in forward order, and let the next
         forward wait per block (the update is HBM-bound, the forward GEMMs MFMA-bound: ~0.5 ms of the step hides).
         The model's forward / state_dict and this optimizer's state_dict / grad_stats wait for the update by
         themselves; code that reads parameter tensors directly right after step() must call `sync()` first."""
         self._rt = model._rt
         self.overlap_forward = bool(overlap_forward)
+        self.per_parameter_steps = bool(per_parameter_steps)
+        self._cohorts: Optional[CohortPlan] = None
         if params is None:
             params = list(model.parameters())
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -78,9 +89,12 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def _segments(self, f, group):
         """[(region, lo, hi)] covering the group's parameters that currently have a gradient."""
+        return self._segments_of(f, group["params"])
+
+    def _segments_of(self, f, params):
         idx = {id(p): i for i, p in enumerate(f.params)}
         items = []
-        for p in group["params"]:
+        for p in params:
             if p.grad is None:
                 continue
             i = idx.get(id(p))
@@ -108,7 +122,12 @@ class FusedAdamW(torch.optim.Optimizer):
             b1, b2 = group["betas"]
             rows.append((float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
                          float(self.grad_scale)))
+        if self.per_parameter_steps:  # one row per record: the group's values into each of its cohorts' records
+            return [rows[g] for g in self._plan_cohorts().group_of]
         return rows
+
+    def _n_records(self) -> int:
+        return self._plan_cohorts().n_records if self.per_parameter_steps else len(self.param_groups)
 
     def sync_hyper(self, force: bool = False):
         """Push lr / betas / eps / weight_decay / grad_scale to the device records when they changed on the host.
@@ -116,9 +135,16 @@ class FusedAdamW(torch.optim.Optimizer):
         f = self._ensure_state()
         rows = self._host_hyper()
         if getattr(self, "_hyper", None) is None or self._hyper.device != f.device:
+            moved = getattr(self, "_hyper", None)  # the records on the device the storage left, if any
             self._hyper = torch.zeros(len(rows), self.HYPER_STRIDE, dtype=torch.float32, device=f.device)
-            for gi, group in enumerate(self.param_groups):  # resume: restore the step counter
-                self._hyper[gi, 6] = float(group.get("step", 0))
+            if self.per_parameter_steps and moved is not None and moved.shape[0] == len(rows):
+                # the device records are authoritative (steps the loss scaler skipped are not in the host mirrors): carry them over
+                self._hyper[:, 6:11] = moved[:, 6:11].to(f.device)
+            elif self.per_parameter_steps:  # (first step, or after load_state_dict: the plan's steps are the loaded ones)
+                self._hyper[:, 6] = torch.tensor(self._plan_cohorts().steps, dtype=torch.float32)
+            else:
+                for gi, group in enumerate(self.param_groups):  # resume: restore the step counter
+                    self._hyper[gi, 6] = float(group.get("step", 0))
             self._hyper_host = None
         if force or rows != self._hyper_host:
             # The MAE loop changes lr EVERY iteration (engine_pretrain.py:47-48): the upload must not block the host, or
@@ -147,13 +173,13 @@ class FusedAdamW(torch.optim.Optimizer):
     def _clip_buffers(self, f, n_segs):
         """Workspace, f64 sums, f32 triple and f64 record of the norm kernels: allocated once (outside capture: a GraphedStep runs
         its eager warm-up steps first), at fixed addresses, so that a captured step replays them."""
-        G = len(self.param_groups)
+        G, R = len(self.param_groups), self._n_records()  # (R == G unless per_parameter_steps: one sum per record)
         size = ctypes.c_size_t(0)
-        _lib.check(self._rt.k.lib.pm_grad_norms_workspace(n_segs, G, ctypes.byref(size)), "pm_grad_norms_workspace")
+        _lib.check(self._rt.k.lib.pm_grad_norms_workspace(n_segs, R, ctypes.byref(size)), "pm_grad_norms_workspace")
         b = getattr(self, "_clip_buf", None)
-        if b is None or b["ws"].device != f.device or b["ws"].numel() * 8 < size.value or b["sumsq"].numel() != G:
+        if b is None or b["ws"].device != f.device or b["ws"].numel() * 8 < size.value or b["sumsq"].numel() != R:
             b = self._clip_buf = {"ws": torch.zeros((size.value + 7) // 8, dtype=torch.float64, device=f.device),
-                                  "sumsq": torch.zeros(G, dtype=torch.float64, device=f.device),
+                                  "sumsq": torch.zeros(R, dtype=torch.float64, device=f.device),
                                   "stats": torch.zeros(3, dtype=torch.float32, device=f.device),
                                   "record": torch.zeros(G + 3, dtype=torch.float64, device=f.device),
                                   "norms": torch.zeros(G + 3, dtype=torch.float64, device=f.device)}
@@ -173,7 +199,7 @@ class FusedAdamW(torch.optim.Optimizer):
         """The statistics pass on the current stream: per-group f64 sums into the optimizer's buffer, the f32 triple into `stats`
         (default: the optimizer's own).  Returns the buffers."""
         b = self._clip_buffers(f, len(stat_segs))
-        _lib.check(self._rt.k.lib.pm_grad_norms(self._grad_segment_array(f, stat_segs), len(stat_segs), len(self.param_groups),
+        _lib.check(self._rt.k.lib.pm_grad_norms(self._grad_segment_array(f, stat_segs), len(stat_segs), self._n_records(),
                                                 _ptr(b["ws"]), b["ws"].numel() * 8, _ptr(b["sumsq"]),
                                                 _ptr(stats if stats is not None else b["stats"]), _stream()), "pm_grad_norms")
         return b
@@ -207,9 +233,10 @@ class FusedAdamW(torch.optim.Optimizer):
         stat_segs = [(gi, r, lo, hi) for gi, group in enumerate(self.param_groups) for r, lo, hi in self._segments(f, group)]
         if not stat_segs:
             return torch.zeros(G + 1, dtype=torch.float64, device=f.device)
+        # (per_parameter_steps: the segments are tagged by their group's FIRST record, g -- a parameter that has its first gradient
+        # has no cohort before the step -- and summed per group like any other tagging)
         b = self._grad_norms_pass(f, stat_segs)
-        _lib.check(self._rt.k.lib.pm_grad_clip(_ptr(b["sumsq"]), _ptr(self._hyper), G, 0.0, 0, 0, _ptr(b["norms"]), _stream()),
-                   "pm_grad_clip")
+        self._clip_call(b, 0.0, 0, 0, b["norms"])
         out = b["norms"][:G + 1].clone()
         if loss_scaler is not None and loss_scaler.enabled:
             state, _ = loss_scaler._device_state(f.device)
@@ -246,11 +273,15 @@ class FusedAdamW(torch.optim.Optimizer):
             self.sync_hyper()
         lib = self._rt.k.lib
         overlap = self.overlap_forward and not capturing and f.device.type == "cuda"
-        work = []  # (group index, region, lo, hi)
-        for gi, group in enumerate(self.param_groups):
-            group["step"] = int(group.get("step", 0)) + 1  # host mirror (the device record is authoritative)
-            for r, lo, hi in self._segments(f, group):
-                work.append((gi, r, lo, hi))
+        work = []  # (group index, region, lo, hi); per_parameter_steps: (record index, ...), see _cohort_work
+        if self.per_parameter_steps:
+            work = self._cohort_work(f, capturing)
+        else:
+            for gi, group in enumerate(self.param_groups):
+                group["step"] = int(group.get("step", 0)) + 1  # host mirror (the device record is authoritative)
+                for r, lo, hi in self._segments(f, group):
+                    work.append((gi, r, lo, hi))
+        n_rec = self._n_records()
         scaled = loss_scaler is not None and loss_scaler.enabled
         clip = max_norm is not None and bool(work)
         stat_segs = list(work) if (scaled or clip) else []
@@ -289,7 +320,7 @@ class FusedAdamW(torch.optim.Optimizer):
                     stats.zero_()
                     for _, r, lo, hi in stat_segs:
                         _lib.check(lib.pm_grad_stats(_ptr(f.G[r][lo:hi]), hi - lo, _ptr(stats), _stream()), "pm_grad_stats")
-                _lib.check(lib.pm_loss_scale_update(_ptr(state), _ptr(stats), _ptr(self._hyper), len(self.param_groups),
+                _lib.check(lib.pm_loss_scale_update(_ptr(state), _ptr(stats), _ptr(self._hyper), n_rec,
                                                     loss_scaler.growth_factor, loss_scaler.backoff_factor,
                                                     loss_scaler.growth_interval, _stream()), "pm_loss_scale_update")
                 self._scaler_used = True
@@ -297,8 +328,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 self._grad_norms_pass(f, stat_segs)
             if clip:
                 b = self._clip_buf
-                _lib.check(lib.pm_grad_clip(_ptr(b["sumsq"]), _ptr(self._hyper), len(self.param_groups), float(max_norm), 1,
-                                            1 if scaled else 0, _ptr(b["record"]), _stream()), "pm_grad_clip")
+                self._clip_call(b, float(max_norm), 1, 1 if scaled else 0, b["record"])
                 self._clip_seen = True
                 self._clip_ev = None
                 if overlap:  # the record is written on the side stream: `last_clip` makes its reader's stream wait for it
@@ -307,12 +337,25 @@ class FusedAdamW(torch.optim.Optimizer):
             if overlap and work:
                 # the whole update in ONE C call: [wait for the main stream's event,] tick, then launch + done event per segment
                 segs, events = self._segment_array(f, work, side)
-                _lib.check(lib.pm_adamw_segments(segs, len(work), _ptr(self._hyper), len(self.param_groups),
-                                                 None if (scaled or clip) else ev.cuda_event, _stream(), self.OVERLAP_MAX_BLOCKS),
-                           "pm_adamw_segments")
+                wait = None if (scaled or clip) else ev.cuda_event
+                if self.per_parameter_steps:
+                    tick_dev, tick_host = self._tick
+                    _lib.check(lib.pm_adamw_segments_list(segs, len(work), _ptr(self._hyper), n_rec, _ptr(tick_dev), tick_host,
+                                                          len(tick_host), wait, _stream(), self.OVERLAP_MAX_BLOCKS),
+                               "pm_adamw_segments_list")
+                else:
+                    _lib.check(lib.pm_adamw_segments(segs, len(work), _ptr(self._hyper), len(self.param_groups), wait, _stream(),
+                                                     self.OVERLAP_MAX_BLOCKS), "pm_adamw_segments")
                 rt.pending_updates += [(r, lo, hi, done) for (_, r, lo, hi), done in zip(work, events)]
                 return loss
-            _lib.check(lib.pm_adamw_tick(_ptr(self._hyper), len(self.param_groups), _stream()), "pm_adamw_tick")
+            if self.per_parameter_steps:
+                if not work:  # nothing has a gradient: no record advances
+                    return loss
+                tick_dev, tick_host = self._tick
+                _lib.check(lib.pm_adamw_tick_list(_ptr(self._hyper), n_rec, _ptr(tick_dev), tick_host, len(tick_host), _stream()),
+                           "pm_adamw_tick_list")
+            else:
+                _lib.check(lib.pm_adamw_tick(_ptr(self._hyper), len(self.param_groups), _stream()), "pm_adamw_tick")
             for gi, r, lo, hi in work:
                 shadow = f.S[lo:hi] if (r == "mat" and f.S is not None) else None
                 _lib.check(lib.pm_adamw_dev(_ptr(f.P[r][lo:hi]), _ptr(f.G[r][lo:hi]), _ptr(self._M[r][lo:hi]),
@@ -320,6 +363,92 @@ class FusedAdamW(torch.optim.Optimizer):
                                             _lib.dtype_code(shadow.dtype) if shadow is not None else 0, hi - lo,
                                             _ptr(self._hyper[gi]), _stream()), "pm_adamw_dev")
         return loss
+
+    # -- per_parameter_steps: cohorts of parameters with a common step history (cohorts.py) ---------------------------------------
+    def _plan_cohorts(self) -> CohortPlan:
+        if self._cohorts is None:
+            self._cohorts = CohortPlan(len(self.param_groups))
+        return self._cohorts
+
+    def _cohort_keys(self, f):
+        """Per param group, the flat-storage index of every parameter (the plan's keys), and {key: parameter}."""
+        idx = {id(p): i for i, p in enumerate(f.params)}
+        groups, by_key = [], {}
+        for group in self.param_groups:
+            keys = []
+            for p in group["params"]:
+                i = idx.get(id(p))
+                if i is None:
+                    raise _lib.PolypMaeError("FusedAdamW: parameter does not belong to the model's flat storage")
+                keys.append(i)
+                by_key[i] = p
+            groups.append(keys)
+        return groups, by_key
+
+    def _cohort_work(self, f, capturing):
+        """Advance the plan by this step's `p.grad is None` pattern and return the work list [(record, region, lo, hi)].  New and
+        split records are created here (device copies of the rows they start from), the group's hyper-parameters go into them, and
+        the device lists the kernels read (`_tick`: the records to advance; `_group_of`: record -> group) follow.  Under capture
+        nothing of that may change: the plan is fixed while a graph lives."""
+        plan = self._plan_cohorts()
+        groups, by_key = self._cohort_keys(f)
+        active = {k for k, p in by_key.items() if p.grad is not None}
+        if capturing:
+            if getattr(self, "_hyper", None) is None or plan.preview(groups, active):
+                raise _lib.PolypMaeError("FusedAdamW(per_parameter_steps=True): the set of parameters with a gradient changed; the "
+                                         "cohort plan is fixed while a graph lives -- take one eager step in the new stage, then "
+                                         "capture again")
+        copies, tick = plan.advance(groups, active)
+        R = plan.n_records
+        if self._hyper.shape[0] != R:  # (never under capture: preview() refused above)
+            grown = torch.zeros(R, self.HYPER_STRIDE, dtype=torch.float32, device=self._hyper.device)
+            grown[:self._hyper.shape[0]] = self._hyper
+            for dst, src in copies:  # a split: the idle part's record starts as a copy (step, bias corrections, flags)
+                grown[dst] = grown[src]
+            self._hyper = grown
+            self._hyper_host = None
+        if not capturing:
+            self.sync_hyper()
+        self._set_device_lists(plan, tick, capturing)
+        work = []
+        for by_record in plan.records_of(groups, active):
+            for rec in sorted(by_record):
+                work += [(rec, r, lo, hi) for r, lo, hi in self._segments_of(f, [by_key[k] for k in by_record[rec]])]
+        return work
+
+    def _set_device_lists(self, plan, tick, capturing):
+        dev = self._hyper.device
+        key = tuple(plan.group_of)
+        if getattr(self, "_group_of_key", None) != (key, dev):
+            host = (ctypes.c_int * len(key))(*key)
+            self._group_of = (torch.tensor(key, dtype=torch.int32).to(dev), host)
+            self._group_of_key = (key, dev)
+        tick = tuple(tick)
+        if getattr(self, "_tick_key", None) != (tick, dev, len(key)):
+            if capturing:
+                raise _lib.PolypMaeError("FusedAdamW(per_parameter_steps=True): the records to advance changed under capture")
+            old = getattr(self, "_tick", None)
+            buf = old[0] if old is not None and old[0].device == dev and old[0].numel() >= max(len(key), 1) else \
+                torch.zeros(max(len(key), 16), dtype=torch.int32, device=dev)  # fixed address while the record count stands
+            if tick:
+                buf[:len(tick)].copy_(torch.tensor(tick, dtype=torch.int32))
+            self._tick = (buf, (ctypes.c_int * len(tick))(*tick))
+            self._tick_key = (tick, dev, len(key))
+
+    def _clip_call(self, b, max_norm, clip, scaled, record):
+        """pm_grad_clip, or its sibling over cohort records (sums per record -> per group, the coefficient into every record)."""
+        lib = self._rt.k.lib
+        G = len(self.param_groups)
+        if self.per_parameter_steps:
+            plan = self._plan_cohorts()
+            if getattr(self, "_group_of_key", None) != (tuple(plan.group_of), self._hyper.device):
+                self._set_device_lists(plan, (getattr(self, "_tick_key", None) or ((),))[0], False)
+            group_dev, group_host = self._group_of
+            _lib.check(lib.pm_grad_clip_cohorts(_ptr(b["sumsq"]), _ptr(self._hyper), plan.n_records, _ptr(group_dev), group_host, G,
+                                                max_norm, clip, scaled, _ptr(record), _stream()), "pm_grad_clip_cohorts")
+        else:
+            _lib.check(lib.pm_grad_clip(_ptr(b["sumsq"]), _ptr(self._hyper), G, max_norm, clip, scaled, _ptr(record), _stream()),
+                       "pm_grad_clip")
 
     # -- the overlapped update's launcher arguments (pm_adamw_segments) -----------------------------------------
     # Workgroups per launch of the overlapped update (pm_adamw_grid; 0 = the full grid, which the inline path keeps).  Chosen by
@@ -382,13 +511,19 @@ class FusedAdamW(torch.optim.Optimizer):
         if host and M:
             M = {r: t.detach().cpu() for r, t in M.items()}
             V = {r: t.detach().cpu() for r, t in V.items()}
+        psteps = None
+        if self.per_parameter_steps:
+            # torch's layout exactly: an entry per UPDATED parameter, its step the cohort's, read from the device records (one
+            # D2H read: steps the loss scaler skipped are not in it); no entry for a parameter that was never updated
+            records = self._hyper[:, 6].tolist() if getattr(self, "_hyper", None) is not None else None
+            psteps = self._plan_cohorts().parameter_steps(records)
         for group in self.param_groups:
             ids = []
             for p in group["params"]:
                 i = idx.get(id(p))
-                if i is not None and M:
+                if i is not None and M and (psteps is None or i in psteps):
                     r, lo, n = f.region[i], f.offset[i], f.numel[i]
-                    state[k] = {"step": torch.tensor(float(group.get("step", 0))),
+                    state[k] = {"step": torch.tensor(float(group.get("step", 0) if psteps is None else psteps[i])),
                                 "exp_avg": M[r][lo:lo + n].view(p.shape).clone(),
                                 "exp_avg_sq": V[r][lo:lo + n].view(p.shape).clone()}
                 ids.append(k)
@@ -402,9 +537,10 @@ class FusedAdamW(torch.optim.Optimizer):
         f = self._ensure_state()
         self._rt.wait_updates()
         idx = {id(p): i for i, p in enumerate(f.params)}
+        psteps = {}  # per_parameter_steps: flat index -> the parameter's own step
         for group, saved in zip(self.param_groups, sd["param_groups"]):
             for kk, v in saved.items():
-                if kk != "params":
+                if kk != "params" and not (self.per_parameter_steps and kk == "step"):
                     group[kk] = v
             for p, k in zip(group["params"], saved["params"]):
                 st = sd["state"].get(k)
@@ -414,7 +550,13 @@ class FusedAdamW(torch.optim.Optimizer):
                 r, lo, n = f.region[i], f.offset[i], f.numel[i]
                 self._M[r][lo:lo + n].copy_(st["exp_avg"].reshape(-1))
                 self._V[r][lo:lo + n].copy_(st["exp_avg_sq"].reshape(-1))
-                group["step"] = int(float(st["step"]))
+                if self.per_parameter_steps:
+                    psteps[i] = float(st["step"])
+                else:
+                    group["step"] = int(float(st["step"]))
+        if self.per_parameter_steps:  # the cohorts are rebuilt from the per-parameter steps (torch.optim.AdamW's dict loads as well)
+            self._cohorts = CohortPlan.from_steps(self._cohort_keys(f)[0], psteps)
+            self._group_of_key = self._tick_key = None
         self._hyper = None  # rebuild the device records (incl. the step counters) at the next step()
 
 

@@ -87,6 +87,223 @@ def configure_finetune_parameters(model, mode: str) -> None:
 
 
 # ---------------------------------------------------------------------------------------------------
+# staged fine-tuning (Exp-5C: protocol.finetune_schedule), the epoch scheduler and early stopping, as the reference has them
+# ---------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class FinetuneStage:
+    """tc.py:508-524.  Epochs are 1-based and inclusive."""
+    index: int
+    start_epoch: int
+    end_epoch: int
+    mode: str
+    head_lr: float
+    backbone_lr: float
+    base_lr: float
+    backbone_lr_scale: Optional[float]
+    label: Optional[str] = None
+
+    @property
+    def epochs(self) -> int:
+        return self.end_epoch - self.start_epoch + 1
+
+
+def _optional_float(value, context: str) -> Optional[float]:
+    """tc.py:709-718."""
+    if value is None:
+        return None
+    try:
+        numeric = float(value)
+    except (TypeError, ValueError) as exc:
+        raise ValueError(f"Invalid numeric value for {context}: {value!r}") from exc
+    if math.isnan(numeric) or math.isinf(numeric):
+        raise ValueError(f"Non-finite value for {context}: {value!r}")
+    return numeric
+
+
+def materialize_finetune_schedule(spec, base_lr: float, default_mode: str = "full") -> List[FinetuneStage]:
+    """A `protocol.finetune_schedule` list (config/exp/exp5c/budgets/*.yaml: name, mode, epochs, lr, head_lr, backbone_lr,
+    backbone_lr_scale per stage) as stages: tc.py:721-776 (_sanitize_finetune_schedule_config: a stage without `mode` inherits the
+    previous one's, `index` is the position) followed by tc.py:860-903 (_materialize_finetune_schedule).  The head's lr is
+    `head_lr`, else the stage's `lr`, else base_lr; the backbone's is, in this order of precedence, `backbone_lr`; 0.0 when the mode
+    is "none"; stage lr x `backbone_lr_scale`; the stage lr."""
+    if spec in (None, False) or not spec:
+        return []
+    if not isinstance(spec, (list, tuple)):
+        raise TypeError("Fine-tune schedule must be a list of stage dictionaries.")
+    stages: List[FinetuneStage] = []
+    start_epoch, previous_mode = 1, default_mode
+    for index, entry in enumerate(spec):
+        if not hasattr(entry, "get"):
+            raise TypeError(f"Schedule entry #{index + 1} must be a mapping; received {type(entry)!r}.")
+        raw_mode = entry.get("mode", previous_mode)
+        mode = str(previous_mode if raw_mode is None else raw_mode).strip().lower() or str(previous_mode).strip().lower()
+        if mode not in FINETUNE_MODES:
+            raise ValueError(f"Unsupported fine-tuning mode '{raw_mode}'. Expected one of {sorted(FINETUNE_MODES)}.")
+        if entry.get("epochs") is None:
+            raise ValueError(f"Schedule entry #{index + 1} is missing required key 'epochs'.")
+        try:
+            epochs = int(entry.get("epochs"))
+        except (TypeError, ValueError) as exc:
+            raise ValueError(f"Schedule entry #{index + 1} provided non-integer epochs {entry.get('epochs')!r}.") from exc
+        if epochs <= 0:
+            raise ValueError(f"Schedule entry #{index + 1} must have a positive epoch count; received {epochs}.")
+        stage_lr, head_lr, backbone_lr, lr_scale = (_optional_float(entry.get(k), f"schedule entry #{index + 1} {k}")
+                                                    for k in ("lr", "head_lr", "backbone_lr", "backbone_lr_scale"))
+        stage_base_lr = stage_lr if stage_lr is not None else float(base_lr)
+        if backbone_lr is not None:
+            resolved = backbone_lr
+        elif mode == "none":
+            resolved = 0.0
+        elif lr_scale is not None:
+            resolved = float(stage_base_lr) * float(lr_scale)
+        else:
+            resolved = float(stage_base_lr)
+        end_epoch = start_epoch + epochs - 1
+        stages.append(FinetuneStage(index=index, start_epoch=start_epoch, end_epoch=end_epoch, mode=mode,
+                                    head_lr=float(head_lr if head_lr is not None else stage_base_lr), backbone_lr=float(resolved),
+                                    base_lr=float(stage_base_lr), backbone_lr_scale=lr_scale, label=entry.get("name")))
+        start_epoch, previous_mode = end_epoch + 1, mode
+    return stages
+
+
+class FinetuneScheduleRuntime:
+    """tc.py:906-953: applies the stage of a (1-based) epoch when the stage INDEX changes -- configure_finetune_parameters and the
+    lr of the param groups named "head" / "backbone" -- and not otherwise.  An epoch past the last stage stays in the last stage.
+
+    Kept as the reference has it: a LambdaLR rewrites every group's lr from its `base_lrs` x lambda(epoch) in each scheduler.step(),
+    so with the cosine scheduler a stage's head_lr / backbone_lr hold for the FIRST epoch of the stage only; from its second epoch
+    on both groups run at base lr x lambda again (the frozen parameters have no gradient, so the backbone's lr is idle in "none")."""
+
+    def __init__(self, stages):
+        self.stages: List[FinetuneStage] = list(stages)
+        self._current_stage_index: Optional[int] = None
+
+    def is_active(self) -> bool:
+        return bool(self.stages)
+
+    def stage_for_epoch(self, epoch: int) -> Optional[FinetuneStage]:
+        for stage in self.stages:
+            if stage.start_epoch <= epoch <= stage.end_epoch:
+                return stage
+        return self.stages[-1] if self.stages else None
+
+    def apply_if_needed(self, model, optimizer, epoch: int, printer: Optional[Callable] = None) -> Optional[FinetuneStage]:
+        stage = self.stage_for_epoch(epoch)
+        if stage is None or self._current_stage_index == stage.index:
+            return stage
+        if len({s.mode for s in self.stages}) > 1 and getattr(optimizer, "per_parameter_steps", True) is False:
+            # (torch's own optimizers keep per-parameter steps and have no such attribute)
+            raise ValueError("a fine-tune schedule changes the set of trainable parameters mid-run: optim.FusedAdamW shares one step "
+                             "per param group by default and would take other steps than torch.optim.AdamW after an unfreeze; "
+                             "construct it with per_parameter_steps=True")
+        configure_finetune_parameters(_unwrap(model), stage.mode)
+        for group in optimizer.param_groups:
+            if group.get("name") == "head":
+                group["lr"] = stage.head_lr
+            elif group.get("name") == "backbone":
+                group["lr"] = stage.backbone_lr
+        if printer is not None:
+            printer(f"[finetune] Stage {stage.index + 1}{f' ({stage.label})' if stage.label else ''}: epochs {stage.start_epoch}-"
+                    f"{stage.end_epoch} | mode={stage.mode} | head_lr={stage.head_lr:.2e} | backbone_lr={stage.backbone_lr:.2e}")
+        self._current_stage_index = stage.index
+        return stage
+
+    def restore(self, model, stage_index: Optional[int]) -> None:
+        """Resume: the run was in stage `stage_index` -- freeze / unfreeze as that stage does, and leave the group lrs to the loaded
+        optimizer state (apply_if_needed will not fire again before the next stage)."""
+        if stage_index is None:
+            return
+        configure_finetune_parameters(_unwrap(model), self.stages[int(stage_index)].mode)
+        self._current_stage_index = int(stage_index)
+
+    def state_dict(self) -> dict:
+        return {"stage_index": self._current_stage_index}
+
+
+def create_scheduler(optimizer, name: Optional[str], epochs: int, warmup_epochs: int = 0, min_lr: float = 1e-6,
+                     scheduler_patience: int = 2, scheduler_factor: float = 0.5):
+    """tc.py:3943-3971.  "cosine": LambdaLR over cls_cosine_lambda, stepped once per epoch; "plateau": ReduceLROnPlateau in mode
+    "max" (stepped with the monitor value); anything else: None.  optim.FusedAdamW is a torch.optim.Optimizer: torch's schedulers
+    drive its param groups directly, and the next step() uploads what they wrote."""
+    name = (name or "none").lower()
+    if name == "cosine":
+        return torch.optim.lr_scheduler.LambdaLR(optimizer, lambda epoch: cls_cosine_lambda(epoch, warmup_epochs, epochs))
+    if name == "plateau":
+        return torch.optim.lr_scheduler.ReduceLROnPlateau(optimizer, mode="max", factor=scheduler_factor, patience=scheduler_patience,
+                                                          min_lr=min_lr)
+    return None
+
+
+def resolve_monitor_mode(monitor: Optional[str], mode: Optional[str]) -> str:
+    """tc.py:3297-3313: "min" / "max" as given, else ("auto" or nothing) "min" for a monitor that ends or starts with "loss"."""
+    if mode:
+        resolved = mode.lower()
+        if resolved not in {"min", "max", "auto"}:
+            raise ValueError(f"Unsupported early-stop mode: {mode!r}")
+    else:
+        resolved = "auto"
+    if resolved != "auto":
+        return resolved
+    monitor = (monitor or "").lower()
+    if monitor.endswith("loss") or monitor.startswith("loss"):
+        return "min"
+    return "max"
+
+
+def improved(current: float, best: Optional[float], mode: str, min_delta: float) -> bool:
+    """tc.py:3316-3333: no best yet (None or NaN) counts as an improvement, a NaN current never does; a tie inside min_delta is none."""
+    if best is None or math.isnan(best):
+        return True
+    if math.isnan(current):
+        return False
+    if mode == "min":
+        return current < (best - min_delta)
+    if mode == "max":
+        return current > (best + min_delta)
+    raise ValueError(f"Unexpected monitor mode: {mode}")
+
+
+def should_trigger_early_stop(no_improve_epochs: int, patience: int, epochs_completed: int, min_epochs: int) -> bool:
+    """tc.py:3903-3915."""
+    if patience <= 0:
+        return False
+    if epochs_completed < max(min_epochs, 0):
+        return False
+    return no_improve_epochs >= patience
+
+
+class EarlyStopping:
+    """The reference's patience tracker (tc.py:6214-6217, 6541-6547, 7182-7192, 7211-7243) around the three functions above:
+    `update(value, epochs_completed)` after every epoch returns whether to stop."""
+
+    def __init__(self, monitor: str = "val_loss", mode: Optional[str] = None, patience: int = 0, min_delta: float = 0.0,
+                 min_epochs: int = 0):
+        self.monitor = monitor or "val_loss"
+        self.mode = resolve_monitor_mode(self.monitor, mode)
+        self.patience = max(0, int(patience or 0))
+        self.min_delta = 0.0 if math.isnan(float(min_delta)) else float(min_delta)   # tc.py:3289-3294 _safe_min
+        self.min_epochs = max(0, int(min_epochs or 0))
+        self.best: Optional[float] = None
+        self.best_epoch: Optional[int] = None
+        self.no_improve = 0
+
+    def update(self, value: float, epochs_completed: int) -> bool:
+        if improved(float(value), self.best, mode=self.mode, min_delta=self.min_delta):
+            self.best, self.best_epoch, self.no_improve = float(value), int(epochs_completed), 0
+        else:
+            self.no_improve += 1
+        if self.best is not None and math.isnan(self.best):   # tc.py:7190-7192
+            self.best = self.best_epoch = None
+        return should_trigger_early_stop(self.no_improve, self.patience, epochs_completed, self.min_epochs)
+
+    def state_dict(self) -> dict:
+        return {"best": self.best, "best_epoch": self.best_epoch, "no_improve": self.no_improve}
+
+    def load_state_dict(self, sd: dict) -> None:
+        self.best, self.best_epoch, self.no_improve = sd.get("best"), sd.get("best_epoch"), int(sd.get("no_improve", 0))
+
+
+# ---------------------------------------------------------------------------------------------------
 # loss of the fine-tune path (tc.py:3347-3374, 6086-6104)
 # ---------------------------------------------------------------------------------------------------
 def supervised_loss(logits: torch.Tensor, targets: torch.Tensor, pos_weight: Optional[torch.Tensor] = None,
@@ -631,6 +848,8 @@ class ClsResume:
     threshold_records: Dict = field(default_factory=dict)
     source: Optional[Path] = None
     from_parent: bool = False
+    finetune_stage_index: Optional[int] = None      # FinetuneScheduleRuntime.state_dict()["stage_index"] of the saved run
+    early_stop_state: Dict = field(default_factory=dict)   # EarlyStopping.state_dict()
 
 
 def load_cls_checkpoint(stem_path, model, optimizer=None, scheduler=None, parent_checkpoint=None,
@@ -661,6 +880,8 @@ def load_cls_checkpoint(stem_path, model, optimizer=None, scheduler=None, parent
             torch.set_rng_state(main["torch_state"])
         info.thresholds = dict(main.get("thresholds", {}) or {})
         info.threshold_records = dict(main.get("threshold_records", {}) or {})
+        info.finetune_stage_index = main.get("finetune_stage_index")
+        info.early_stop_state = dict(main.get("early_stop_state", {}) or {})
         info.source = Path(existing)
         if not pointer_valid:
             stem = Path(stem_path)
