@@ -775,6 +775,60 @@ int pm_select_tau_workspace(int N, int M, size_t* bytes);
 int pm_select_tau(const double* score, const int* order, const unsigned char* label, const double* previous_tau, int policy,
                   double* out, double* candidates, int N, int M, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- linear probing of a frozen encoder (mae/main_linprobe.py) -------------------------------------------------------------
+ * The launches the probe protocol adds beside the forward-only encoder: the global_pool feature, the BatchNorm1d + Linear head,
+ * softmax cross-entropy with the accuracy counts of engine_finetune.evaluate, the head's weight gradients, and LARS
+ * (mae/util/lars.py).  f32 throughout, fixed summation order (no float atomics), nothing allocated, the stream passed in; every
+ * refusal (PM_EINVAL: a NULL pointer, a short workspace, eps < 0; PM_ESHAPE; PM_EALIGN) returns before the first launch.
+ *
+ * pm_pool_norm_fwd: feat[b] = LayerNorm_{gamma, beta, eps}(mean_{n >= 1} x[b, n, :]) -- models_vit.py:46-48 (global_pool), forward
+ *   only (the encoder and fc_norm are frozen).  x f32 [B, N, D] (the last block's output, no final norm), feat f32 [B, D];
+ *   N >= 2, D % 4 == 0, D <= 2048; everything 16-byte aligned.  x is read once.  workspace: pm_pool_norm_workspace bytes.
+ *
+ * pm_probe_head_fwd: BatchNorm1d(affine=False) over feat [B, D], then logits = xhat W^T + bias, W [C, D].  xhat [B, D] is saved.
+ *   training != 0: batch mean and biased variance; running = (1 - momentum) running + momentum new, the running variance from the
+ *     unbiased estimate (divisor B - 1), *num_batches_tracked += 1 (int64 on the device), as torch.nn.BatchNorm1d.  B < 2 is
+ *     PM_ESHAPE (torch raises there too).
+ *   training == 0: the same map through running_mean / running_var; nothing is updated (num_batches_tracked may be NULL).
+ *   D % 4 == 0; W and xhat 16-byte aligned; B <= 65535.
+ *
+ * pm_probe_ce: torch.nn.CrossEntropyLoss() (mean over the batch) of logits [B, C] against int64 targets in [0, C), any C >= 1.
+ *   loss f32 [1]; dlogits [B, C] = (softmax - onehot) / B x scale[0] (scale: a device scalar, 1 / accum_iter in training; dlogits
+ *   NULL: not computed, scale may be NULL); correct int64 [2], overwritten: the rows whose target is correct at 1 and at
+ *   k = min(5, C), a row being correct at k when fewer than k classes have a logit strictly greater than the target's.  A target
+ *   outside [0, C) makes the loss NaN, counts as wrong and gets a zero gradient row.  workspace: pm_probe_ce_workspace bytes.
+ *
+ * pm_probe_head_bwd: dW [C, D] += dlogits^T xhat, dbias [C] += sum_b dlogits: one addition into what they held (gradient
+ *   accumulation over accum_iter micro-batches).  There is no gradient with respect to the features.  C <= 65535.
+ *
+ * pm_lars_step: mae/util/lars.py:22-47 over n_segs tensors of ONE param group.  hyper: device f32 [4] = lr, weight decay,
+ *   momentum, trust coefficient (read by the kernels, so a captured step follows an lr written between replays).
+ *     is_matrix (p.ndim > 1): dp = g + wd p; q = tc |p| / |dp| if |p| > 0 and |dp| > 0, else 1; dp *= q
+ *     otherwise:              dp = g                                 (no decay, no trust ratio)
+ *     mu = momentum mu + dp;  p -= lr mu
+ *   The norms are f64 sums of the squared f32 values over a fixed two-stage map that depends on the segment's length alone: a
+ *   table of several segments gives the bits of one call per segment.  Any n >= 1, 4-byte alignment.
+ *   workspace: 8-byte aligned, pm_lars_workspace(n_segs) bytes. */
+typedef struct pm_lars_segment {
+  float* p;
+  const float* g;
+  float* mu;
+  long n;
+  int is_matrix;
+} pm_lars_segment;
+int pm_pool_norm_workspace(int B, int N, int D, size_t* bytes);
+int pm_pool_norm_fwd(const float* x, int B, int N, int D, const float* gamma, const float* beta, float eps, float* feat,
+                     void* workspace, size_t ws_bytes, void* stream);
+int pm_probe_head_fwd(const float* feat, int B, int D, int C, const float* W, const float* bias, float* running_mean,
+                      float* running_var, long long* num_batches_tracked, int training, float momentum, float eps, float* xhat,
+                      float* logits, void* stream);
+int pm_probe_ce_workspace(int B, size_t* bytes);
+int pm_probe_ce(const float* logits, const long long* target, int B, int C, const float* scale, float* loss, float* dlogits,
+                long long* correct, void* workspace, size_t ws_bytes, void* stream);
+int pm_probe_head_bwd(const float* dlogits, const float* xhat, int B, int D, int C, float* dW, float* dbias, void* stream);
+int pm_lars_workspace(int n_segs, size_t* bytes);
+int pm_lars_step(const pm_lars_segment* segs, int n_segs, const float* hyper, void* workspace, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

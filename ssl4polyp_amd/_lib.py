@@ -96,6 +96,14 @@ SIGNATURES = {
     "pm_group_metrics": [P, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, ctypes.c_size_t, P],
     "pm_select_tau_workspace": [I, I, P],
     "pm_select_tau": [P, P, P, P, I, P, P, I, I, P, ctypes.c_size_t, P],
+    "pm_pool_norm_workspace": [I, I, I, P],
+    "pm_pool_norm_fwd": [P, I, I, I, P, P, F, P, P, ctypes.c_size_t, P],
+    "pm_probe_head_fwd": [P, I, I, I, P, P, P, P, P, I, F, F, P, P, P],
+    "pm_probe_ce_workspace": [I, P],
+    "pm_probe_ce": [P, P, I, I, P, P, P, P, P, ctypes.c_size_t, P],
+    "pm_probe_head_bwd": [P, P, I, I, I, P, P, P],
+    "pm_lars_workspace": [I, P],
+    "pm_lars_step": [P, I, P, P, ctypes.c_size_t, P],
 }
 
 ABI_VERSION = 16  # pm_abi_version() of the library these signatures describe
@@ -142,6 +150,11 @@ class AdamwSegment(ctypes.Structure):
 class GradSegment(ctypes.Structure):
     """pm_grad_segment of include/polypmae.h."""
     _fields_ = [("g", c_void_p), ("n", c_long), ("group", c_int)]
+
+
+class LarsSegment(ctypes.Structure):
+    """pm_lars_segment of include/polypmae.h."""
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("mu", c_void_p), ("n", c_long), ("is_matrix", c_int)]
 
 
 class BlockBwdDesc(ctypes.Structure):

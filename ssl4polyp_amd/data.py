@@ -246,6 +246,32 @@ def draw_rrc_boxes(B: int, height, width, generator: Optional[torch.Generator] =
     return out
 
 
+def draw_linprobe_boxes(B: int, height, width, generator: Optional[torch.Generator] = None, scale=(0.08, 1.0),
+                        ratio=(3.0 / 4.0, 4.0 / 3.0)):
+    """mae/util/crop.py RandomResizedCrop.get_params (the linear probe's training crop, main_linprobe.py:146) for B frames -> int32
+    [B, 4] = (top, left, h, w).  Not torchvision's sampler (draw_rrc_boxes): one draw, no retry loop and no central-crop fallback;
+    a box that does not fit is clamped to the frame, and the aspect ratio is exp of an f32 uniform between the f32 logs of `ratio`,
+    evaluated in f32 as the reference's torch.exp does.  One generator serves the batch in frame order (None: torch's global one,
+    as the reference uses it)."""
+    g = generator
+    hs = [int(v) for v in height] if isinstance(height, (Sequence, np.ndarray, torch.Tensor)) else [int(height)] * B
+    ws = [int(v) for v in width] if isinstance(width, (Sequence, np.ndarray, torch.Tensor)) else [int(width)] * B
+    if len(hs) != B or len(ws) != B:
+        raise ValueError("height / width: a scalar or one value per frame")
+    log_ratio = torch.log(torch.tensor(ratio))
+    out = np.zeros((B, 4), dtype=np.int32)
+    for b in range(B):
+        height, width = hs[b], ws[b]
+        target = height * width * torch.empty(1).uniform_(scale[0], scale[1], generator=g).item()
+        aspect = torch.exp(torch.empty(1).uniform_(log_ratio[0], log_ratio[1], generator=g)).item()
+        w = min(int(round(math.sqrt(target * aspect))), width)
+        h = min(int(round(math.sqrt(target / aspect))), height)
+        i = torch.randint(0, height - h + 1, size=(1,), generator=g).item()
+        j = torch.randint(0, width - w + 1, size=(1,), generator=g).item()
+        out[b] = (i, j, h, w)
+    return out
+
+
 def _check_boxes(boxes, hw) -> np.ndarray:
     """Crop boxes (top, left, h, w), one per frame, each non-empty and inside its own frame -- hw: int [B, 2] = (H_b, W_b), a
     uniform batch's one size broadcast -- as the int32 C-contiguous [B, 4] table the crop kernels read."""

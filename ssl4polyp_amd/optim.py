@@ -679,3 +679,80 @@ class LossScaler:
             self._state[1] = float(sd.get("_growth_tracker", 0))
         else:
             self._pending = dict(sd)
+
+
+class FusedLARS(torch.optim.Optimizer):
+    """LARS as the MAE linear probe uses it (mae/util/lars.py: the MoCo v3 implementation), the reference's constructor, one
+    `pm_lars_step` call per param group over a table of its tensors: parameters with more than one dimension get weight decay and
+    the trust ratio q = tc |p| / |g + wd p| (q = 1 when either norm is 0), the others neither; mu = momentum mu + dp, p -= lr mu.
+
+    The parameters are any contiguous f32 tensors on the GPU (the probe head's two, or views into a model's flat storage).  lr,
+    weight decay, momentum and the trust coefficient live in a device record per group that the kernels read: `step()` refreshes
+    it from `param_groups` without a host sync (so `lr_sched.adjust_learning_rate`, `lr_scale` included, works unchanged), and
+    under stream capture leaves it alone -- call `sync_hyper()` between graph replays.  `state_dict()` has the reference's layout
+    (per-parameter `mu`; the groups' lr / weight_decay / momentum / trust_coefficient) and `load_state_dict` accepts the
+    reference's."""
+
+    def __init__(self, params, lr=0, weight_decay=0, momentum=0.9, trust_coefficient=0.001):
+        defaults = dict(lr=lr, weight_decay=weight_decay, momentum=momentum, trust_coefficient=trust_coefficient)
+        super().__init__(params, defaults)
+        self._hyper: Optional[torch.Tensor] = None
+        self._hyper_host = None
+        self._tables: Dict[int, tuple] = {}
+
+    def _rows(self):
+        return [(float(g["lr"]), float(g["weight_decay"]), float(g["momentum"]), float(g["trust_coefficient"])) for g in self.param_groups]
+
+    def sync_hyper(self, device=None) -> None:
+        """Push the groups' hyper-parameters to the device records when they changed on the host (an asynchronous copy)."""
+        rows = self._rows()
+        if self._hyper is None or (device is not None and self._hyper.device != torch.device(device)) or \
+                self._hyper.shape[0] != len(rows):
+            if device is None:
+                device = next(p.device for g in self.param_groups for p in g["params"])
+            self._hyper = torch.zeros(len(rows), 4, dtype=torch.float32, device=device)
+            self._hyper_host = None
+        if rows != self._hyper_host:
+            self._hyper.copy_(torch.tensor(rows, dtype=torch.float32).pin_memory(), non_blocking=True)
+            self._hyper_host = rows
+
+    def _table(self, gi: int, group):
+        """(pm_lars_segment array, workspace) of the group's parameters that have a gradient; rebuilt when a buffer moved."""
+        live = [p for p in group["params"] if p.grad is not None]
+        for p in live:
+            if p.dtype != torch.float32 or p.device.type != "cuda" or not p.is_contiguous():
+                raise _lib.PolypMaeError("FusedLARS: parameters must be contiguous f32 tensors on the GPU")
+            if p.grad.dtype != torch.float32 or not p.grad.is_contiguous() or p.grad.device != p.device:
+                raise _lib.PolypMaeError("FusedLARS: gradients must be contiguous f32 tensors on the parameter's device")
+            if "mu" not in self.state[p]:
+                self.state[p]["mu"] = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        key = tuple((p.data_ptr(), p.grad.data_ptr(), self.state[p]["mu"].data_ptr(), p.numel(), p.ndim > 1) for p in live)
+        cached = self._tables.get(gi)
+        if cached is None or cached[0] != key:
+            if torch.cuda.is_current_stream_capturing():
+                raise _lib.PolypMaeError("FusedLARS: the set of gradients changed under stream capture; take one eager step first")
+            arr = (_lib.LarsSegment * max(len(key), 1))()
+            for i, (pp, gp, mp, n, mat) in enumerate(key):
+                arr[i] = _lib.LarsSegment(pp, gp, mp, n, 1 if mat else 0)
+            size = ctypes.c_size_t(0)
+            if key:
+                _lib.check(_lib.load().pm_lars_workspace(len(key), ctypes.byref(size)), "pm_lars_workspace")
+            ws = torch.empty(max(size.value // 8, 1), dtype=torch.float64, device=live[0].device) if key else None
+            cached = self._tables[gi] = (key, arr, ws)
+        return cached
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing() and self._hyper is not None):
+            self.sync_hyper()
+        lib = _lib.load()
+        for gi, group in enumerate(self.param_groups):
+            key, arr, ws = self._table(gi, group)
+            if not key:
+                continue
+            _lib.check(lib.pm_lars_step(arr, len(key), _ptr(self._hyper[gi]), _ptr(ws), ws.numel() * 8, _stream()), "pm_lars_step")
+        return loss

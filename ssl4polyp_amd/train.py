@@ -524,6 +524,86 @@ def train_epoch_cls(model, train_loader: Iterable, optimizer, device, pos_weight
     return stats
 
 
+# ---------------------------------------------------------------------------------------------------
+# linear probe (mae/main_linprobe.py through engine_finetune.train_one_epoch / evaluate)
+# ---------------------------------------------------------------------------------------------------
+def linprobe_schedule(epoch: int, n_iter: int, args) -> List[tuple]:
+    """[(lr in force, update after this micro-step?)] for the n_iter micro-steps of `epoch`, as engine_finetune.py:47-48, 71-75
+    runs them: the lr is adjusted when step % accum_iter == 0, at step / n_iter + epoch; the optimiser steps (and the gradients
+    are zeroed) when (step + 1) % accum_iter == 0."""
+    accum = max(int(getattr(args, "accum_iter", 1)), 1)
+    out, lr = [], 0.0
+    for it in range(n_iter):
+        if it % accum == 0:
+            lr = mae_lr(it / n_iter + epoch, args.lr, args.min_lr, args.warmup_epochs, args.epochs)
+        out.append((lr, (it + 1) % accum == 0))
+    return out
+
+
+def _probe_batch(batch, device, prepare):
+    if prepare is not None:
+        return prepare(batch)
+    return batch[0].to(device, non_blocking=True), torch.as_tensor(batch[-1]).to(device, non_blocking=True)
+
+
+def linprobe_one_epoch(model, data_loader: Iterable, optimizer, device, epoch: int, args, prepare: Optional[Callable] = None,
+                       printer: Optional[Callable] = print) -> Dict[str, float]:
+    """engine_finetune.train_one_epoch as main_linprobe calls it (no mixup, no clipping): per-iteration lr (linprobe_schedule),
+    softmax cross-entropy whose gradient is divided by accum_iter, LARS step + zero_grad every accum_iter micro-steps.  The loss
+    and the accuracy counts are summed on the device and read back once, at the end of the epoch (the reference reads
+    loss.item() every step).  `prepare(batch) -> (images f32 [B, 3, S, S], targets int64 [B])` on the device (default: the
+    batch's first and last entries, moved).  -> {"loss": mean of the batch means, "acc1", "acc5": per cent, "lr": the last lr}."""
+    from .probe import probe_ce
+    model.train(True)
+    accum = max(int(getattr(args, "accum_iter", 1)), 1)
+    n_iter = len(data_loader)
+    scale = torch.full((), 1.0 / accum, dtype=torch.float32, device=device)
+    acc = torch.zeros(5, dtype=torch.float64, device=device)   # sum of batch-mean losses, batches, correct at 1, at k, samples
+    optimizer.zero_grad(set_to_none=False)
+    lr = 0.0
+    t0 = time.perf_counter()
+    for it, batch in enumerate(data_loader):
+        if it % accum == 0:
+            lr = adjust_learning_rate(optimizer, it / n_iter + epoch, args)
+        imgs, targets = _probe_batch(batch, device, prepare)
+        loss, correct = probe_ce(model(imgs), targets, scale)
+        loss.backward()
+        acc[0] += loss.detach()
+        acc[1] += 1.0
+        acc[2:4] += correct
+        acc[4] += float(imgs.shape[0])
+        if (it + 1) % accum == 0:
+            optimizer.step()
+            optimizer.zero_grad(set_to_none=False)
+    s, n, c1, ck, m = acc.tolist()   # the epoch's one read-back
+    stats = {"loss": s / max(n, 1.0), "acc1": 100.0 * c1 / max(m, 1.0), "acc5": 100.0 * ck / max(m, 1.0), "lr": lr,
+             "seconds": time.perf_counter() - t0, "samples": int(m)}
+    if not math.isfinite(stats["loss"]):
+        raise FloatingPointError(f"Loss is {stats['loss']}, stopping training")  # engine_finetune.py:63-66
+    if printer is not None:
+        printer({"epoch": epoch, **stats})
+    return stats
+
+
+@torch.no_grad()
+def evaluate_probe(model, data_loader: Iterable, device, prepare: Optional[Callable] = None) -> Dict[str, float]:
+    """engine_finetune.evaluate with its meters: acc1 / acc5 (per cent) weighted by batch size, loss the mean of the batch means.
+    acc5 counts the target among the top min(5, C) logits (timm 0.4.12's accuracy(topk=(1, 5)) raises for C < 5; later timm
+    clamps k the same way).  One read-back per pass."""
+    from .probe import probe_ce
+    model.eval()
+    acc = torch.zeros(5, dtype=torch.float64, device=device)
+    for batch in data_loader:
+        imgs, targets = _probe_batch(batch, device, prepare)
+        loss, correct = probe_ce(model(imgs), targets)
+        acc[0] += loss
+        acc[1] += 1.0
+        acc[2:4] += correct
+        acc[4] += float(imgs.shape[0])
+    s, n, c1, ck, m = acc.tolist()
+    return {"loss": s / max(n, 1.0), "acc1": 100.0 * c1 / max(m, 1.0), "acc5": 100.0 * ck / max(m, 1.0), "samples": int(m)}
+
+
 def class_probabilities(logits: torch.Tensor) -> torch.Tensor:
     """tc.py:4700-4730: binary packs (n_class = 2) score with sigmoid(l1 - l0), multi-class with softmax -- computed on
     the device the logits live on.  Returns [B] (binary: P(class 1)) or [B, n_class]."""
