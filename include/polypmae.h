@@ -829,6 +829,66 @@ int pm_probe_head_bwd(const float* dlogits, const float* xhat, int B, int D, int
 int pm_lars_workspace(int n_segs, size_t* bytes);
 int pm_lars_step(const pm_lars_segment* segs, int n_segs, const float* hyper, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- end-to-end fine-tuning of the MAE encoder (mae/main_finetune.py, engine_finetune.py) ----------------------------------
+ * What the recipe puts around the block stack: timm's Mixup / CutMix of the batch (mode "batch"), SoftTargetCrossEntropy over the
+ * mixed, smoothed targets, the trainable global_pool (models_vit.py:46-48) and the plain Linear head.  Conventions of the probe
+ * section: f32 throughout, fixed summation order (no float atomics), nothing allocated, the stream passed in; every refusal returns
+ * before the first launch; everything 16-byte aligned unless stated.
+ *
+ * pm_mix_record: the draw of one step, on the DEVICE (the host writes it through pinned memory with an asynchronous copy, so no
+ *   launch argument changes from step to step and a captured step follows new draws).  lam and one_minus_lam are both rounded from
+ *   the host's doubles (one_minus_lam is NOT 1.f - lam).  use_cutmix != 0: the box rows [yl, yh) x columns [xl, xh).
+ *
+ * pm_mix_batch: x f32 [B, C, H, W] in place; sample b is paired with B - 1 - b (timm's x.flip(0)); one thread owns the same
+ *   elements of both members of a pair.  B odd is PM_ESHAPE (timm asserts an even batch); C H W < 2^31.
+ *     Mixup:   x_b <- fl(fl(lam x_b) + fl(one_minus_lam x_p)) and the same for the partner, from the OLD values; two products and
+ *              one sum, never a fused multiply-add: torch's x.flip(0).mul_(1 - lam); x.mul_(lam).add_(.) bit for bit.
+ *     CutMix:  inside the box the pair swaps its old values; outside nothing is read or written.  An empty box writes nothing; the
+ *              box is clipped to the image; xl may have any alignment.
+ *   enabled == 0: the host drew lam == 1 without a box -- every check, no launch.  (A record that holds that draw makes the
+ *   launched kernel write nothing either.)  rec: 4-byte aligned.
+ *
+ * pm_soft_ce: timm's SoftTargetCrossEntropy over mixup_target, the targets never materialised.  logits [B, C], int64 target [B];
+ *     off = smoothing / C, on = 1 - smoothing + off (in double, rounded to f32, as timm's one_hot stores them)
+ *     t_b  = lam onehot(y_b; on, off) + one_minus_lam onehot(y_{B-1-b}; on, off)     (the two weights ADD when the classes coincide)
+ *     loss = mean_b sum_c t_bc (lse_b - z_bc);   dlogits = (softmax - t) / B x scale[0]
+ *   rec NULL: lam = 1, one_minus_lam = 0 -- then it is LabelSmoothingCrossEntropy(smoothing), and with smoothing = 0
+ *   torch.nn.CrossEntropyLoss().  scale: a device scalar (1 / accum_iter), as for pm_probe_ce; dlogits NULL: not computed.  A target
+ *   of the row or of its partner outside [0, C) makes the loss NaN and gives the row a zero gradient.  Any C >= 1, any B <= 65535
+ *   (the middle row of an odd batch is its own partner).  4-byte alignment (target: 8).  workspace: pm_soft_ce_workspace bytes.
+ *
+ * pm_pool_norm_fwd_train: pm_pool_norm_fwd (same two-stage sum: feat has its bits) that also writes the pooled row [B, D] and
+ *   mean / rstd [B] of the LayerNorm for the backward.  workspace: pm_pool_norm_workspace bytes.
+ * pm_pool_norm_bwd: from dfeat [B, D]: dpooled = LayerNorm backward on the pooled row; dx[b, 0, :] = 0, dx[b, n >= 1, :] =
+ *   dpooled[b] / (N - 1), written as f32 dx [B, N, D] and as its copy dx_act in act_dtype (round to nearest even; PM_F32: a second
+ *   f32 copy), one coalesced pass of 16-byte stores.  dx NULL: not computed (dx_act must be NULL too); dx_act NULL: f32 only.
+ *   dgamma[d] += sum_b dfeat xhat, dbeta[d] += sum_b dfeat, b ascending, ONE addition into what they held (accum_iter; the caller
+ *   zeroes them for a fresh gradient); NULL: the parameter is frozen, nothing is written.  N >= 2, D % 4 == 0, D <= 2048,
+ *   B <= 65535.  workspace: pm_pool_norm_bwd_workspace bytes.
+ *
+ * pm_linear_head_fwd: logits [B, C] = feat [B, D] W^T + bias, W [C, D].  D % 4 == 0, B, C <= 65535; logits / bias 4-byte aligned.
+ * pm_linear_head_dfeat: dfeat [B, D] = dlogits [B, C] W, summed over c in ascending order.  dlogits 4-byte aligned.
+ *   (dW / dbias of this head: pm_probe_head_bwd with feat as xhat.) */
+typedef struct pm_mix_record {
+  float lam;
+  float one_minus_lam;
+  int use_cutmix;
+  int yl, yh, xl, xh;
+  int reserved;
+} pm_mix_record;
+int pm_mix_batch(float* x, int B, int C, int H, int W, const pm_mix_record* rec, int enabled, void* stream);
+int pm_soft_ce_workspace(int B, size_t* bytes);
+int pm_soft_ce(const float* logits, const long long* target, int B, int C, const pm_mix_record* rec, float smoothing,
+               const float* scale, float* loss, float* dlogits, void* workspace, size_t ws_bytes, void* stream);
+int pm_pool_norm_fwd_train(const float* x, int B, int N, int D, const float* gamma, const float* beta, float eps, float* feat,
+                           float* pooled, float* mean, float* rstd, void* workspace, size_t ws_bytes, void* stream);
+int pm_pool_norm_bwd_workspace(int B, int N, int D, size_t* bytes);
+int pm_pool_norm_bwd(const float* dfeat, const float* pooled, const float* mean, const float* rstd, const float* gamma, int B, int N,
+                     int D, float* dx, void* dx_act, int act_dtype, float* dgamma, float* dbeta, void* workspace, size_t ws_bytes,
+                     void* stream);
+int pm_linear_head_fwd(const float* feat, int B, int D, int C, const float* W, const float* bias, float* logits, void* stream);
+int pm_linear_head_dfeat(const float* dlogits, const float* W, int B, int D, int C, float* dfeat, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,6 +104,14 @@ SIGNATURES = {
     "pm_probe_head_bwd": [P, P, I, I, I, P, P, P],
     "pm_lars_workspace": [I, P],
     "pm_lars_step": [P, I, P, P, ctypes.c_size_t, P],
+    "pm_mix_batch": [P, I, I, I, I, P, I, P],
+    "pm_soft_ce_workspace": [I, P],
+    "pm_soft_ce": [P, P, I, I, P, F, P, P, P, P, ctypes.c_size_t, P],
+    "pm_pool_norm_fwd_train": [P, I, I, I, P, P, F, P, P, P, P, P, ctypes.c_size_t, P],
+    "pm_pool_norm_bwd_workspace": [I, I, I, P],
+    "pm_pool_norm_bwd": [P, P, P, P, P, I, I, I, P, P, I, P, P, P, ctypes.c_size_t, P],
+    "pm_linear_head_fwd": [P, I, I, I, P, P, P, P],
+    "pm_linear_head_dfeat": [P, P, I, I, I, P, P],
 }
 
 ABI_VERSION = 16  # pm_abi_version() of the library these signatures describe
@@ -155,6 +163,12 @@ class GradSegment(ctypes.Structure):
 class LarsSegment(ctypes.Structure):
     """pm_lars_segment of include/polypmae.h."""
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("mu", c_void_p), ("n", c_long), ("is_matrix", c_int)]
+
+
+class MixRecord(ctypes.Structure):
+    """pm_mix_record of include/polypmae.h (eight 4-byte words)."""
+    _fields_ = [("lam", c_float), ("one_minus_lam", c_float), ("use_cutmix", c_int), ("yl", c_int), ("yh", c_int), ("xl", c_int),
+                ("xh", c_int), ("reserved", c_int)]
 
 
 class BlockBwdDesc(ctypes.Structure):

@@ -1,5 +1,7 @@
 """The ViT of the MAE linear-probe / fine-tune entry points (mae/models_vit.py) on the encoder runtime of this package, and what
-mae/main_linprobe.py does to it: the BatchNorm + Linear probe head and the loading of a pre-training checkpoint.
+mae/main_linprobe.py does to it: the BatchNorm + Linear probe head and the loading of a pre-training checkpoint.  With the plain
+Linear head it is built with, the model is the trainable classifier of mae/main_finetune.py (_VitFinetuneFn, csrc/pm_finetune.hip;
+load_pretrained_for_finetune); what follows describes the probe.
 
 State-dict keys are the reference's: cls_token, pos_embed, patch_embed.*, blocks.*, norm.* (cls token) or fc_norm.* (global_pool),
 head.weight, head.bias -- and head.0.running_mean / running_var / num_batches_tracked, head.1.weight / bias after add_probe_head.
@@ -9,6 +11,7 @@ frozen in this protocol, so the feature pass records nothing for a backward; the
 encoder's precision mode."""
 from __future__ import annotations
 
+import ctypes
 from functools import partial
 from typing import Optional
 
@@ -16,15 +19,17 @@ import torch
 from torch import nn
 
 from . import _lib
-from .engine import BlockStack, StackGeom
-from .models import (_DEFAULT_PRECISION, Block, PatchEmbed, _ClassifierBase, _EncoderFrontMixin, _Runtime, _update_gate)
+from .engine import BlockStack, StackGeom, _ptr, _stream
+from .models import (_DEFAULT_PRECISION, Block, PatchEmbed, _ClassifierBase, _EncoderFrontMixin, _Needs, _Runtime, _plan_grads,
+                     _update_gate)
 from .probe import ProbeHead, pool_norm
 
 
 class VisionTransformer(_ClassifierBase):
     """mae/models_vit.py:20-53 (timm 0.4.12 VisionTransformer + global_pool), same seeded initialisation order as
-    models.VisionTransformer_from_Any.  forward(imgs) = head(forward_features(imgs)); the head must be the probe head
-    (add_probe_head): the plain Linear of the fine-tune recipe has no kernel here and is refused."""
+    models.VisionTransformer_from_Any.  With the probe head (add_probe_head) forward(imgs) = head(forward_features(imgs)) over the
+    frozen, forward-only encoder; with the plain Linear it is built with, forward is the trainable classifier of the fine-tune
+    recipe (main_finetune.py), one autograd node over the engine.  Stochastic depth (drop_path) is not built."""
 
     def __init__(self, img_size=224, patch_size=16, embed_dim=768, depth=12, num_heads=12, num_classes=1000, global_pool=False,
                  precision: Optional[str] = None):
@@ -85,11 +90,153 @@ class VisionTransformer(_ClassifierBase):
         rt.put_ws(g, ws)
         return x
 
+    def no_weight_decay(self):
+        """timm 0.4.12 VisionTransformer.no_weight_decay (main_finetune.py:306)."""
+        return {"pos_embed", "cls_token"}
+
     def forward(self, imgs: torch.Tensor) -> torch.Tensor:
-        if not isinstance(self.head, ProbeHead):
-            raise _lib.PolypMaeError("models_vit.VisionTransformer runs with the linear-probe head only: call add_probe_head(model) "
-                                     "first (the fine-tune recipe's plain Linear head is not built)")
-        return self.head(self.forward_features(imgs))
+        """Probe head (add_probe_head): head(forward_features(imgs)), the encoder frozen and forward-only.  Plain nn.Linear head
+        (the fine-tune recipe, main_finetune.py): front, block stack, pooling and head as one autograd node (_VitFinetuneFn)."""
+        if isinstance(self.head, ProbeHead):
+            return self.head(self.forward_features(imgs))
+        if not isinstance(self.head, nn.Linear):
+            raise _lib.PolypMaeError(f"models_vit.VisionTransformer: the head must be the probe head or a plain nn.Linear "
+                                     f"(got {type(self.head).__name__})")
+        rt = self._rt
+        rt.ensure(imgs.device)
+        assert imgs.shape[2] == self.patch_embed.img_size[0] and imgs.shape[3] == self.patch_embed.img_size[1]
+        from . import ops  # registers torch.ops.polypmae.* on first use
+        return torch.ops.polypmae.vit_finetune_forward(imgs, ops.register_runtime(rt), list(rt.flat.params))
+
+
+def _workspace(query, what: str, *dims) -> torch.Tensor:
+    size = ctypes.c_size_t(0)
+    _lib.check(query(*dims, ctypes.byref(size)), what)
+    return size.value
+
+
+class _VitFinetuneFn(torch.autograd.Function):
+    """imgs -> logits of models_vit.VisionTransformer with its plain Linear head (models_vit.py:34-53), one node, modelled on
+    models._VitClsFn.  global_pool: the dense block stack, then pm_pool_norm_fwd_train / pm_pool_norm_bwd (fc_norm of the mean of the
+    patch rows).  cls token: pm_vit_head_fwd / _bwd without their Linear (W = NULL / dfeat) -- D <= 1024 there, and the cls-row top
+    block under _VitClsFn's own condition.  The head, the pool and the loss run in f32 in every precision mode."""
+
+    @staticmethod
+    def forward(ctx, rt: _Runtime, imgs: torch.Tensor, names, *params):
+        k, f, mod, g = rt.k, rt.flat, rt.module, rt.enc_geom
+        lib = k.lib
+        B = imgs.shape[0]
+        L = mod.patch_embed.num_patches
+        N, D = L + 1, g.dim
+        pool = mod.global_pool
+        norm = "fc_norm" if pool else "norm"
+        needs = ctx.needs_input_grad[3:] if rt.grad_enabled else (False,) * len(params)
+        need = _Needs(names, needs, rt.unused)
+        training = any(needs)
+        below = any(nd for n, nd in zip(names, needs) if not n.startswith(("head.", norm + ".")))   # anything under the final norm
+        imgs = imgs.contiguous().float()
+        cols, x0 = _EncoderFrontMixin.front_fwd(rt, imgs, None, L)
+        ws = rt.get_ws(g, B, N, below)
+        W, _ = rt.stack_weights("blocks.", g.depth)
+        cls_top = (not pool) and k.SPARSE_TOP and N > 1 and (B % 8 == 0 or not training)
+        x = BlockStack(k, g).forward(ws, x0, W, before_block=_update_gate(rt, "blocks."), keep_from=need.keep_from(g.depth),
+                                     cls_top=cls_top)
+        Nh = 1 if ws.cls_top else N
+        rt.wait_updates()
+        dev, f32 = imgs.device, torch.float32
+        C = mod.head.weight.shape[0]
+        feat = torch.empty(B, D, dtype=f32, device=dev)
+        mean, rstd = torch.empty(B, dtype=f32, device=dev), torch.empty(B, dtype=f32, device=dev)
+        pooled = None
+        gamma, beta = f.param_view(norm + ".weight"), f.param_view(norm + ".bias")
+        if pool:
+            pooled = torch.empty(B, D, dtype=f32, device=dev)
+            nbytes = _workspace(lib.pm_pool_norm_workspace, "pm_pool_norm_workspace", B, N, D)
+            scratch = torch.empty((nbytes + 3) // 4, dtype=f32, device=dev)
+            _lib.check(lib.pm_pool_norm_fwd_train(_ptr(x), B, N, D, _ptr(gamma), _ptr(beta), rt.eps, _ptr(feat), _ptr(pooled), _ptr(mean),
+                                                  _ptr(rstd), _ptr(scratch), scratch.numel() * 4, _stream()), "pm_pool_norm_fwd_train")
+        else:
+            _lib.check(lib.pm_vit_head_fwd(_ptr(x), Nh, 0, _ptr(gamma), _ptr(beta), None, None, _ptr(feat), None, _ptr(mean), _ptr(rstd),
+                                           None, B, D, 0, rt.eps, _stream()), "pm_vit_head_fwd")
+        logits = torch.empty(B, C, dtype=f32, device=dev)
+        _lib.check(lib.pm_linear_head_fwd(_ptr(feat), B, D, C, _ptr(f.param_view("head.weight")), _ptr(f.param_view("head.bias")),
+                                          _ptr(logits), _stream()), "pm_linear_head_fwd")
+        if training:
+            ctx.rt, ctx.names, ctx.ws = rt, names, ws
+            xs = x
+            if not below:   # nothing under the final norm trains: keep what its backward reads, release the stack's buffers
+                xs = None if pool else x.view(B, Nh, D)[:, 0].clone()
+                rt.put_ws(g, ws)
+                ctx.ws = None
+                cols = x0 = None
+            ctx.saved = (cols, x0, xs, feat, pooled, mean, rstd)
+            ctx.dims = (B, L, N, D, C, pool, below, Nh if below else 1)
+        else:
+            rt.put_ws(g, ws)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        rt, names, ws = ctx.rt, ctx.names, ctx.ws
+        k, f, mod, g = rt.k, rt.flat, rt.module, rt.enc_geom
+        lib = k.lib
+        cols, x0, x, feat, pooled, mean, rstd = ctx.saved
+        B, L, N, D, C, pool, below, x_rows = ctx.dims
+        norm = "fc_norm" if pool else "norm"
+        needs = list(ctx.needs_input_grad[3:])
+        need = _Needs(names, needs, rt.unused)
+        accumulate = _plan_grads(rt, names, needs)
+        dev, f32 = dlogits.device, torch.float32
+        dlogits = dlogits.contiguous().float()
+        # the head: dW / dbias are ONE addition into what the flat gradient held (pm_probe_head_bwd)
+        if need("head.weight") or need("head.bias"):
+            if not accumulate and need("head.weight"):
+                f.grad_view("head.weight").zero_()   # (a matrix: _plan_grads zeroed the vectors only)
+            dW = f.grad_view("head.weight") if need("head.weight") else torch.zeros(C, D, dtype=f32, device=dev)
+            db = f.grad_view("head.bias") if need("head.bias") else torch.zeros(C, dtype=f32, device=dev)
+            _lib.check(lib.pm_probe_head_bwd(_ptr(dlogits), _ptr(feat), B, D, C, _ptr(dW), _ptr(db), _stream()), "pm_probe_head_bwd")
+        trainable = need.blocks("blocks.", g.depth)
+        front = need.front(True)
+        below_head = front or any(trainable)
+        dgamma = f.grad_view(norm + ".weight") if need(norm + ".weight") else None
+        dbeta = f.grad_view(norm + ".bias") if need(norm + ".bias") else None
+        if below_head or dgamma is not None or dbeta is not None:
+            dfeat = torch.empty(B, D, dtype=f32, device=dev)
+            _lib.check(lib.pm_linear_head_dfeat(_ptr(dlogits), _ptr(f.param_view("head.weight")), B, D, C, _ptr(dfeat), _stream()),
+                       "pm_linear_head_dfeat")
+            if below_head and ws.cls_top:   # the head's gradient on the B cls rows only: what the cls-row top block takes
+                tc = BlockStack.top_compact(ws, g, k.act_dtype, dev)
+                dx, dx_act = tc["dx"], tc["dx_act"]
+            else:
+                dx = ws.dx[0] if below_head else None
+                dx_act = ws.dx_act[0] if below_head else None
+            gamma = f.param_view(norm + ".weight")
+            if pool:
+                nbytes = _workspace(lib.pm_pool_norm_bwd_workspace, "pm_pool_norm_bwd_workspace", B, N, D)
+                scratch = torch.empty((nbytes + 3) // 4, dtype=f32, device=dev)
+                _lib.check(lib.pm_pool_norm_bwd(_ptr(dfeat), _ptr(pooled), _ptr(mean), _ptr(rstd), _ptr(gamma), B, N, D, _ptr(dx),
+                                                _ptr(dx_act), k.act, _ptr(dgamma), _ptr(dbeta), _ptr(scratch), scratch.numel() * 4,
+                                                _stream()), "pm_pool_norm_bwd")
+            else:
+                _lib.check(lib.pm_vit_head_bwd(None, _ptr(dfeat), _ptr(x), x_rows, 0, _ptr(gamma), None, None, None, _ptr(mean),
+                                               _ptr(rstd), _ptr(dx), _ptr(dx_act), k.act, None, None, _ptr(dgamma), _ptr(dbeta), B, D, 0,
+                                               _stream()), "pm_vit_head_bwd")
+        sync = rt.grad_sync
+        if below_head:
+            W, G = rt.stack_weights("blocks.", g.depth)
+            cb = (lambda i: sync.block_done("blocks.", i)) if sync is not None else None
+            dx0, _ = BlockStack(k, g).backward(ws, x0, W, G, dx, dx_act, False, trainable, front, lambda n, i: accumulate, cb,
+                                               defer_join=True)
+            if front and dx0 is not None:
+                _EncoderFrontMixin.front_bwd(rt, dx0, cols, None, B, L, accumulate, need, True)
+            BlockStack.join_deferred(ws)
+        if sync is not None:
+            sync.backward_done()
+        if ws is not None:
+            rt.put_ws(g, ws)
+        ctx.saved = None
+        grads = [None if (accumulate or not need(n)) else f.grad_view(n) for n in names]
+        return (None, None, None, *grads)
 
 
 def vit_base_patch16(num_classes=1000, global_pool=False, **kwargs):
@@ -144,4 +291,25 @@ def load_pretrained_for_probe(model: VisionTransformer, checkpoint_model: dict):
     want = {"head.weight", "head.bias"} | ({"fc_norm.weight", "fc_norm.bias"} if model.global_pool else set())
     assert set(msg.missing_keys) == want, f"missing keys {sorted(msg.missing_keys)}; expected {sorted(want)}"
     nn.init.trunc_normal_(model.head.weight, std=0.01)   # following MoCo v3
+    return msg
+
+
+def load_pretrained_for_finetune(model: VisionTransformer, checkpoint_model: dict):
+    """main_finetune.py:255-279 on the `["model"]` dict of a main_pretrain checkpoint: the key handling of load_pretrained_for_probe
+    (head keys of another shape dropped, non-strict load, the missing keys must be exactly the head -- and fc_norm with global_pool),
+    then head.weight gets trunc-normal std 2e-5.  Returns load_state_dict's result."""
+    checkpoint_model = dict(checkpoint_model)
+    own = model.state_dict()
+    for k in ("head.weight", "head.bias"):
+        if k in checkpoint_model and checkpoint_model[k].shape != own[k].shape:
+            print(f"Removing key {k} from pretrained checkpoint")
+            del checkpoint_model[k]
+    interpolate_pos_embed(model, checkpoint_model)
+    msg = model.load_state_dict(checkpoint_model, strict=False)
+    if model.global_pool:
+        assert set(msg.missing_keys) == {"head.weight", "head.bias", "fc_norm.weight", "fc_norm.bias"}, \
+            f"missing keys {sorted(msg.missing_keys)}"
+    else:
+        assert set(msg.missing_keys) == {"head.weight", "head.bias"}, f"missing keys {sorted(msg.missing_keys)}"
+    nn.init.trunc_normal_(model.head.weight, std=2e-5)   # manually initialize fc layer
     return msg

@@ -6,6 +6,7 @@ North-star wording: "hand-written HIP for CDNA4 exposed as custom torch ops thro
         polypmae::vit_forward(imgs, runtime, pool, head, params) -> logits | features       (models.py:129-140, 211-222)
         polypmae::mae_forward(imgs, noise, mask_ratio, runtime, params) -> (loss, pred, mask) (models_mae.py:216-220)
         polypmae::supervised_loss(logits, targets, pos_weight?, class_weights?) -> loss       (tc.py:3347-3374, 6086-6104)
+        polypmae::vit_finetune_forward(imgs, runtime, params) -> logits       (mae/models_vit.py:34-53 with its plain Linear head)
     Their autograd kernels are the one-node autograd.Functions of models.py (the engine owns every intermediate buffer,
     so a step is one node, not ~200);
   * per-kernel functional ops with autograd, for callers that compose their own blocks (the list of SURVEY 8-b):
@@ -61,6 +62,7 @@ def _k(t_or_dtype, eps: float = 1e-6) -> Kernels:
 _DEF.define("vit_forward(Tensor imgs, int runtime, int pool, bool head, Tensor[] params) -> Tensor")
 _DEF.define("mae_forward(Tensor imgs, Tensor noise, float mask_ratio, int runtime, Tensor[] params) -> (Tensor, Tensor, Tensor)")
 _DEF.define("supervised_loss(Tensor logits, Tensor targets, Tensor? pos_weight, Tensor? class_weights) -> Tensor")
+_DEF.define("vit_finetune_forward(Tensor imgs, int runtime, Tensor[] params) -> Tensor")
 
 
 def _vit_forward(imgs, runtime, pool, head, params):
@@ -84,6 +86,13 @@ def _supervised_loss(logits, targets, pos_weight, class_weights):
     return _SupervisedLossFn.apply(logits, targets, pos_weight, class_weights)
 
 
+def _vit_finetune_forward(imgs, runtime, params):
+    from .models_vit import _VitFinetuneFn
+    rt = _rt(runtime)
+    rt.grad_enabled = torch.is_grad_enabled()   # (as for vit_forward: grad mode is already off inside Function.forward)
+    return _VitFinetuneFn.apply(rt, imgs, rt.flat.names, *params)
+
+
 # AutogradCUDA: the kernel that runs for CUDA (HIP) tensors whether or not a gradient is required; it builds the
 # one-node graph itself.  No CPU / CompositeImplicit registration exists: a CPU tensor fails in the dispatcher.
 _IMPL = torch.library.Library("polypmae", "IMPL")
@@ -97,6 +106,7 @@ def _impl(name, fn):
 _impl("vit_forward", _vit_forward)
 _impl("mae_forward", _mae_forward)
 _impl("supervised_loss", _supervised_loss)
+_impl("vit_finetune_forward", _vit_finetune_forward)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -217,5 +227,5 @@ _impl("linear_bias_gelu", lambda x, w, b: _LinearFn.apply(x, w, b, None, EPI_GEL
 _impl("linear_bias_residual", lambda x, w, b, r: _LinearFn.apply(x, w, b, r, EPI_RESIDUAL))
 _impl("attention", lambda qkv, heads: _AttentionFn.apply(qkv, int(heads)))
 
-OP_NAMES = ("vit_forward", "mae_forward", "supervised_loss", "layernorm", "linear_bias", "linear_bias_gelu",
+OP_NAMES = ("vit_forward", "mae_forward", "supervised_loss", "vit_finetune_forward", "layernorm", "linear_bias", "linear_bias_gelu",
             "linear_bias_residual", "attention")

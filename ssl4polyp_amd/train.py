@@ -585,6 +585,62 @@ def linprobe_one_epoch(model, data_loader: Iterable, optimizer, device, epoch: i
     return stats
 
 
+def finetune_one_epoch(model, data_loader: Iterable, optimizer, device, epoch: int, args, mixup_fn=None, loss_scaler=None,
+                       prepare: Optional[Callable] = None, log_every: int = 20, printer: Optional[Callable] = print) -> Dict[str, float]:
+    """engine_finetune.train_one_epoch (:25-101) as main_finetune calls it, without its host syncs: the lr is adjusted when
+    step % accum_iter == 0 at step / len + epoch (per-group lr_scale honoured), the batch is mixed in place (mixup_fn: mixup.Mixup, or
+    None), the loss is mixup.soft_target_ce -- SoftTargetCrossEntropy over the mixed targets, LabelSmoothingCrossEntropy
+    (args.smoothing) or plain cross-entropy without mixing -- whose gradient is divided by accum_iter; backward goes through
+    loss_scaler.scale in fp16 (optim.LossScaler); optimizer.step(max_norm=args.clip_grad) and zero_grad every accum_iter micro-steps.
+    The reference reads loss.item() every step and stops on a non-finite value; here the losses are summed on the device and read
+    back every log_every updates and at the end of the epoch, where the same stop is raised.
+    -> {"loss": mean of the batch losses, "lr": the last (largest) lr, "seconds", "samples"}."""
+    from .mixup import soft_target_ce
+    model.train(True)
+    accum = max(int(getattr(args, "accum_iter", 1)), 1)
+    scale_loss = loss_scaler.scale if loss_scaler is not None else (lambda x: x)
+    opt_step = _clip_step(optimizer, loss_scaler, getattr(args, "clip_grad", None))
+    smoothing = mixup_fn.label_smoothing if mixup_fn is not None else float(getattr(args, "smoothing", 0.0))
+    n_iter = len(data_loader)
+    scale = torch.full((), 1.0 / accum, dtype=torch.float32, device=device)
+    acc = torch.zeros(2, dtype=torch.float64, device=device)   # sum of the batch losses and their number since the last read-back
+    total, count, samples, lr = 0.0, 0.0, 0, 0.0
+    optimizer.zero_grad(set_to_none=True)
+    t0 = time.perf_counter()
+
+    def flush(step):
+        nonlocal total, count
+        s, n = acc.tolist()
+        acc.zero_()
+        if not math.isfinite(s):
+            raise FloatingPointError(f"Loss is {s / max(n, 1.0)}, stopping training")  # engine_finetune.py:63-66
+        total, count = total + s, count + n
+        if printer is not None and n > 0:
+            printer({"epoch": epoch, "step": step, "loss": s / n, "lr": lr})
+
+    for it, batch in enumerate(data_loader):
+        if it % accum == 0:
+            lr = adjust_learning_rate(optimizer, it / n_iter + epoch, args)
+        imgs, targets = _probe_batch(batch, device, prepare)
+        if mixup_fn is not None:
+            if prepare is None:
+                imgs = imgs.clone()   # (the mixing is in place: never into the loader's own tensor)
+            imgs, targets = mixup_fn(imgs, targets)
+        loss = soft_target_ce(model(imgs), targets, mixup_fn.state if mixup_fn is not None else None, smoothing, scale)
+        scale_loss(loss).backward()
+        acc[0] += loss.detach()
+        acc[1] += 1.0
+        samples += int(imgs.shape[0])
+        if (it + 1) % accum == 0:
+            opt_step()
+            optimizer.zero_grad(set_to_none=True)
+        if (it + 1) % (log_every * accum) == 0:
+            flush(it + 1)
+    flush(n_iter)
+    stats = {"loss": total / max(count, 1.0), "lr": lr, "seconds": time.perf_counter() - t0, "samples": samples}
+    return stats
+
+
 @torch.no_grad()
 def evaluate_probe(model, data_loader: Iterable, device, prepare: Optional[Callable] = None) -> Dict[str, float]:
     """engine_finetune.evaluate with its meters: acc1 / acc5 (per cent) weighted by batch size, loss the mean of the batch means.
