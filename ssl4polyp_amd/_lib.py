@@ -240,6 +240,13 @@ def check(status: int, what: str) -> None:
         raise PolypMaeError(f"{what} failed: {load().pm_strerror(status).decode()} (status {status})")
 
 
+def workspace_bytes(name: str, *dims) -> int:
+    """The byte count the `pm_*_workspace` query `name` reports for `dims` (a refusal raises under the query's own name)."""
+    size = ctypes.c_size_t(0)
+    check(getattr(load(), name)(*dims, ctypes.byref(size)), name)
+    return int(size.value)
+
+
 def dtype_code(torch_dtype) -> int:
     import torch
 

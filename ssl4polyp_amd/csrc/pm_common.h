@@ -176,6 +176,26 @@ __device__ __forceinline__ float wave_sum(float v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// sum over a workgroup of 256 threads (4 waves), fixed order: butterfly inside a wave, then (w0 + w1) + (w2 + w3) through red[4] in
+// LDS; every thread gets the result
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();  // (red may still be read from the previous call)
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
 // sum of p[b * stride] for b = first, first + step, ... < n, in that fixed order (deterministic), with U loads in
 // flight at a time (the second-stage reductions are latency-bound otherwise)
 template <int U>

@@ -16,37 +16,25 @@
 //   soft_ce_rows / soft_ce_finish one wave per sample: log-sum-exp, loss_b = sum_c t_c (lse - z_c) with the target row
 //                                 t = lam onehot(y_b) + (1 - lam) onehot(y_partner) built on the fly (the two weights ADD when the
 //                                 classes coincide), dlogits = (softmax - t) s / B; then one workgroup adds up the rows.
-//   pool_partial / pool_norm      pm_probe.hip's two-stage pool + fc_norm, statement for statement (feat has its bits), that also
-//                                 leaves the pooled row and mean / rstd for the backward.
+//   pool_partial / pool_norm<true>, linear_kernel   pm_pool_head.h, shared with pm_probe.hip: the two-stage pool + fc_norm that also
+//                                 leaves the pooled row and mean / rstd for the backward, and logits = feat W^T + bias.
 //   pool_bwd_row / _fill / _pgrad LayerNorm backward on the pooled row, / (N - 1), into a [B, D] row; ONE coalesced pass writes
 //                                 that row to every patch row of dx (f32) and dx_act (16-byte stores), zeros to the cls row;
 //                                 dgamma / dbeta: one thread per column, samples in ascending order, one addition into the prior.
-//   linear_kernel                 logits = feat W^T + bias: one wave per (sample, class), 16 classes per wave (the probe's shape).
 //   dfeat_kernel                  dfeat = dlogits W: 8 samples x 4 columns per thread, classes in ascending order; W is read once
 //                                 per 8 samples.
 #include <math.h>
 
-#include "pm_common.h"
+#include "pm_pool_head.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / PM_WAVE;
-constexpr int kMaxD = 2048;     // two 16-byte vectors per lane in pool_norm_kernel
-constexpr int kPoolRows = 32;   // patch rows per first-stage workgroup (pm_probe.hip's)
 constexpr int kMaxBlocks = 2048;
 constexpr int kDfeatRows = 8;
 constexpr int kDfeatDepth = 16;
 constexpr int kPgradDepth = 16;
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();  // (red may still be read from the previous call)
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // one rounding each: an instruction the compiler cannot fuse with its neighbour
 __device__ __forceinline__ float mul_rn(float a, float b) {
@@ -176,85 +164,6 @@ __global__ __launch_bounds__(kThreads) void soft_ce_finish_kernel(const float* _
   if (threadIdx.x == 0) loss[0] = total / (float)B;
 }
 
-// ------------------------------------------------------------------------------------------------ pool + fc_norm, training
-// (pm_probe.hip's pool_partial_kernel / pool_norm_kernel, the same statements in the same order)
-__global__ __launch_bounds__(kThreads) void pool_partial_kernel(const float* __restrict__ x, int N, int D, int S,
-                                                                float* __restrict__ partial) {
-  const int b = blockIdx.x / S, s = blockIdx.x % S;
-  const int n0 = 1 + s * kPoolRows;
-  const int n1 = n0 + kPoolRows < N ? n0 + kPoolRows : N;
-  const float* base = x + (long)b * N * D;
-  float* out = partial + (long)blockIdx.x * D;
-  for (int c = threadIdx.x * 4; c < D; c += kThreads * 4) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    int n = n0;
-    for (; n + 3 < n1; n += 4) {
-      f32x4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(base + (long)(n + u) * D + c);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc += v[u];
-    }
-    for (; n < n1; ++n) acc += *reinterpret_cast<const f32x4*>(base + (long)n * D + c);
-    *reinterpret_cast<f32x4*>(out + c) = acc;
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void pool_norm_kernel(const float* __restrict__ partial, int N, int D, int S,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                             float* __restrict__ feat, float* __restrict__ pooled,
-                                                             float* __restrict__ mean_out, float* __restrict__ rstd_out) {
-  __shared__ float red[kWaves];
-  const int b = blockIdx.x;
-  const float* rows = partial + (long)b * S * D;
-  const float den = (float)(N - 1);
-  f32x4 v[2];
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int c = (threadIdx.x + j * kThreads) * 4;
-    v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (c < D) {
-      for (int s = 0; s < S; ++s) v[j] += *reinterpret_cast<const f32x4*>(rows + (long)s * D + c);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[j][e] = v[j][e] / den;
-        sum += v[j][e];
-      }
-    }
-  }
-  const float mean = block_sum(sum, red) / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int c = (threadIdx.x + j * kThreads) * 4;
-    if (c < D) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float d = v[j][e] - mean;
-        q += d * d;
-      }
-    }
-  }
-  const float rstd = rsqrtf(block_sum(q, red) / (float)D + eps);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int c = (threadIdx.x + j * kThreads) * 4;
-    if (c < D) {
-      const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + c), bt = *reinterpret_cast<const f32x4*>(beta + c);
-      f32x4 y;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) y[e] = (v[j][e] - mean) * rstd * g[e] + bt[e];
-      *reinterpret_cast<f32x4*>(feat + (long)b * D + c) = y;
-      *reinterpret_cast<f32x4*>(pooled + (long)b * D + c) = v[j];
-    }
-  }
-  if (threadIdx.x == 0) {
-    mean_out[b] = mean;
-    rstd_out[b] = rstd;
-  }
-}
-
 // ------------------------------------------------------------------------------------------------ pool + fc_norm, backward
 // workgroup b: row[b][d] = rstd (gg_d - c1 - xhat_d c2) / (N - 1), gg = dfeat gamma, c1 = mean_d gg, c2 = mean_d gg xhat
 __global__ __launch_bounds__(kThreads) void pool_bwd_row_kernel(const float* __restrict__ dfeat, const float* __restrict__ pooled,
@@ -355,30 +264,7 @@ __global__ __launch_bounds__(64) void pool_bwd_pgrad_kernel(const float* __restr
   if (dbeta) dbeta[d] += sb;
 }
 
-// ------------------------------------------------------------------------------------------------ the plain Linear head
-// logits[b][c] = sum_d feat[b][d] W[c][d] + bias[c]; workgroup (class strip of 64, b), wave w owns 16 classes
-__global__ __launch_bounds__(kThreads) void linear_kernel(const float* __restrict__ feat, const float* __restrict__ W,
-                                                          const float* __restrict__ bias, int D, int C, float* __restrict__ logits) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int b = blockIdx.y;
-  const float* xr = feat + (long)b * D;
-  for (int i = 0; i < 16; ++i) {
-    const int c = blockIdx.x * 64 + wave * 16 + i;
-    if (c >= C) return;  // (wave-uniform; no barrier below)
-    const float* wr = W + (long)c * D;
-    float acc = 0.f;
-    for (int k = lane * 4; k < D; k += 64 * 4) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(xr + k), w = *reinterpret_cast<const f32x4*>(wr + k);
-      acc += a[0] * w[0];
-      acc += a[1] * w[1];
-      acc += a[2] * w[2];
-      acc += a[3] * w[3];
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) logits[(long)b * C + c] = acc + bias[c];
-  }
-}
-
+// ------------------------------------------------------------------------------------------------ the plain Linear head, backward
 // dfeat[b][d] = sum_c dlogits[b][c] W[c][d], c ascending.  Workgroup (64 vectors of 4 columns, kDfeatRows samples): one 16-byte load
 // of W per class serves kDfeatRows samples; the dlogits of a class are uniform over the workgroup.
 __global__ __launch_bounds__(64) void dfeat_kernel(const float* __restrict__ dlogits, const float* __restrict__ W, int B, int D, int C,
@@ -413,8 +299,6 @@ __global__ __launch_bounds__(64) void dfeat_kernel(const float* __restrict__ dlo
     if (b0 + r < B) *reinterpret_cast<f32x4*>(dfeat + (long)(b0 + r) * D + d) = acc[r];
   }
 }
-
-int pool_splits(int N) { return (N - 1 + kPoolRows - 1) / kPoolRows; }
 
 int pool_shape_ok(int B, int N, int D) {
   return !(B <= 0 || B > 65535 || N < 2 || D <= 0 || (D & 3) || D > kMaxD || (long)B * pool_splits(N) > (1L << 30) ||
@@ -478,15 +362,15 @@ extern "C" int pm_pool_norm_fwd_train(const float* x, int B, int N, int D, const
   if (!x || !gamma || !beta || !feat || !pooled || !mean || !rstd || !workspace) return PM_EINVAL;
   if (!pool_shape_ok(B, N, D)) return PM_ESHAPE;
   if (!(eps >= 0.f)) return PM_EINVAL;
-  const int S = pool_splits(N);
-  if (ws_bytes < (size_t)B * S * D * sizeof(float)) return PM_EINVAL;   // (= pm_pool_norm_workspace)
+  if (ws_bytes < pool_workspace_bytes(B, N, D)) return PM_EINVAL;   // (= pm_pool_norm_workspace)
   if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)feat | (uintptr_t)pooled | (uintptr_t)workspace) & 15)
     return PM_EALIGN;
   if (((uintptr_t)mean | (uintptr_t)rstd) & 3) return PM_EALIGN;
   hipStream_t q = pm_stream(stream);
-  hipLaunchKernelGGL(pool_partial_kernel, dim3(B * S), dim3(kThreads), 0, q, x, N, D, S, (float*)workspace);
-  hipLaunchKernelGGL(pool_norm_kernel, dim3(B), dim3(kThreads), 0, q, (const float*)workspace, N, D, S, gamma, beta, eps, feat, pooled,
-                     mean, rstd);
+  const int S = pool_splits(N);
+  hipLaunchKernelGGL(pool_partial_kernel, dim3(B * S), dim3(kPoolThreads), 0, q, x, N, D, S, (float*)workspace);
+  hipLaunchKernelGGL(pool_norm_kernel<true>, dim3(B), dim3(kPoolThreads), 0, q, (const float*)workspace, N, D, S, gamma, beta, eps, feat,
+                     pooled, mean, rstd);
   return pm_check_launch();
 }
 
@@ -534,7 +418,7 @@ extern "C" int pm_linear_head_fwd(const float* feat, int B, int D, int C, const 
   if (B <= 0 || B > 65535 || D <= 0 || (D & 3) || C <= 0 || C > 65535) return PM_ESHAPE;
   if (((uintptr_t)feat | (uintptr_t)W) & 15) return PM_EALIGN;
   if (((uintptr_t)bias | (uintptr_t)logits) & 3) return PM_EALIGN;
-  hipLaunchKernelGGL(linear_kernel, dim3((C + 63) / 64, B), dim3(kThreads), 0, pm_stream(stream), feat, W, bias, D, C, logits);
+  hipLaunchKernelGGL(linear_kernel, dim3((C + 63) / 64, B), dim3(kPoolThreads), 0, pm_stream(stream), feat, W, bias, D, C, logits);
   return pm_check_launch();
 }
 

@@ -41,12 +41,6 @@ struct GradBatch {
   int n_segs;
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // the workgroup's [sum, #NaN, #Inf] since the last flush, added to row[0..3) by lane 0; called under uniform control flow
 __device__ __forceinline__ void flush_group(double& ss, unsigned& nn, unsigned& ni, double* __restrict__ row, double (*red)[kWaves]) {
   const double a = wave_sum_f64(ss), b = wave_sum_f64((double)nn), c = wave_sum_f64((double)ni);

@@ -11,16 +11,6 @@ namespace {
 
 constexpr int kHeadVec = 4;  // f32x4 per lane -> D <= 1024
 
-// block-wide sum of one float per thread (256 threads), fixed order; every thread gets the result
-__device__ __forceinline__ float block_sum256(float v, float* s4) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) s4[wave] = v;
-  __syncthreads();
-  return (s4[0] + s4[1]) + (s4[2] + s4[3]);
-}
-
 // ---------------------------------------------------------------------------------------------
 // pool = cls: LayerNorm of row 0 + Linear(D -> n_class)  (W == NULL: features only, head=False)
 // ---------------------------------------------------------------------------------------------
@@ -236,7 +226,7 @@ __global__ __launch_bounds__(256) void spatial_head_fwd_kernel(const float* __re
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       if (k0 + k >= n_class) break;
-      const float t = block_sum256(part[k], s4);
+      const float t = block_sum(part[k], s4);
       if (tid == 0) logits[(long)b * n_class + k0 + k] = t + (bias ? bias[k0 + k] : 0.f);
     }
   }
@@ -260,7 +250,7 @@ __global__ __launch_bounds__(256) void spatial_head_bwd_kernel(const float* __re
     sgg[d] = gg;
     s1 += gg;
   }
-  const float c1 = block_sum256(s1, s4) / (float)D;  // (also publishes sgg)
+  const float c1 = block_sum(s1, s4) / (float)D;  // (also publishes sgg)
   const f32x4 z = {0.f, 0.f, 0.f, 0.f};
   if (wave == 0) {  // the cls row does not reach the pooled feature
 #pragma unroll
@@ -393,7 +383,7 @@ __global__ __launch_bounds__(256) void sup_loss_kernel(const float* __restrict__
       const float lw = 1.0f + (pw - 1.0f) * y;
       num += (1.0f - y) * z + lw * (log1pf(expf(-fabsf(z))) + fmaxf(-z, 0.f));
     }
-    const float tot = block_sum256(num, s4);
+    const float tot = block_sum(num, s4);
     const float invB = 1.0f / (float)B;
     if (tid == 0) loss[0] = tot * invB;
     for (int b = tid; b < B; b += 256) {
@@ -425,9 +415,9 @@ __global__ __launch_bounds__(256) void sup_loss_kernel(const float* __restrict__
     num += w * (m + logf(se) - l[y]);
     den += w;
   }
-  const float tn = block_sum256(num, s4);
-  const float td = block_sum256(den, s4);
-  const float poison = block_sum256(bad, s4) > 0.f ? __builtin_nanf("") : 0.f;
+  const float tn = block_sum(num, s4);
+  const float td = block_sum(den, s4);
+  const float poison = block_sum(bad, s4) > 0.f ? __builtin_nanf("") : 0.f;
   if (tid == 0) loss[0] = tn / td + poison;
   const float inv = 1.0f / td + poison;
   for (int b = tid; b < B; b += 256) {

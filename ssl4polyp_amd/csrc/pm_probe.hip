@@ -8,13 +8,11 @@
 // (no float atomics: two-stage sums with fixed trees), takes its stream, allocates nothing and checks its shapes on the host
 // before the first launch.
 //
-//   pool_partial_kernel / pool_norm_kernel   the one HBM-bound pass: x [B, N, D] is read once, kPoolRows patch rows per workgroup
-//                                            as 16-byte loads, four rows in flight; one workgroup per sample then adds the partial
-//                                            rows in ascending order, divides by N - 1 and applies LayerNorm.
+//   pool_partial_kernel / pool_norm_kernel<false>, linear_kernel     pm_pool_head.h, shared with pm_finetune.hip: the global_pool
+//                                            feature, and logits = xhat W^T + bias.
 //   bn_kernel                                64 feature columns x 16 row groups per workgroup: batch mean, biased variance (two
 //                                            passes: the deviations from the mean), xhat, the running statistics of
 //                                            torch.nn.BatchNorm1d (momentum, unbiased variance), the int64 counter.
-//   linear_kernel                            logits = xhat W^T + bias: one wave per (sample, class), 16 classes per wave.
 //   ce_rows_kernel / ce_finish_kernel        one wave per sample: log-sum-exp, the row's loss, dlogits x s / B, the number of
 //                                            classes strictly above the target's logit; then one workgroup adds up the rows.
 //   head_dw_kernel / head_dbias_kernel       dW += dlogits^T xhat, dbias += sum_b dlogits: 4 row groups per column, combined as
@@ -25,111 +23,15 @@
 //                                            device record, so a captured step replays with a new lr.
 #include <math.h>
 
-#include "pm_common.h"
+#include "pm_pool_head.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / PM_WAVE;
-constexpr int kMaxD = 2048;      // two 16-byte vectors per lane in pool_norm_kernel
-constexpr int kPoolRows = 32;    // patch rows per first-stage workgroup
 constexpr int kLarsRows = 32;    // partial rows per segment
 constexpr int kLarsBatch = 32;   // segments per launch (they travel as kernel arguments)
 constexpr int kLarsMaxBlocks = 256;
-
-// sum over the workgroup (4 waves): butterfly inside a wave, then (w0 + w1) + (w2 + w3); every thread gets the result
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();  // (red may still be read from the previous call)
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// ------------------------------------------------------------------------------------------------ pool + fc_norm
-// workgroup (b, s): partial[b][s][:] = sum of rows 1 + s kPoolRows ... of sample b, ascending
-__global__ __launch_bounds__(kThreads) void pool_partial_kernel(const float* __restrict__ x, int N, int D, int S,
-                                                                float* __restrict__ partial) {
-  const int b = blockIdx.x / S, s = blockIdx.x % S;
-  const int n0 = 1 + s * kPoolRows;
-  const int n1 = n0 + kPoolRows < N ? n0 + kPoolRows : N;
-  const float* base = x + (long)b * N * D;
-  float* out = partial + (long)blockIdx.x * D;
-  for (int c = threadIdx.x * 4; c < D; c += kThreads * 4) {
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    int n = n0;
-    for (; n + 3 < n1; n += 4) {
-      f32x4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const f32x4*>(base + (long)(n + u) * D + c);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc += v[u];
-    }
-    for (; n < n1; ++n) acc += *reinterpret_cast<const f32x4*>(base + (long)n * D + c);
-    *reinterpret_cast<f32x4*>(out + c) = acc;
-  }
-}
-
-// workgroup b: pooled = (partial rows in ascending order) / (N - 1), then LayerNorm over D
-__global__ __launch_bounds__(kThreads) void pool_norm_kernel(const float* __restrict__ partial, int N, int D, int S,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                             float* __restrict__ feat) {
-  __shared__ float red[kWaves];
-  const int b = blockIdx.x;
-  const float* rows = partial + (long)b * S * D;
-  const float den = (float)(N - 1);
-  f32x4 v[2];
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int c = (threadIdx.x + j * kThreads) * 4;
-    v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (c < D) {
-      for (int s = 0; s < S; ++s) v[j] += *reinterpret_cast<const f32x4*>(rows + (long)s * D + c);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[j][e] = v[j][e] / den;
-        sum += v[j][e];
-      }
-    }
-  }
-  const float mean = block_sum(sum, red) / (float)D;
-  float q = 0.f;
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int c = (threadIdx.x + j * kThreads) * 4;
-    if (c < D) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float d = v[j][e] - mean;
-        q += d * d;
-      }
-    }
-  }
-  const float rstd = rsqrtf(block_sum(q, red) / (float)D + eps);
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int c = (threadIdx.x + j * kThreads) * 4;
-    if (c < D) {
-      const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + c), bt = *reinterpret_cast<const f32x4*>(beta + c);
-      f32x4 y;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) y[e] = (v[j][e] - mean) * rstd * g[e] + bt[e];
-      *reinterpret_cast<f32x4*>(feat + (long)b * D + c) = y;
-    }
-  }
-}
 
 // ------------------------------------------------------------------------------------------------ BatchNorm1d(affine=False)
 // 64 columns x 16 row groups; row group g owns rows g, g + 16, ...; the groups are combined in the order 0..15
@@ -184,29 +86,6 @@ __global__ __launch_bounds__(1024) void bn_kernel(const float* __restrict__ feat
     for (int b = rg; b < B; b += 16) xhat[(long)b * D + d] = (feat[(long)b * D + d] - mean) * rstd;
   }
   if (training && blockIdx.x == 0 && threadIdx.x == 0) *tracked += 1;
-}
-
-// logits[b][c] = sum_d xhat[b][d] W[c][d] + bias[c]; workgroup (class strip of 64, b), wave w owns 16 classes
-__global__ __launch_bounds__(kThreads) void linear_kernel(const float* __restrict__ xhat, const float* __restrict__ W,
-                                                          const float* __restrict__ bias, int D, int C, float* __restrict__ logits) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int b = blockIdx.y;
-  const float* xr = xhat + (long)b * D;
-  for (int i = 0; i < 16; ++i) {
-    const int c = blockIdx.x * 64 + wave * 16 + i;
-    if (c >= C) return;  // (wave-uniform; no barrier below)
-    const float* wr = W + (long)c * D;
-    float acc = 0.f;
-    for (int k = lane * 4; k < D; k += 64 * 4) {
-      const f32x4 a = *reinterpret_cast<const f32x4*>(xr + k), w = *reinterpret_cast<const f32x4*>(wr + k);
-      acc += a[0] * w[0];
-      acc += a[1] * w[1];
-      acc += a[2] * w[2];
-      acc += a[3] * w[3];
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) logits[(long)b * C + c] = acc + bias[c];
-  }
 }
 
 // ------------------------------------------------------------------------------------------------ cross-entropy + accuracy
@@ -369,14 +248,12 @@ __global__ __launch_bounds__(kThreads) void lars_update_kernel(const LarsBatch b
   }
 }
 
-int pool_splits(int N) { return (N - 1 + kPoolRows - 1) / kPoolRows; }
-
 }  // namespace
 
 extern "C" int pm_pool_norm_workspace(int B, int N, int D, size_t* bytes) {
   if (!bytes) return PM_EINVAL;
   if (B <= 0 || N < 2 || D <= 0 || (D & 3) || D > kMaxD || (long)B * pool_splits(N) > (1L << 30)) return PM_ESHAPE;
-  *bytes = (size_t)B * pool_splits(N) * D * sizeof(float);
+  *bytes = pool_workspace_bytes(B, N, D);
   return PM_OK;
 }
 
@@ -391,8 +268,9 @@ extern "C" int pm_pool_norm_fwd(const float* x, int B, int N, int D, const float
   if (((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)feat | (uintptr_t)workspace) & 15) return PM_EALIGN;
   hipStream_t q = pm_stream(stream);
   const int S = pool_splits(N);
-  hipLaunchKernelGGL(pool_partial_kernel, dim3(B * S), dim3(kThreads), 0, q, x, N, D, S, (float*)workspace);
-  hipLaunchKernelGGL(pool_norm_kernel, dim3(B), dim3(kThreads), 0, q, (const float*)workspace, N, D, S, gamma, beta, eps, feat);
+  hipLaunchKernelGGL(pool_partial_kernel, dim3(B * S), dim3(kPoolThreads), 0, q, x, N, D, S, (float*)workspace);
+  hipLaunchKernelGGL(pool_norm_kernel<false>, dim3(B), dim3(kPoolThreads), 0, q, (const float*)workspace, N, D, S, gamma, beta, eps, feat,
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr);
   return pm_check_launch();
 }
 
@@ -410,7 +288,7 @@ extern "C" int pm_probe_head_fwd(const float* feat, int B, int D, int C, const f
   hipStream_t q = pm_stream(stream);
   hipLaunchKernelGGL(bn_kernel, dim3((D + 63) / 64), dim3(1024), 0, q, feat, B, D, running_mean, running_var, num_batches_tracked,
                      training ? 1 : 0, momentum, eps, xhat);
-  hipLaunchKernelGGL(linear_kernel, dim3((C + 63) / 64, B), dim3(kThreads), 0, q, (const float*)xhat, W, bias, D, C, logits);
+  hipLaunchKernelGGL(linear_kernel, dim3((C + 63) / 64, B), dim3(kPoolThreads), 0, q, (const float*)xhat, W, bias, D, C, logits);
   return pm_check_launch();
 }
 

@@ -15,7 +15,6 @@ frame where it lies (`pm_aug_resized_crop_ragged_u8`); the folder dataset and it
 from __future__ import annotations
 
 import concurrent.futures
-import ctypes
 import math
 from typing import Iterable, Iterator, Optional, Sequence, Tuple
 
@@ -745,10 +744,8 @@ class DeviceJpegDecoder:
     def _parallel_ws(self, batch) -> tuple:
         """What the parallel entries take last: subseq with its count, sync_rounds, the grow-only workspace with its size, `stats`."""
         t = batch.t
-        need = ctypes.c_size_t(0)
-        _lib.check(_lib.load().pm_jpeg_decode_workspace(t["intervals"].shape[0], t["subseq"].numel(), ctypes.byref(need)),
-                   "pm_jpeg_decode_workspace")
-        ws = self._scratch.grow("workspace", need.value, torch.uint8)
+        need = _lib.workspace_bytes("pm_jpeg_decode_workspace", t["intervals"].shape[0], t["subseq"].numel())
+        ws = self._scratch.grow("workspace", need, torch.uint8)
         stats = self._scratch.grow("stats", 8, torch.int32)
         return self._ptr(t["subseq"]), t["subseq"].numel(), self.sync_rounds, ws.data_ptr(), ws.numel(), stats.data_ptr()
 
@@ -782,9 +779,7 @@ class DeviceJpegDecoder:
         _lib.check(lib.pm_jpeg_decode_planes(*lead, coef.data_ptr(), planes.data_ptr(), m["blocks"], *self._parallel_ws(batch), stream),
                    "pm_jpeg_decode_planes")
         Hmax, Wmax = (int(v) for v in hw.max(0))
-        need = ctypes.c_size_t(0)
-        _lib.check(lib.pm_jpeg_resized_crop_workspace(B, Hmax, Wmax, S, ctypes.byref(need)), "pm_jpeg_resized_crop_workspace")
-        cws = sc.grow("crop_ws", need.value, torch.uint8)
+        cws = sc.grow("crop_ws", _lib.workspace_bytes("pm_jpeg_resized_crop_workspace", B, Hmax, Wmax, S), torch.uint8)
         _lib.check(lib.pm_jpeg_resized_crop_u8(planes.data_ptr(), m["blocks"], ptr(t["frames"]), t["frames"].shape[0], ptr(t["fallback"]),
                                                t["fallback"].numel(), ptr(t["fallback_table"]), t["fallback_table"].shape[0],
                                                src_d.data_ptr(), t["hw"].data_ptr(), box_d.data_ptr(), out.data_ptr(),

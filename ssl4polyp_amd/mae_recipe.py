@@ -1,0 +1,167 @@
+"""What the two MAE image-folder recipes share (main_linprobe: linear probing; main_finetune_mae: end-to-end fine-tuning): the common
+flags, the lr resolution, the input pipeline of mae/main_linprobe.py:144-156 and the epoch loop around the recipe's own train call.
+
+Training frames: folder.folder_loader on DATA/train, the workers only decode; on the device the crop of mae/util/crop.py
+(data.draw_linprobe_boxes -- not torchvision's sampler) through DeviceAugmenter.random_resized_crop(bicubic), then flip / ToTensor /
+Normalize (mae_tail).  Validation frames: the workers do Resize(256, bicubic) + CenterCrop(224) with Pillow, as the reference's workers
+do, and the device normalises (preprocess_u8).  The crops, flips and the sampler's order of epoch e depend on (seed, e) alone, so a
+resumed run continues as the uninterrupted one."""
+from __future__ import annotations
+
+import json
+import os
+
+import numpy as np
+import torch
+
+from .train import evaluate_probe, load_mae_checkpoint, save_mae_checkpoint
+
+
+def add_common_flags(p, precision_help: str):
+    """The flags both parsers define.  The nine whose defaults differ between the recipes (batch_size, epochs, model, weight_decay,
+    blr, min_lr, warmup_epochs, global_pool, output_dir) get theirs from the caller's set_defaults."""
+    p.add_argument("--batch_size", type=int, help="batch size per GPU")
+    p.add_argument("--epochs", type=int)
+    p.add_argument("--accum_iter", default=1, type=int)
+    p.add_argument("--model", type=str)
+    p.add_argument("--weight_decay", type=float)
+    p.add_argument("--lr", type=float, default=None)
+    p.add_argument("--blr", type=float)
+    p.add_argument("--min_lr", type=float)
+    p.add_argument("--warmup_epochs", type=int)
+    p.add_argument("--finetune", default="", help="pre-training checkpoint to start from")
+    p.add_argument("--global_pool", action="store_true")
+    p.add_argument("--cls_token", action="store_false", dest="global_pool")
+    p.add_argument("--data_path", default="/datasets01/imagenet_full_size/061417/", type=str)
+    p.add_argument("--nb_classes", default=1000, type=int)
+    p.add_argument("--output_dir")
+    p.add_argument("--seed", default=0, type=int)
+    p.add_argument("--resume", default="")
+    p.add_argument("--start_epoch", default=0, type=int)
+    p.add_argument("--eval", action="store_true")
+    p.add_argument("--dist_eval", action="store_true", default=False)
+    p.add_argument("--num_workers", default=10, type=int)
+    p.add_argument("--pin_mem", action="store_true")
+    p.add_argument("--no_pin_mem", action="store_false", dest="pin_mem")
+    p.set_defaults(pin_mem=True)
+    p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"], help=precision_help)
+    return p
+
+
+class _ValFrames(torch.utils.data.Dataset):
+    """main_linprobe.py:151-156 in the workers: Resize(256, interpolation=3) + CenterCrop(224) with Pillow -> uint8 [224, 224, 3]."""
+
+    def __init__(self, root: str, resize: int = 256, crop: int = 224):
+        from .folder import find_classes, make_dataset
+        self.classes, self.class_to_idx = find_classes(root)
+        self.samples = make_dataset(root, self.class_to_idx)
+        self.resize, self.crop = resize, crop
+
+    def __len__(self):
+        return len(self.samples)
+
+    def __getitem__(self, i):
+        from PIL import Image
+        path, target = self.samples[i]
+        with open(path, "rb") as f:
+            img = Image.open(f).convert("RGB")
+        w, h = img.size
+        if (w <= h and w != self.resize) or (h <= w and h != self.resize):   # torchvision Resize(int): the shorter side
+            nw, nh = (self.resize, int(self.resize * h / w)) if w <= h else (int(self.resize * w / h), self.resize)
+            img = img.resize((nw, nh), Image.BICUBIC)
+            w, h = nw, nh
+        top, left = int(round((h - self.crop) / 2.0)), int(round((w - self.crop) / 2.0))   # torchvision center_crop
+        return np.asarray(img.crop((left, top, left + self.crop, top + self.crop))), target
+
+
+def _val_collate(items):
+    frames, labels = zip(*items)
+    return torch.from_numpy(np.stack(frames)), torch.tensor(labels, dtype=torch.int64)
+
+
+def start(args) -> torch.device:
+    """The process's device, made current, and the host seeds."""
+    device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    torch.cuda.set_device(device)
+    torch.manual_seed(args.seed)
+    np.random.seed(args.seed)
+    return device
+
+
+def resolve_lr(args) -> None:
+    """lr = blr * batch_size * accum_iter / 256 unless --lr was given, and the reference's print-out."""
+    eff = args.batch_size * args.accum_iter
+    if args.lr is None:
+        args.lr = args.blr * eff / 256
+    print(f"base lr: {args.lr * 256 / eff:.2e}\nactual lr: {args.lr:.2e}\naccumulate grad iterations: {args.accum_iter}\n"
+          f"effective batch size: {eff}")
+
+
+def run_epochs(args, model, opt, device, train_epoch, *, crop_size: int, train_loader, val_loader, prepare_given: bool, scaler=None,
+               log_extra=None, log_encoding=None):
+    """Resume, build the loaders the caller did not pass, then --eval or the epoch loop -> (model, opt, history): history holds one
+    {"epoch", "train", "test"} record per epoch run (--eval: one "test").
+
+    train_epoch(epoch, train_loader, prepare_train) -> the epoch's train statistics: the recipe's own call.
+    prepare_given: whether prepare_train / prepare_val (host batch -> device batch) are applied to loaders the CALLER passed as well
+      (the probe), or only to the folder loaders built here, a passed loader yielding device batches as they are (the fine-tune).
+    scaler: the fp16 loss scaler restored from / saved into the checkpoints.  log_extra: further keys of the log.txt line;
+    log_encoding: the encoding log.txt is opened with."""
+    from .data import DeviceAugmenter, draw_linprobe_boxes, preprocess_u8
+    from .folder import folder_loader
+    if args.resume:
+        args.start_epoch = load_mae_checkpoint(args.resume, model, opt, args, loss_scaler=scaler)
+    aug = DeviceAugmenter(device, size=crop_size)
+    gen = torch.Generator()
+    sampler = None
+
+    def prepare_train(batch):
+        frames, labels = batch
+        frames = frames.to(device, non_blocking=True)
+        hw = frames.sizes
+        boxes = draw_linprobe_boxes(len(frames), hw[:, 0], hw[:, 1], gen)
+        return aug.mae_tail(aug.random_resized_crop(frames, boxes=boxes), generator=gen), labels.to(device, non_blocking=True)
+
+    def prepare_val(batch):
+        frames, labels = batch
+        return preprocess_u8(frames.to(device, non_blocking=True)), labels.to(device, non_blocking=True)
+
+    if val_loader is None:
+        extra = {"multiprocessing_context": "spawn", "persistent_workers": True} if args.num_workers > 0 else {}
+        val_loader = torch.utils.data.DataLoader(_ValFrames(os.path.join(args.data_path, "val")), batch_size=args.batch_size,
+                                                 shuffle=False, num_workers=args.num_workers, pin_memory=args.pin_mem,
+                                                 drop_last=False, collate_fn=_val_collate, **extra)
+    elif not prepare_given:
+        prepare_val = None
+    if train_loader is None and not args.eval:
+        train_loader = folder_loader(os.path.join(args.data_path, "train"), args.batch_size, 1, 0, args.seed, args.num_workers,
+                                     args.pin_mem)
+        sampler = train_loader.sampler
+    elif not prepare_given:
+        prepare_train = None
+
+    if args.eval:
+        test = evaluate_probe(model, val_loader, device, prepare_val)
+        print(f"Accuracy of the network on the {test['samples']} test images: {test['acc1']:.1f}%")
+        return model, opt, [{"test": test}]
+    history = []
+    ckpt_dir = os.path.join(args.output_dir, "ckpts") if args.output_dir else None
+    max_accuracy = 0.0
+    for epoch in range(args.start_epoch, args.epochs):
+        gen.manual_seed(args.seed + epoch)
+        if sampler is not None:
+            sampler.set_epoch(args.seed + epoch)
+        train = train_epoch(epoch, train_loader, prepare_train)
+        if ckpt_dir:
+            save_mae_checkpoint(ckpt_dir, epoch, model, opt, args, scaler_state=scaler.state_dict() if scaler is not None else None)
+        test = evaluate_probe(model, val_loader, device, prepare_val)
+        print(f"Accuracy of the network on the {test['samples']} test images: {test['acc1']:.1f}%")
+        max_accuracy = max(max_accuracy, test["acc1"])
+        print(f"Max accuracy: {max_accuracy:.2f}%")
+        history.append({"epoch": epoch, "train": train, "test": test})
+        if args.output_dir:
+            os.makedirs(args.output_dir, exist_ok=True)
+            with open(os.path.join(args.output_dir, "log.txt"), mode="a", encoding=log_encoding) as f:
+                f.write(json.dumps({**{f"train_{k}": v for k, v in train.items()}, **{f"test_{k}": v for k, v in test.items()},
+                                    "epoch": epoch, **(log_extra or {})}) + "\n")
+    return model, opt, history

@@ -19,8 +19,6 @@ grid (f1_morph_threshold, curve_rows / export_curves) are integer-exact torch pl
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
@@ -81,12 +79,6 @@ def draw_cluster_samples(cluster_sets, rng: np.random.Generator, R: int):
     return out[0] if single else out
 
 
-def _workspace_bytes(N, M, R, K, C) -> int:
-    need = ctypes.c_size_t(0)
-    _lib.check(_lib.load().pm_boot_metrics_workspace(N, M, R, K, C, ctypes.byref(need)), "pm_boot_metrics_workspace")
-    return need.value
-
-
 def bootstrap_binary_metrics(probs, labels, tau, cluster, draws, n_clusters=None, chunk=CHUNK, device=None) -> torch.Tensor:
     """The 16 values of compute_binary_metrics (METRIC_KEYS order) for every replicate and run: f64 [R, M, 16] on the device.
 
@@ -114,7 +106,7 @@ def bootstrap_binary_metrics(probs, labels, tau, cluster, draws, n_clusters=None
         raise ValueError(f"tau: one value or one per run ({M}), got {tuple(tau_d.shape)}")
     order = torch.sort(score, dim=1, descending=True, stable=True).indices.to(torch.int32).contiguous()
     chunk = max(1, min(int(chunk), MAX_REPLICATES_PER_CALL, max(R, 1)))
-    ws = torch.empty(_workspace_bytes(N, M, chunk, K, C), dtype=torch.uint8, device=device)
+    ws = torch.empty(_lib.workspace_bytes("pm_boot_metrics_workspace", N, M, chunk, K, C), dtype=torch.uint8, device=device)
     out = torch.empty((R, M, len(METRIC_KEYS)), dtype=torch.float64, device=device)
     lib = _lib.load()
     stream = torch.cuda.current_stream(device).cuda_stream
@@ -178,9 +170,7 @@ def select_threshold(probs, labels, policy, previous_tau=None, return_candidates
         raise ValueError(f"previous_tau: one value or one per run ({M}), got {tuple(prev.shape)}")
     order = torch.sort(score, dim=1, descending=True, stable=True).indices.to(torch.int32).contiguous()
     lib = _lib.load()
-    need = ctypes.c_size_t(0)
-    _lib.check(lib.pm_select_tau_workspace(N, M, ctypes.byref(need)), "pm_select_tau_workspace")
-    ws = torch.empty(need.value, dtype=torch.uint8, device=device)
+    ws = torch.empty(_lib.workspace_bytes("pm_select_tau_workspace", N, M), dtype=torch.uint8, device=device)
     out = torch.empty((M, len(TAU_KEYS)), dtype=torch.float64, device=device)
     cand = torch.empty((M, MAX_CANDIDATES), dtype=torch.float64, device=device) if return_candidates else None
     _lib.check(lib.pm_select_tau(score.data_ptr(), order.data_ptr(), label.data_ptr(), prev.data_ptr(), POLICIES[name], out.data_ptr(),
@@ -464,9 +454,7 @@ def bootstrap_group_metrics(probs, labels, tau, groups: GroupSet, cluster, draws
     seg = torch.from_numpy(groups.seg).to(device)
     lib = _lib.load()
     chunk = max(1, min(int(chunk), MAX_REPLICATES_PER_CALL, R))
-    need = ctypes.c_size_t(0)
-    _lib.check(lib.pm_group_metrics_workspace(N, M, E, G, chunk, K, C, ctypes.byref(need)), "pm_group_metrics_workspace")
-    ws = torch.empty(need.value, dtype=torch.uint8, device=device)
+    ws = torch.empty(_lib.workspace_bytes("pm_group_metrics_workspace", N, M, E, G, chunk, K, C), dtype=torch.uint8, device=device)
     stream = torch.cuda.current_stream(device).cuda_stream
     for r0 in range(0, R, chunk):
         n = min(chunk, R - r0)

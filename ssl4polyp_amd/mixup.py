@@ -11,7 +11,6 @@ rand_bbox, cutmix_bbox_and_lam with correct_lam) is RESTATED from timm 0.4.12's 
 (no run of timm was recorded); tests/test_finetune_mae_cpu.py pins it to a hand-computed sequence from a seeded RandomState."""
 from __future__ import annotations
 
-import ctypes
 import struct
 from typing import Optional, Tuple
 
@@ -178,10 +177,8 @@ def soft_ce_raw(logits, target, record: Optional[torch.Tensor], smoothing: float
         raise _lib.PolypMaeError(f"soft_target_ce: targets must be int64 [{B}] (got {target.dtype} {tuple(target.shape)})")
     target = target.contiguous()
     lib = _lib.load()
-    size = ctypes.c_size_t(0)
-    _lib.check(lib.pm_soft_ce_workspace(B, ctypes.byref(size)), "pm_soft_ce_workspace")
     dev = logits.device
-    ws = torch.empty((size.value + 3) // 4, dtype=torch.float32, device=dev)
+    ws = torch.empty((_lib.workspace_bytes("pm_soft_ce_workspace", B) + 3) // 4, dtype=torch.float32, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     dlogits = torch.empty(B, C, dtype=torch.float32, device=dev) if want_grad else None
     _lib.check(lib.pm_soft_ce(_ptr(logits), _ptr(target), B, C, _ptr(record), float(smoothing), _ptr(scale), _ptr(loss), _ptr(dlogits),

@@ -11,7 +11,6 @@ frozen in this protocol, so the feature pass records nothing for a backward; the
 encoder's precision mode."""
 from __future__ import annotations
 
-import ctypes
 from functools import partial
 from typing import Optional
 
@@ -109,12 +108,6 @@ class VisionTransformer(_ClassifierBase):
         return torch.ops.polypmae.vit_finetune_forward(imgs, ops.register_runtime(rt), list(rt.flat.params))
 
 
-def _workspace(query, what: str, *dims) -> torch.Tensor:
-    size = ctypes.c_size_t(0)
-    _lib.check(query(*dims, ctypes.byref(size)), what)
-    return size.value
-
-
 class _VitFinetuneFn(torch.autograd.Function):
     """imgs -> logits of models_vit.VisionTransformer with its plain Linear head (models_vit.py:34-53), one node, modelled on
     models._VitClsFn.  global_pool: the dense block stack, then pm_pool_norm_fwd_train / pm_pool_norm_bwd (fc_norm of the mean of the
@@ -151,7 +144,7 @@ class _VitFinetuneFn(torch.autograd.Function):
         gamma, beta = f.param_view(norm + ".weight"), f.param_view(norm + ".bias")
         if pool:
             pooled = torch.empty(B, D, dtype=f32, device=dev)
-            nbytes = _workspace(lib.pm_pool_norm_workspace, "pm_pool_norm_workspace", B, N, D)
+            nbytes = _lib.workspace_bytes("pm_pool_norm_workspace", B, N, D)
             scratch = torch.empty((nbytes + 3) // 4, dtype=f32, device=dev)
             _lib.check(lib.pm_pool_norm_fwd_train(_ptr(x), B, N, D, _ptr(gamma), _ptr(beta), rt.eps, _ptr(feat), _ptr(pooled), _ptr(mean),
                                                   _ptr(rstd), _ptr(scratch), scratch.numel() * 4, _stream()), "pm_pool_norm_fwd_train")
@@ -212,7 +205,7 @@ class _VitFinetuneFn(torch.autograd.Function):
                 dx_act = ws.dx_act[0] if below_head else None
             gamma = f.param_view(norm + ".weight")
             if pool:
-                nbytes = _workspace(lib.pm_pool_norm_bwd_workspace, "pm_pool_norm_bwd_workspace", B, N, D)
+                nbytes = _lib.workspace_bytes("pm_pool_norm_bwd_workspace", B, N, D)
                 scratch = torch.empty((nbytes + 3) // 4, dtype=f32, device=dev)
                 _lib.check(lib.pm_pool_norm_bwd(_ptr(dfeat), _ptr(pooled), _ptr(mean), _ptr(rstd), _ptr(gamma), B, N, D, _ptr(dx),
                                                 _ptr(dx_act), k.act, _ptr(dgamma), _ptr(dbeta), _ptr(scratch), scratch.numel() * 4,
@@ -276,10 +269,10 @@ def interpolate_pos_embed(model: VisionTransformer, checkpoint_model: dict) -> N
                                  "position-embedding interpolation for another input size is not supported")
 
 
-def load_pretrained_for_probe(model: VisionTransformer, checkpoint_model: dict):
-    """main_linprobe.py:216-240 on the `["model"]` dict of a main_pretrain checkpoint, BEFORE add_probe_head: head keys of another
-    shape are dropped, the rest loads non-strictly (the MAE's decoder and mask token are unexpected keys), the missing keys must be
-    exactly the head (and fc_norm with global_pool), head.weight gets trunc-normal std 0.01.  Returns load_state_dict's result."""
+def _load_pretrained(model: VisionTransformer, checkpoint_model: dict, head_std: float):
+    """The `["model"]` dict of a main_pretrain checkpoint into `model`: head keys of another shape are dropped, the rest loads
+    non-strictly (the MAE's decoder and mask token are unexpected keys), the missing keys must be exactly the head (and fc_norm with
+    global_pool), head.weight gets trunc-normal std `head_std`.  Returns load_state_dict's result."""
     checkpoint_model = dict(checkpoint_model)
     own = model.state_dict()
     for k in ("head.weight", "head.bias"):
@@ -290,26 +283,15 @@ def load_pretrained_for_probe(model: VisionTransformer, checkpoint_model: dict):
     msg = model.load_state_dict(checkpoint_model, strict=False)
     want = {"head.weight", "head.bias"} | ({"fc_norm.weight", "fc_norm.bias"} if model.global_pool else set())
     assert set(msg.missing_keys) == want, f"missing keys {sorted(msg.missing_keys)}; expected {sorted(want)}"
-    nn.init.trunc_normal_(model.head.weight, std=0.01)   # following MoCo v3
+    nn.init.trunc_normal_(model.head.weight, std=head_std)
     return msg
+
+
+def load_pretrained_for_probe(model: VisionTransformer, checkpoint_model: dict):
+    """main_linprobe.py:216-240, BEFORE add_probe_head: _load_pretrained with the head at std 0.01 (following MoCo v3)."""
+    return _load_pretrained(model, checkpoint_model, 0.01)
 
 
 def load_pretrained_for_finetune(model: VisionTransformer, checkpoint_model: dict):
-    """main_finetune.py:255-279 on the `["model"]` dict of a main_pretrain checkpoint: the key handling of load_pretrained_for_probe
-    (head keys of another shape dropped, non-strict load, the missing keys must be exactly the head -- and fc_norm with global_pool),
-    then head.weight gets trunc-normal std 2e-5.  Returns load_state_dict's result."""
-    checkpoint_model = dict(checkpoint_model)
-    own = model.state_dict()
-    for k in ("head.weight", "head.bias"):
-        if k in checkpoint_model and checkpoint_model[k].shape != own[k].shape:
-            print(f"Removing key {k} from pretrained checkpoint")
-            del checkpoint_model[k]
-    interpolate_pos_embed(model, checkpoint_model)
-    msg = model.load_state_dict(checkpoint_model, strict=False)
-    if model.global_pool:
-        assert set(msg.missing_keys) == {"head.weight", "head.bias", "fc_norm.weight", "fc_norm.bias"}, \
-            f"missing keys {sorted(msg.missing_keys)}"
-    else:
-        assert set(msg.missing_keys) == {"head.weight", "head.bias"}, f"missing keys {sorted(msg.missing_keys)}"
-    nn.init.trunc_normal_(model.head.weight, std=2e-5)   # manually initialize fc layer
-    return msg
+    """main_finetune.py:255-279: _load_pretrained with the head at std 2e-5 ("manually initialize fc layer")."""
+    return _load_pretrained(model, checkpoint_model, 2e-5)

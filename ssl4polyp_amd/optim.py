@@ -174,11 +174,10 @@ class FusedAdamW(torch.optim.Optimizer):
         """Workspace, f64 sums, f32 triple and f64 record of the norm kernels: allocated once (outside capture: a GraphedStep runs
         its eager warm-up steps first), at fixed addresses, so that a captured step replays them."""
         G, R = len(self.param_groups), self._n_records()  # (R == G unless per_parameter_steps: one sum per record)
-        size = ctypes.c_size_t(0)
-        _lib.check(self._rt.k.lib.pm_grad_norms_workspace(n_segs, R, ctypes.byref(size)), "pm_grad_norms_workspace")
+        size = _lib.workspace_bytes("pm_grad_norms_workspace", n_segs, R)
         b = getattr(self, "_clip_buf", None)
-        if b is None or b["ws"].device != f.device or b["ws"].numel() * 8 < size.value or b["sumsq"].numel() != R:
-            b = self._clip_buf = {"ws": torch.zeros((size.value + 7) // 8, dtype=torch.float64, device=f.device),
+        if b is None or b["ws"].device != f.device or b["ws"].numel() * 8 < size or b["sumsq"].numel() != R:
+            b = self._clip_buf = {"ws": torch.zeros((size + 7) // 8, dtype=torch.float64, device=f.device),
                                   "sumsq": torch.zeros(R, dtype=torch.float64, device=f.device),
                                   "stats": torch.zeros(3, dtype=torch.float32, device=f.device),
                                   "record": torch.zeros(G + 3, dtype=torch.float64, device=f.device),
@@ -734,10 +733,8 @@ class FusedLARS(torch.optim.Optimizer):
             arr = (_lib.LarsSegment * max(len(key), 1))()
             for i, (pp, gp, mp, n, mat) in enumerate(key):
                 arr[i] = _lib.LarsSegment(pp, gp, mp, n, 1 if mat else 0)
-            size = ctypes.c_size_t(0)
-            if key:
-                _lib.check(_lib.load().pm_lars_workspace(len(key), ctypes.byref(size)), "pm_lars_workspace")
-            ws = torch.empty(max(size.value // 8, 1), dtype=torch.float64, device=live[0].device) if key else None
+            ws = (torch.empty(max(_lib.workspace_bytes("pm_lars_workspace", len(key)) // 8, 1), dtype=torch.float64, device=live[0].device)
+                  if key else None)
             cached = self._tables[gi] = (key, arr, ws)
         return cached
 

@@ -5,7 +5,6 @@ csrc/pm_probe.hip (f32, fixed summation order); a missing kernel is an error, th
 The head, its loss and LARS (optim.FusedLARS) run in f32 in every precision mode; only the encoder follows the configured mode."""
 from __future__ import annotations
 
-import ctypes
 from typing import Optional
 
 import torch
@@ -30,9 +29,7 @@ def pool_norm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
     x, gamma, beta = _f32(x.detach(), "pool_norm x"), _f32(gamma.detach(), "pool_norm weight"), _f32(beta.detach(), "pool_norm bias")
     B, N, D = x.shape
     lib = _lib.load()
-    size = ctypes.c_size_t(0)
-    _lib.check(lib.pm_pool_norm_workspace(B, N, D, ctypes.byref(size)), "pm_pool_norm_workspace")
-    ws = torch.empty((size.value + 3) // 4, dtype=torch.float32, device=x.device)
+    ws = torch.empty((_lib.workspace_bytes("pm_pool_norm_workspace", B, N, D) + 3) // 4, dtype=torch.float32, device=x.device)
     feat = torch.empty(B, D, dtype=torch.float32, device=x.device)
     _lib.check(lib.pm_pool_norm_fwd(_ptr(x), B, N, D, _ptr(gamma), _ptr(beta), float(eps), _ptr(feat), _ptr(ws), ws.numel() * 4,
                                     _stream()), "pm_pool_norm_fwd")
@@ -72,10 +69,8 @@ def probe_ce_raw(logits, target, scale: Optional[torch.Tensor], want_grad: bool)
         raise _lib.PolypMaeError(f"probe_ce: targets must be int64 [{B}] (got {target.dtype} {tuple(target.shape)})")
     target = target.contiguous()
     lib = _lib.load()
-    size = ctypes.c_size_t(0)
-    _lib.check(lib.pm_probe_ce_workspace(B, ctypes.byref(size)), "pm_probe_ce_workspace")
     dev = logits.device
-    ws = torch.empty((size.value + 3) // 4, dtype=torch.float32, device=dev)
+    ws = torch.empty((_lib.workspace_bytes("pm_probe_ce_workspace", B) + 3) // 4, dtype=torch.float32, device=dev)
     loss = torch.empty(1, dtype=torch.float32, device=dev)
     correct = torch.empty(2, dtype=torch.int64, device=dev)
     dlogits = torch.empty(B, C, dtype=torch.float32, device=dev) if want_grad else None

@@ -430,6 +430,29 @@ def test_linear_head(case):
             what)
 
 
+@pytest.mark.parametrize("case", [(2, 64, 1), (3, 768, 7), (2, 64, 81)])
+def test_linear_head_has_the_bits_of_the_probe_head(case):
+    """pm_probe_head_fwd and pm_linear_head_fwd launch one linear_kernel (csrc/pm_pool_head.h): on the xhat the probe's BatchNorm
+    left, the plain head gives the probe's logits bit for bit.  One class and one k-step; three k-steps and a partial 16-class group;
+    a second 64-class strip whose second wave is partial."""
+    B, D, C = case
+    g = _gen(B * 11 + D + C)
+    feat = (torch.randn(B, D, generator=g) * 1.5 + 0.3).to(DEV)
+    W = (torch.randn(C, D, generator=g) * (1.0 / D ** 0.5)).to(DEV)
+    bias = (torch.randn(C, generator=g) * 0.1).to(DEV)
+    rm, rv = torch.zeros(D, device=DEV), torch.ones(D, device=DEV)
+    nbt = torch.zeros((), dtype=torch.int64, device=DEV)
+    bufs = {"xhat": _guarded((B, D)), "probe logits": _guarded((B, C)), "linear logits": _guarded((B, C))}
+    o = {n: v for n, (_, v) in bufs.items()}
+    assert abi("pm_probe_head_fwd", feat, B, D, C, W, bias, rm, rv, nbt, 1, 0.1, 1e-6, o["xhat"], o["probe logits"]) == 0
+    assert abi("pm_linear_head_fwd", o["xhat"], B, D, C, W, bias, o["linear logits"]) == 0
+    torch.cuda.synchronize()
+    for n, (buf, _) in bufs.items():
+        _guards_hold(buf, f"shared linear kernel {case} {n}")
+    assert not bool(torch.isnan(o["probe logits"]).any())
+    assert torch.equal(o["probe logits"].view(torch.int32), o["linear logits"].view(torch.int32))
+
+
 def test_linear_head_refusals():
     from ssl4polyp_amd import _lib
     feat, W, bias = torch.randn(2, 64, device=DEV), torch.randn(3, 64, device=DEV), torch.randn(3, device=DEV)
