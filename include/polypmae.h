@@ -303,6 +303,25 @@ int pm_aug_resized_crop_u8(const unsigned char* src, const int* box, unsigned ch
 int pm_aug_resized_crop_ragged_u8(const unsigned char* src, const long long* offset, const int* hw, const int* box, unsigned char* dst,
                                   int bicubic, int B, int Hmax, int Wmax, int out, void* workspace, size_t ws_bytes, void* stream);
 
+/* The validation transform of the MAE recipes (mae/main_linprobe.py:151-156: Resize(resize, bicubic) + CenterCrop(crop)) over the
+ * packed ragged batch of pm_aug_resized_crop_ragged_u8 (src, offset i64 [B], hw i32 [B][2]): dst u8 [B][crop][crop][3] equals
+ * Image.resize((nw, nh), BICUBIC).crop((left, top, left + crop, top + crop)) byte for byte, and the resized nw x nh frame is never
+ * written.  win i32 [B][4] = (nh, nw, top, left): the full resized size and the window's origin in it, computed by the caller as
+ * torchvision does (the shorter side becomes `resize`, the other int(resize * other / shorter); nh = H_b, nw = W_b when the shorter
+ * side already equals `resize`; top = round((nh - crop) / 2.0), half to even, likewise left).  The taps are built on the device in
+ * Resample.c's double arithmetic for the full resized size, for the window's crop columns and rows only (one launch); the
+ * horizontal pass runs over the source rows the window's vertical taps read, into a u8 temporary, then the vertical pass.
+ *   workspace: 16-byte aligned (PM_EALIGN otherwise), at least pm_aug_resize_center_crop_workspace(B, Hmax, Wmax, resize, crop,
+ *   &bytes) bytes (PM_EINVAL otherwise, as for a NULL pointer); it is sized for resized sides >= resize, which the rule above gives.
+ *   PM_ESHAPE: B outside 1..65535, crop < 1, crop > resize (torchvision pads there), a non-positive size.  Every refusal returns
+ *   before the first launch.  The tables are device memory and are trusted as those of pm_aug_resized_crop_ragged_u8 are: H_b <=
+ *   Hmax, W_b <= Wmax, frame b inside src, the window inside nh x nw.  Reads stay inside frame b and writes inside dst and the
+ *   queried workspace whatever win holds. */
+int pm_aug_resize_center_crop_workspace(int B, int Hmax, int Wmax, int resize, int crop, size_t* bytes);
+int pm_aug_resize_center_crop_ragged_u8(const unsigned char* src, const long long* offset, const int* hw, const int* win,
+                                        unsigned char* dst, int B, int Hmax, int Wmax, int resize, int crop, void* workspace,
+                                        size_t ws_bytes, void* stream);
+
 /* ColorJitter: per sample, ops in `order` (0 brightness, 1 contrast, 2 saturation, 3 hue; -1 = none): ImageEnhance blends (float32,
  * truncating / clipping as Blend.c), contrast against int(mean luminance + 0.5) of the image as it stands before that op, hue as
  * an HSV round trip with H += hue_shift (uint8 wrap-around; hue_shift = uint8(hue_factor * 255)).  lsum: u64 [B] scratch.

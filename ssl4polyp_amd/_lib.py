@@ -53,6 +53,8 @@ SIGNATURES = {
     "pm_aug_resize_u8": [P, P, P, P, P, I, P, P, I, I, I, I, I, I, P],
     "pm_aug_resized_crop_u8": [P, P, P, I, I, I, I, I, P, ctypes.c_size_t, P],
     "pm_aug_resized_crop_ragged_u8": [P, P, P, P, P, I, I, I, I, I, P, ctypes.c_size_t, P],
+    "pm_aug_resize_center_crop_workspace": [I, I, I, I, I, P],
+    "pm_aug_resize_center_crop_ragged_u8": [P, P, P, P, P, I, I, I, I, I, P, ctypes.c_size_t, P],
     "pm_aug_color_jitter_u8": [P, P, P, P, I, I, I, P],
     "pm_aug_gaussian_blur_u8": [P, P, P, P, I, I, I, I, P],
     "pm_aug_geometry_u8": [P, P, P, I, I, I, I, F, F, F, F, F, F, P],

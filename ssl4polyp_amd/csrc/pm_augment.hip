@@ -233,6 +233,133 @@ __global__ __launch_bounds__(256) void resample_crop_jpeg_kernel(const unsigned 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Validation transform: Resize(resize, bicubic) + CenterCrop(crop) = Image.resize((nw, nh), BICUBIC).crop(window) without the
+// resized frame.  Pillow resamples the whole frame horizontally, rounds to u8, then vertically; an output pixel of the window
+// depends on its own column's and row's taps only, so the taps of the FULL resized size are built for the window's crop columns
+// and rows alone, the horizontal pass runs over the source rows the window's vertical taps read, and the vertical pass over tmp.
+// ---------------------------------------------------------------------------------------------
+// win[b] = (nh, nw, top, left): the full resized size and the window's origin in it.  blockIdx.y = axis (0: horizontal taps, in_size
+// W_b, out_size nw, first output index left; 1: vertical, H_b, nh, top); one thread per (sample, window index); the arithmetic is
+// resample_coeffs_kernel's with the bicubic filter.  bounds [2][B][crop][2] holds the x tables, then the y tables; taps
+// [2][B][ksize][crop] has the window index innermost, so that the lanes of the horizontal pass, which run along it, read tap t of
+// their 64 outputs from consecutive words.
+__global__ __launch_bounds__(256) void center_crop_coeffs_kernel(const int* __restrict__ hw, const int* __restrict__ win, int crop,
+                                                                 int ksize_max, int* __restrict__ bounds, int* __restrict__ taps,
+                                                                 int B) {
+  const int id = blockIdx.x * 256 + threadIdx.x;
+  if (id >= B * crop) return;
+  const int axis = blockIdx.y;
+  const int b = id / crop, i = id % crop;
+  const int in_size = hw[2 * b + (axis ? 0 : 1)];
+  const int out_size = win[4 * b + (axis ? 0 : 1)];
+  const int xx = win[4 * b + (axis ? 2 : 3)] + i;
+  const double scale = (double)in_size / (double)out_size;
+  const double filterscale = scale < 1.0 ? 1.0 : scale;
+  const double support = 2.0 * filterscale;
+  const double center = (xx + 0.5) * scale;
+  const double ss = 1.0 / filterscale;
+  int xmin = (int)(center - support + 0.5);
+  if (xmin < 0) xmin = 0;
+  int xmax = (int)(center + support + 0.5);
+  if (xmax > in_size) xmax = in_size;
+  xmax -= xmin;
+  if (xmax > ksize_max) xmax = ksize_max;  // (cannot happen when both resized sides are >= resize, which sized ksize_max)
+  double ww = 0.0;
+  for (int x = 0; x < xmax; ++x) ww += resample_filter((x + xmin - center + 0.5) * ss, 1);
+  int* k = taps + ((long)axis * B + b) * ksize_max * crop + i;
+  for (int x = 0; x < ksize_max; ++x) {
+    int v = 0;
+    if (x < xmax) {
+      double w = resample_filter((x + xmin - center + 0.5) * ss, 1);
+      if (ww != 0.0) w /= ww;
+      v = w < 0 ? (int)(-0.5 + w * (double)(1 << kPrecisionBits)) : (int)(0.5 + w * (double)(1 << kPrecisionBits));
+    }
+    k[(long)x * crop] = v;
+  }
+  const long ti = (long)axis * B * crop + id;
+  bounds[2 * ti] = xmin;
+  bounds[2 * ti + 1] = xmax;
+}
+
+__device__ __forceinline__ void store_px8(unsigned char* q, int ss0, int ss1, int ss2) {
+  ss0 >>= kPrecisionBits; ss1 >>= kPrecisionBits; ss2 >>= kPrecisionBits;
+  q[0] = (unsigned char)(ss0 < 0 ? 0 : (ss0 > 255 ? 255 : ss0));
+  q[1] = (unsigned char)(ss1 < 0 ? 0 : (ss1 > 255 ? 255 : ss1));
+  q[2] = (unsigned char)(ss2 < 0 ? 0 : (ss2 > 255 ? 255 : ss2));
+}
+
+// one pass, sample b = blockIdx.y; the source rows the window reads are row0 .. row0 + rows of frame b, from the sample's first and
+// last vertical bounds (they ascend with the output row), rows capped at the `rows_cap` rows tmp holds per sample:
+//   horizontal: frame b (byte offset[b], rows of hw[b][1] pixels) rows row0 .. -> tmp [B][rows_cap][crop] rows 0 .. rows
+//   vertical:   tmp -> dst [B][crop][crop]
+// Lanes run along the output x of one row; blockIdx.x strides over the sample's rows x crop or crop x crop outputs.  The
+// horizontal pass is bound by the number of gather instructions (neighbouring lanes start 3 x scale bytes apart), so it fetches a
+// source pixel as ONE unaligned 4-byte load -- its three bytes and the next pixel's first -- except the last tap's pixel, which
+// may be the last of the frame and is read byte by byte.
+template <bool VERTICAL>
+__global__ __launch_bounds__(256) void center_crop_pass_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ tmp,
+                                                              unsigned char* __restrict__ dst, const long long* __restrict__ offset,
+                                                              const int* __restrict__ hw, const int* __restrict__ bounds,
+                                                              const int* __restrict__ taps, int ksize, int B, int crop, int rows_cap) {
+  const int b = blockIdx.y;
+  const long tx = (long)b * crop, ty = ((long)B + b) * crop;
+  const int row0 = bounds[2 * ty];
+  int rows = bounds[2 * (ty + crop - 1)] + bounds[2 * (ty + crop - 1) + 1] - row0;
+  rows = rows > rows_cap ? rows_cap : rows;
+  unsigned char* mid = tmp + (long)b * rows_cap * crop * 3;
+  const int* kb = taps + ((VERTICAL ? (long)B : 0L) + b) * ksize * crop;
+  if constexpr (VERTICAL) {
+    unsigned char* out = dst + (long)b * crop * crop * 3;
+    const long stride = (long)crop * 3;
+    for (long id = (long)blockIdx.x * 256 + threadIdx.x; id < (long)crop * crop; id += (long)gridDim.x * 256) {
+      const int xo = id % crop;
+      const int yo = id / crop;
+      const int lo = bounds[2 * (ty + yo)] - row0;  // rows of tmp count from row0
+      int n = bounds[2 * (ty + yo) + 1];
+      n = n > rows - lo ? rows - lo : n;            // never past the rows the horizontal pass wrote
+      const int* k = kb + yo;
+      int ss0 = 1 << (kPrecisionBits - 1), ss1 = ss0, ss2 = ss0;
+      const unsigned char* p = mid + lo * stride + xo * 3;
+      for (int t = 0; t < n; ++t) {
+        const int kk = k[(long)t * crop];
+        ss0 += p[0] * kk;
+        ss1 += p[1] * kk;
+        ss2 += p[2] * kk;
+        p += stride;
+      }
+      store_px8(out + id * 3, ss0, ss1, ss2);
+    }
+  } else {
+    const long stride = (long)hw[2 * b + 1] * 3;  // bytes per source row
+    const unsigned char* img = src + offset[b] + row0 * stride;
+    for (long id = (long)blockIdx.x * 256 + threadIdx.x; id < (long)rows * crop; id += (long)gridDim.x * 256) {
+      const int xo = id % crop;
+      const int yo = id / crop;
+      const int lo = bounds[2 * (tx + xo)], n = bounds[2 * (tx + xo) + 1];
+      const int* k = kb + xo;
+      int ss0 = 1 << (kPrecisionBits - 1), ss1 = ss0, ss2 = ss0;
+      const unsigned char* p = img + yo * stride + (long)lo * 3;
+      for (int t = 0; t < n - 1; ++t) {
+        unsigned int v;
+        __builtin_memcpy(&v, p, 4);
+        const int kk = k[(long)t * crop];
+        ss0 += (int)(v & 255u) * kk;
+        ss1 += (int)((v >> 8) & 255u) * kk;
+        ss2 += (int)((v >> 16) & 255u) * kk;
+        p += 3;
+      }
+      if (n > 0) {
+        const int kk = k[(long)(n - 1) * crop];
+        ss0 += p[0] * kk;
+        ss1 += p[1] * kk;
+        ss2 += p[2] * kk;
+      }
+      store_px8(mid + id * 3, ss0, ss1, ss2);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // ColorJitter: four per-pixel ops in a per-sample order; contrast needs the image's mean luminance first
 // ---------------------------------------------------------------------------------------------
 struct Px { int r, g, b; };
@@ -758,6 +885,61 @@ extern "C" int pm_jpeg_resized_crop_u8(const unsigned char* planes, long blocks,
   if (n_fallback > 0 && (!fallback_table || !fallback)) return PM_EINVAL;
   const JpegSource j = {planes, blocks, frames, n_frames, fallback, fallback_bytes, fallback_table, n_fallback, source};
   return resized_crop_launch(nullptr, nullptr, hw, box, dst, bicubic, B, Hmax, Wmax, out, workspace, ws_bytes, stream, &j);
+}
+
+// the sizes of the Resize + CenterCrop workspace: both resized sides are >= resize, so no axis shrinks by more than big / resize
+struct CenterCropPlan {
+  int ksize;      // taps per output index: Resample.c's ceil(support) * 2 + 1 at the largest scale, + 2
+  int rows_cap;   // source rows one window's vertical taps can span: (crop - 1) * scale + 2 * support + 1, at most Hmax
+  size_t tables;  // bytes of the bounds and the taps of both axes
+  size_t bytes;
+};
+
+static int center_crop_plan(int B, int Hmax, int Wmax, int resize, int crop, CenterCropPlan* p) {
+  if (B <= 0 || B > 65535 || Hmax <= 0 || Wmax <= 0 || resize <= 0 || crop < 1 || crop > resize) return PM_ESHAPE;
+  if ((long)B * crop > 0x3fffffffL) return PM_ESHAPE;  // (table indices are int)
+  const int big = Hmax > Wmax ? Hmax : Wmax;
+  const double fs = big > resize ? (double)big / resize : 1.0;
+  p->ksize = (int)ceil(2.0 * fs) * 2 + 3;
+  const double sv = (double)Hmax / resize;
+  const double span = (crop - 1) * sv + 4.0 * (sv > 1.0 ? sv : 1.0) + 3.0;
+  p->rows_cap = span < (double)Hmax ? (int)span : Hmax;
+  p->tables = 2 * ((size_t)B * crop * 2 + (size_t)B * crop * p->ksize) * sizeof(int);
+  p->bytes = (p->tables + (size_t)B * p->rows_cap * crop * 3 + 15) & ~(size_t)15;
+  return PM_OK;
+}
+
+extern "C" int pm_aug_resize_center_crop_workspace(int B, int Hmax, int Wmax, int resize, int crop, size_t* bytes) {
+  CenterCropPlan p;
+  const int st = center_crop_plan(B, Hmax, Wmax, resize, crop, &p);
+  if (st != PM_OK) return st;
+  if (!bytes) return PM_EINVAL;
+  *bytes = p.bytes;
+  return PM_OK;
+}
+
+extern "C" int pm_aug_resize_center_crop_ragged_u8(const unsigned char* src, const long long* offset, const int* hw, const int* win,
+                                                   unsigned char* dst, int B, int Hmax, int Wmax, int resize, int crop,
+                                                   void* workspace, size_t ws_bytes, void* stream) {
+  if (!src || !offset || !hw || !win || !dst || !workspace) return PM_EINVAL;
+  CenterCropPlan p;
+  const int st = center_crop_plan(B, Hmax, Wmax, resize, crop, &p);
+  if (st != PM_OK) return st;
+  if (ws_bytes < p.bytes) return PM_EINVAL;
+  if ((uintptr_t)workspace & 15) return PM_EALIGN;
+  int* bounds = reinterpret_cast<int*>(workspace);
+  int* taps = bounds + (size_t)B * crop * 4;
+  unsigned char* tmp = reinterpret_cast<unsigned char*>(workspace) + p.tables;
+  hipStream_t s = pm_stream(stream);
+  hipLaunchKernelGGL(center_crop_coeffs_kernel, dim3((B * crop + 255) / 256, 2), dim3(256), 0, s, hw, win, crop, p.ksize, bounds, taps,
+                     B);
+  const int cap = 8192 / B > 1 ? 8192 / B : 1;  // (at most 8192 blocks over the B samples, as the resized crop)
+  hipLaunchKernelGGL(center_crop_pass_kernel<false>, dim3(aug_grid((long)p.rows_cap * crop, cap), B), dim3(256), 0, s, src, tmp, dst,
+                     offset,
+                     hw, bounds, taps, p.ksize, B, crop, p.rows_cap);
+  hipLaunchKernelGGL(center_crop_pass_kernel<true>, dim3(aug_grid((long)crop * crop, cap), B), dim3(256), 0, s, src, tmp, dst, offset,
+                     hw, bounds, taps, p.ksize, B, crop, p.rows_cap);
+  return pm_check_launch();
 }
 
 extern "C" int pm_aug_color_jitter_u8(const unsigned char* src, unsigned char* dst, const pm_aug_jitter* jitter,

@@ -288,6 +288,25 @@ def _whole_frame_boxes(hw) -> np.ndarray:
     return boxes
 
 
+def center_crop_windows(hw, resize: int, crop: int) -> np.ndarray:
+    """torchvision Resize(resize) + CenterCrop(crop) of frames of sizes hw [B, 2] = (H_b, W_b) -> int32 [B, 4] = (nh, nw, top, left):
+    the full resized size and the crop window's origin in it, in the arithmetic of mae_recipe._ValFrames.  Resize(int) brings the
+    shorter side to `resize` and the other to int(resize * other / shorter), and does nothing when the shorter side already equals
+    `resize`; center_crop's origin is int(round((n - crop) / 2.0)), Python's round-half-to-even."""
+    resize, crop = int(resize), int(crop)
+    if crop < 1 or crop > resize:
+        raise ValueError(f"crop must be in 1..resize (torchvision pads a crop of {crop} out of a resize to {resize}: not built)")
+    out = np.zeros((len(hw), 4), dtype=np.int32)
+    for b, (h, w) in enumerate(hw):
+        h, w = int(h), int(w)
+        if h <= 0 or w <= 0:
+            raise ValueError("frames must be non-empty")
+        if (w <= h and w != resize) or (h <= w and h != resize):
+            h, w = (int(resize * h / w), resize) if w <= h else (resize, int(resize * w / h))
+        out[b] = (h, w, int(round((h - crop) / 2.0)), int(round((w - crop) / 2.0)))
+    return out
+
+
 class _Scratch:
     """The device buffers one object keeps across calls, by name (`bufs`), so that a steady stream of batches allocates nothing."""
 
@@ -381,6 +400,25 @@ class DeviceAugmenter:
         _lib.check(lib.pm_aug_resize_u8(frames.data_ptr(), tmp.data_ptr(), out.data_ptr(), bx.data_ptr(), tx.data_ptr(), kx,
                                         by.data_ptr(), ty.data_ptr(), ky, B, Hs, Ws, S, S,
                                         torch.cuda.current_stream(self.device).cuda_stream), "pm_aug_resize_u8")
+        return out
+
+    def resize_center_crop(self, frames: "RaggedFrames", resize: int = 256, crop: Optional[int] = None) -> torch.Tensor:
+        """A device-resident RaggedFrames -> uint8 [B, crop, crop, 3] (crop=None: self.size): the validation transform of the MAE
+        recipes, Resize(resize, bicubic) + CenterCrop(crop) as torchvision runs it on PIL images, byte for byte
+        (pm_aug_resize_center_crop_ragged_u8; the windows are center_crop_windows of the frames' sizes).  crop > resize raises
+        ValueError: torchvision pads there, which is not built."""
+        if not isinstance(frames, RaggedFrames):
+            raise TypeError("resize_center_crop takes a RaggedFrames")
+        _check_ragged_on_device(frames, "DeviceAugmenter")
+        B, R, C, sc = len(frames), int(resize), int(self.size if crop is None else crop), self._scratch
+        win = center_crop_windows(frames.sizes, R, C)
+        Hmax, Wmax = (int(v) for v in frames.sizes.max(0))
+        ws = sc.grow("center_ws", _lib.workspace_bytes("pm_aug_resize_center_crop_workspace", B, Hmax, Wmax, R, C), torch.uint8)
+        win_d = sc.upload("center_win", win)
+        out = sc.exact("center_out", (B, C, C, 3), torch.uint8)
+        _lib.check(_lib.load().pm_aug_resize_center_crop_ragged_u8(
+            frames.data.data_ptr(), frames.offset.data_ptr(), frames.hw.data_ptr(), win_d.data_ptr(), out.data_ptr(), B, Hmax, Wmax, R,
+            C, ws.data_ptr(), ws.numel(), torch.cuda.current_stream(self.device).cuda_stream), "pm_aug_resize_center_crop_ragged_u8")
         return out
 
     def random_resized_crop(self, frames, boxes=None, generator: Optional[torch.Generator] = None,
@@ -813,7 +851,7 @@ class DevicePrefetcher:
     def __init__(self, loader: Iterable, device, mean: Sequence[float] = IMAGENET_MEAN, std: Sequence[float] = IMAGENET_STD,
                  flip_p: float = 0.0, generator: Optional[torch.Generator] = None, augment: Optional["DeviceAugmenter"] = None,
                  stream: str = "auto", transform: str = "train", perturb: Optional["DevicePerturber"] = None,
-                 rest_to_device: bool = True, fused_decode: bool = False):
+                 rest_to_device: bool = True, fused_decode: bool = False, eval_resize: int = 256):
         """augment: a DeviceAugmenter -> the loader may yield decoded frames of any size and a transform of the reference runs on
         the copy stream, drawing its parameters from `generator` (`flip_p` is then ignored):
           transform="train": the classification train transform (Resize, ColorJitter, GaussianBlur(25), flips,
@@ -822,7 +860,11 @@ class DevicePrefetcher:
                              mae/main_pretrain.py:156-160);
           transform="eval":  ClassificationTransforms(stage="val" / "test") (transforms.py:247-256): Resize((S, S)), the row
                              perturbations when a DevicePerturber is given as `perturb` (the rows are the LAST element of the
-                             batch), ToTensor, Normalize -- into the slot's own f32 buffer; nothing random.
+                             batch), ToTensor, Normalize -- into the slot's own f32 buffer; nothing random;
+          transform="mae_eval": the validation transform of the MAE recipes (mae/main_linprobe.py:151-156): Resize(eval_resize,
+                             bicubic) + CenterCrop(S) (DeviceAugmenter.resize_center_crop), ToTensor, Normalize -- no flips, nothing
+                             random.  The batches are RaggedFrames or JpegBatch; fused_decode is refused (the variant that reads
+                             the JPEG planes directly is not built).
         rest_to_device=False leaves the tensors after the frames (the labels) on the host: train.evaluate_cls reads the targets of
         every batch on the host, which is a device sync per batch when they were moved.
         fused_decode=True: a JpegBatch is not decoded to full-size RGB frames first; the decoder does the first stage of the
@@ -845,9 +887,12 @@ class DevicePrefetcher:
         "auto": "side" when a torch.distributed process group is initialised, "own" otherwise."""
         if stream not in ("auto", "own", "side"):
             raise ValueError("stream must be 'auto', 'own' or 'side'")
-        if transform not in ("train", "mae", "eval"):
-            raise ValueError("transform must be 'train', 'mae' or 'eval'")
-        if transform in ("mae", "eval") and augment is None:
+        if transform not in ("train", "mae", "eval", "mae_eval"):
+            raise ValueError("transform must be 'train', 'mae', 'eval' or 'mae_eval'")
+        if transform == "mae_eval" and fused_decode:
+            raise ValueError("transform='mae_eval' does not take fused_decode=True: the Resize + CenterCrop that reads the decoder's "
+                             "component planes directly is not built; the batch is decoded to RGB frames first")
+        if transform in ("mae", "eval", "mae_eval") and augment is None:
             raise ValueError(f"transform='{transform}' needs a DeviceAugmenter (augment=...)")
         if perturb is not None and transform != "eval":
             raise ValueError("perturb=... applies to transform='eval' only")
@@ -855,7 +900,7 @@ class DevicePrefetcher:
         self.perturb, self.rest_to_device, self.fused_decode = perturb, bool(rest_to_device), bool(fused_decode)
         self.loader, self.device = loader, torch.device(device)
         self.mean, self.std, self.flip_p, self.generator = mean, std, float(flip_p), generator
-        self.augment = augment
+        self.augment, self.eval_resize = augment, int(eval_resize)
         self._pin = [{}, {}]        # per slot: pinned staging tensors by name, flat and grow-only
         self._dev = [{}, {}]        # per slot: device staging tensors by name, flat and grow-only
         self._out = [None, None]    # per slot: the float32 images
@@ -907,6 +952,10 @@ class DevicePrefetcher:
             if cropped:
                 return self.augment.mae_tail(x, generator=self.generator, out=out)
             return self.augment.mae_transform(x, generator=self.generator, out=out)
+        if self.transform == "mae_eval":
+            if not isinstance(x, RaggedFrames):
+                raise ValueError("transform='mae_eval' takes RaggedFrames or JpegBatch batches")
+            return preprocess_u8(self.augment.resize_center_crop(x, self.eval_resize), None, self.mean, self.std, out=out)
         if self.transform == "eval":
             x = self.augment.resize(x)
             if self.perturb is not None and rest[-1] is not None:

@@ -5,7 +5,16 @@ Training frames: folder.folder_loader on DATA/train, the workers only decode; on
 (data.draw_linprobe_boxes -- not torchvision's sampler) through DeviceAugmenter.random_resized_crop(bicubic), then flip / ToTensor /
 Normalize (mae_tail).  Validation frames: the workers do Resize(256, bicubic) + CenterCrop(224) with Pillow, as the reference's workers
 do, and the device normalises (preprocess_u8).  The crops, flips and the sampler's order of epoch e depend on (seed, e) alone, so a
-resumed run continues as the uninterrupted one."""
+resumed run continues as the uninterrupted one.
+
+Two flags move the remaining host work to the device without changing a byte of any batch; both default to `host`:
+  --decode device          the train workers only read and pack the files (folder_loader(decode="device")); the step decodes the
+                           JpegBatch with DeviceJpegDecoder into the RaggedFrames it then crops.  Files the device decoder does not
+                           take (progressive or greyscale JPEG, PNG, ...) are decoded by the packer in the workers, as elsewhere.
+  --val_transform device   the val workers only decode (or, with --decode device, only read and pack); Resize + CenterCrop run on
+                           the device (DeviceAugmenter.resize_center_crop: Pillow's bicubic taps for the full resized size, evaluated
+                           for the crop window only) behind a DevicePrefetcher(transform="mae_eval").  build_val_loader builds
+                           either input; a loader the caller passes in is used as it is."""
 from __future__ import annotations
 
 import json
@@ -45,7 +54,16 @@ def add_common_flags(p, precision_help: str):
     p.add_argument("--no_pin_mem", action="store_false", dest="pin_mem")
     p.set_defaults(pin_mem=True)
     p.add_argument("--precision", default="bf16", choices=["bf16", "fp16", "fp32"], help=precision_help)
+    p.add_argument("--decode", default="host", choices=["host", "device"],
+                   help="where the files are decoded: in the workers with Pillow, or on the device (baseline JPEG; the workers then "
+                        "only read and pack the files, and decode what the device does not take)")
+    p.add_argument("--val_transform", default="host", choices=["host", "device"],
+                   help="where the validation Resize(256, bicubic) + CenterCrop runs: in the workers with Pillow, or on the device "
+                        "(the same bytes)")
     return p
+
+
+VAL_RESIZE = 256   # main_linprobe.py:152: Resize(256, interpolation=3) in front of CenterCrop(224)
 
 
 class _ValFrames(torch.utils.data.Dataset):
@@ -79,6 +97,41 @@ def _val_collate(items):
     return torch.from_numpy(np.stack(frames)), torch.tensor(labels, dtype=torch.int64)
 
 
+def _normalise_on(device):
+    """prepare(batch) of cropped host frames: (uint8 [B, S, S, 3], labels) -> (ToTensor + Normalize, f32 [B, 3, S, S], labels) on
+    the device."""
+    from .data import preprocess_u8
+
+    def prepare(batch):
+        frames, labels = batch
+        return preprocess_u8(frames.to(device, non_blocking=True)), labels.to(device, non_blocking=True)
+
+    return prepare
+
+
+def build_val_loader(args, device, crop_size: int):
+    """The validation input over DATA/val in file order, short last batch kept -> (loader, prepare): prepare(batch) gives (images f32
+    [B, 3, crop_size, crop_size], labels) on the device; the images are the same bytes whatever the flags say.
+      --val_transform host:   the workers run _ValFrames (Pillow), the device normalises;
+      --val_transform device: the workers only decode (--decode host: RaggedFrames) or only read and pack the files (--decode
+                              device: JpegBatch, decoded by DeviceJpegDecoder), and a DevicePrefetcher(transform="mae_eval") does
+                              Resize + CenterCrop + normalise on its copy stream.  Its image tensor is a per-slot buffer that is
+                              refilled two batches later."""
+    from .data import DeviceAugmenter, DevicePrefetcher
+    from .folder import ImageFolderFrames, jpeg_collate, ragged_collate
+    root = os.path.join(args.data_path, "val")
+    extra = {"multiprocessing_context": "spawn", "persistent_workers": True} if args.num_workers > 0 else {}
+    common = dict(batch_size=args.batch_size, shuffle=False, num_workers=args.num_workers, pin_memory=args.pin_mem, drop_last=False,
+                  **extra)
+    if args.val_transform == "host":
+        return torch.utils.data.DataLoader(_ValFrames(root, VAL_RESIZE, crop_size), collate_fn=_val_collate, **common), \
+            _normalise_on(device)
+    loader = torch.utils.data.DataLoader(ImageFolderFrames(root, decode=args.decode),
+                                         collate_fn=jpeg_collate if args.decode == "device" else ragged_collate, **common)
+    return DevicePrefetcher(loader, device, augment=DeviceAugmenter(device, size=crop_size), transform="mae_eval",
+                            eval_resize=VAL_RESIZE), lambda batch: (batch[0], batch[-1])
+
+
 def start(args) -> torch.device:
     """The process's device, made current, and the host seeds."""
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
@@ -107,35 +160,33 @@ def run_epochs(args, model, opt, device, train_epoch, *, crop_size: int, train_l
       (the probe), or only to the folder loaders built here, a passed loader yielding device batches as they are (the fine-tune).
     scaler: the fp16 loss scaler restored from / saved into the checkpoints.  log_extra: further keys of the log.txt line;
     log_encoding: the encoding log.txt is opened with."""
-    from .data import DeviceAugmenter, draw_linprobe_boxes, preprocess_u8
+    from .data import DeviceAugmenter, DeviceJpegDecoder, draw_linprobe_boxes
     from .folder import folder_loader
+    from .jpeg import JpegBatch
     if args.resume:
         args.start_epoch = load_mae_checkpoint(args.resume, model, opt, args, loss_scaler=scaler)
     aug = DeviceAugmenter(device, size=crop_size)
     gen = torch.Generator()
     sampler = None
+    decoder = DeviceJpegDecoder(device)
 
     def prepare_train(batch):
         frames, labels = batch
         frames = frames.to(device, non_blocking=True)
+        if isinstance(frames, JpegBatch):   # (--decode device: the RaggedFrames the workers would have decoded, byte for byte)
+            frames = decoder(frames)
         hw = frames.sizes
         boxes = draw_linprobe_boxes(len(frames), hw[:, 0], hw[:, 1], gen)
         return aug.mae_tail(aug.random_resized_crop(frames, boxes=boxes), generator=gen), labels.to(device, non_blocking=True)
 
-    def prepare_val(batch):
-        frames, labels = batch
-        return preprocess_u8(frames.to(device, non_blocking=True)), labels.to(device, non_blocking=True)
-
+    prepare_val = _normalise_on(device)
     if val_loader is None:
-        extra = {"multiprocessing_context": "spawn", "persistent_workers": True} if args.num_workers > 0 else {}
-        val_loader = torch.utils.data.DataLoader(_ValFrames(os.path.join(args.data_path, "val")), batch_size=args.batch_size,
-                                                 shuffle=False, num_workers=args.num_workers, pin_memory=args.pin_mem,
-                                                 drop_last=False, collate_fn=_val_collate, **extra)
+        val_loader, prepare_val = build_val_loader(args, device, crop_size)
     elif not prepare_given:
         prepare_val = None
     if train_loader is None and not args.eval:
         train_loader = folder_loader(os.path.join(args.data_path, "train"), args.batch_size, 1, 0, args.seed, args.num_workers,
-                                     args.pin_mem)
+                                     args.pin_mem, decode=args.decode)
         sampler = train_loader.sampler
     elif not prepare_given:
         prepare_train = None

@@ -10,7 +10,8 @@ on DATA/val after every epoch, checkpoint-<epoch>.pth in the dict main_pretrain 
     python -m ssl4polyp_amd.main_finetune_mae --resume out/ckpts/checkpoint-49.pth --eval --data_path ...
 
 The input pipeline and the epoch loop are mae_recipe's, shared with main_linprobe: the device crop of mae/util/crop.py, flip, normalise
-for training; Resize(256) + CenterCrop in the workers for validation.  The crops, flips, the sampler's order and the mixing draws of
+for training; Resize(256) + CenterCrop in the workers for validation (--val_transform device: on the device, the same bytes;
+--decode device: the files are decoded on the device too).  The crops, flips, the sampler's order and the mixing draws of
 epoch e depend on (seed, e) alone, so a resumed run continues as the uninterrupted one.  The head, the pool and the loss run in f32 in every --precision.
 
 NOT BUILT -- accepted as flags at their "off" value only, refused otherwise:
