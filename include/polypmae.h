@@ -908,6 +908,25 @@ int pm_pool_norm_bwd(const float* dfeat, const float* pooled, const float* mean,
 int pm_linear_head_fwd(const float* feat, int B, int D, int C, const float* W, const float* bias, float* logits, void* stream);
 int pm_linear_head_dfeat(const float* dlogits, const float* W, int B, int D, int C, float* dfeat, void* stream);
 
+/* ---- stochastic depth of the fine-tune ViT (pm_droppath.hip; timm 0.4.12 DropPath, mae/main_finetune.py:251 drop_path_rate) ----
+ * A block's residual branches become x = x + s[b] * f(LN(x)) with one f32 scale per sample and branch.  Scale tables are f32, one
+ * entry per sample; row r of an [M = B N, D] tensor belongs to sample r / N.  Any finite scale is taken, not only {0, 1 / keep}.
+ * D % 4 == 0, M % N == 0, tensors 16-byte aligned.  No float atomics: results are run-to-run identical.
+ *   pm_drop_path_add:        out[r,:] = x[r,:] + scale[r / N] * y[r,:] in f32, the product rounded before the sum (the bits of
+ *                            torch's `x + y * s[:, None]`).  out may be y (in place on the buffer a GEMM just wrote).
+ *   pm_drop_path_scale_cast: dy_act[r,:] = cast(scale[r / N] * dy[r,:]) to act_dtype (PM_BF16 / PM_F16 / PM_F32, round to nearest
+ *                            even); colsum (optional, f32 [D]) += sum_r scale[r / N] * dy[r,:] through partial rows in `workspace`
+ *                            (pm_drop_path_workspace(M, D) bytes, 16-byte aligned; a smaller one is refused when colsum is given),
+ *                            summed in a fixed order.
+ *   pm_drop_path_scales:     noise f32 [depth, 2, B] of U[0, 1) (pm_mae_noise), rates f32 [depth] (drop probability per block, on
+ *                            the device) -> out[i, j, b] = fl32(keep_i + noise) >= 1 ? fl32(1 / keep_i) : 0 with keep_i =
+ *                            fl32(1 - rates[i]); a block at rate 0 gets exactly 1.0 everywhere. */
+int pm_drop_path_add(const float* x, const float* y, float* out, const float* scale, int M, int N, int D, void* stream);
+int pm_drop_path_workspace(int M, int D, size_t* bytes);
+int pm_drop_path_scale_cast(const float* dy, const float* scale, void* dy_act, int act_dtype, float* colsum, int M, int N, int D,
+                            void* workspace, size_t ws_bytes, void* stream);
+int pm_drop_path_scales(const float* noise, const float* rates, float* out, int depth, int B, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,10 @@ SIGNATURES = {
     "pm_pool_norm_bwd": [P, P, P, P, P, I, I, I, P, P, I, P, P, P, ctypes.c_size_t, P],
     "pm_linear_head_fwd": [P, I, I, I, P, P, P, P],
     "pm_linear_head_dfeat": [P, P, I, I, I, P, P],
+    "pm_drop_path_add": [P, P, P, P, I, I, I, P],
+    "pm_drop_path_workspace": [I, I, P],
+    "pm_drop_path_scale_cast": [P, P, P, I, P, I, I, I, P, ctypes.c_size_t, P],
+    "pm_drop_path_scales": [P, P, P, I, I, P],
 }
 
 ABI_VERSION = 16  # pm_abi_version() of the library these signatures describe

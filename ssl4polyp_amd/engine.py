@@ -314,6 +314,18 @@ class Kernels:
         _lib.check(self.lib.pm_colsum_ws(_ptr(x), N, _lib.dtype_code(x.dtype), _ptr(out), M, N, _ptr(ws), need, _stream()),
                    "pm_colsum")
 
+    # -- stochastic depth (pm_droppath.hip): per-sample scales of a residual branch, scale f32 [M / N]
+    def drop_path_add(self, x, y, out, scale, M, N, D):
+        """out[r] = x[r] + scale[r // N] * y[r] over M rows of D f32 (out may be y)."""
+        _lib.check(self.lib.pm_drop_path_add(_ptr(x), _ptr(y), _ptr(out), _ptr(scale), M, N, D, _stream()), "pm_drop_path_add")
+
+    def drop_path_scale_cast(self, dy, scale, dy_act, colsum, M, N, D):
+        """dy_act[r] = act(scale[r // N] * dy[r]); colsum (f32 [D], None: not wanted) += the column sums of the scaled rows."""
+        need = self._need(("droppath", M, D), lambda: _lib.workspace_bytes("pm_drop_path_workspace", M, D)) if colsum is not None else 0
+        ws = self._scratch(need, dy.device) if need else None
+        _lib.check(self.lib.pm_drop_path_scale_cast(_ptr(dy), _ptr(scale), _ptr(dy_act), _lib.dtype_code(dy_act.dtype), _ptr(colsum),
+                                                    M, N, D, _ptr(ws), need, _stream()), "pm_drop_path_scale_cast")
+
     def attention_fwd(self, qkv, out, lse, B, N, H, dh):
         _lib.check(self.lib.pm_attention_fwd(_ptr(qkv), _ptr(out), _ptr(lse), B, N, H, dh, self.act, _stream()),
                    "pm_attention_fwd")
@@ -429,6 +441,7 @@ class StackWorkspace:
         self._top_c: Optional[dict] = None         # the cls-row top block's compact buffers (BlockStack.top_compact)
         self._deferred_join: list = []             # events a backward(defer_join=True) left for join_deferred
         self.cls_top = False                       # the last forward ran its top block on the cls rows: its result is [B, D]
+        self._drop_zero: Optional[torch.Tensor] = None  # f32 [M, D] zeros: the "residual" of a branch GEMM under stochastic depth
 
     def block(self, i: int) -> BlockWorkspace:
         return self.blocks[i if self.training else i % len(self.blocks)]
@@ -452,7 +465,8 @@ class BlockStack:
         dst.wait_event(ev)
 
     def forward(self, ws: StackWorkspace, x_in: torch.Tensor, W: Sequence[Dict[str, torch.Tensor]],
-                before_block: Optional[Callable[[int], None]] = None, keep_from: int = 0, cls_top: bool = False) -> torch.Tensor:
+                before_block: Optional[Callable[[int], None]] = None, keep_from: int = 0, cls_top: bool = False,
+                drop_scales: Optional[torch.Tensor] = None, drop_blocks: Optional[Sequence[bool]] = None) -> torch.Tensor:
         """x_in f32 [M, D]; W[i] maps BLOCK_PARAM_NAMES -> tensors (matrices act-typed, vectors f32).
         before_block(i) runs before block i's first kernel (gate on a pending optimizer update of its weights).
         keep_from: no backward will run through blocks below this index (frozen blocks under a frozen front: finetune.py:49-91), so
@@ -462,11 +476,22 @@ class BlockStack:
         the TOP block is then per-token work whose other rows nobody reads: proj + residual, LayerNorm2, fc1 + GELU, fc2 + residual run
         on the B cls rows (gathered behind the attention), and the result comes back as [B, D] (= [B, 1, D] for the head kernels).
         Whether the stack took that path (it needs N > 1 and a block to run) is left in `ws.cls_top`, where the backward and the
-        caller read it; a training workspace takes it at a batch that is a multiple of 8 only, and is refused here otherwise."""
+        caller read it; a training workspace takes it at a batch that is a multiple of 8 only, and is refused here otherwise.
+        drop_scales: stochastic depth -- f32 [depth, 2, B] on the device, the scale of sample b in the attention (0) / MLP (1) branch
+        of block i: x = x + s[b] * branch.  None: every launch below is what it was without the argument.  With a table, the blocks
+        named by drop_blocks (default: all) run kernel by kernel: proj and fc2 write the biased branch in f32 (EPI_RESIDUAL against
+        zeros, the plan these GEMMs have anyway) and pm_drop_path_add makes x_mid / x_out in place; the other blocks take today's
+        launches (their rows of the table must be 1).  The cls-row top block is off with a table.  The backward must get the same two
+        arguments."""
         k, g = self.k, self.g
         if not ws.training:
             keep_from = g.depth
         B, N, D = ws.B, ws.N, g.dim
+        drop = self._drop_plan(ws, drop_scales, drop_blocks)
+        if drop is not None:
+            cls_top = False
+            if any(drop) and ws._drop_zero is None:  # (filled on this stream, before the fork below)
+                ws._drop_zero = torch.zeros(ws.M, D, dtype=torch.float32, device=x_in.device)
         cls_top = bool(cls_top and N > 1 and g.depth >= 1)
         if cls_top and ws.training and B % 8:
             raise _lib.PolypMaeError("the cls-row top block needs a batch that is a multiple of 8 to train (16-byte k-major rows)")
@@ -507,7 +532,8 @@ class BlockStack:
                     before_block(i)
             bw, p = ws.block(i), W[i]
             top = cls_top and i == g.depth - 1
-            if fast and not top:
+            dropped = drop is not None and drop[i]
+            if fast and not top and not dropped:
                 # one C call per (block, sample range): pm_vit_block_fwd issues the same seven launches from a descriptor that
                 # is built once and kept (every buffer it names is persistent: workspace, flat parameters, bf16 shadow)
                 for j, (st, b0, b1) in enumerate(parts):
@@ -531,6 +557,10 @@ class BlockStack:
                         k.gather_rows(x.view(-1, D), idx, out=tc["x"][b0:b1])
                         k.gather_rows(bw.attn.view(-1, D), idx, out=tc["attn"][b0:b1])
                         self._mlp_half(p, [tc[n][b0:b1] for n in _MLP_HALF_BUFFERS], b1 - b0, i >= keep_from)
+                    elif dropped:
+                        self._mlp_half(p, [t[r0:r1] for t in (x, bw.attn, bw.x_mid, bw.ln2, bw.mean2, bw.rstd2, bw.h_pre, bw.h_act,
+                                                              bw.x_out)], r1 - r0, i >= keep_from,
+                                       drop=(drop_scales[i, 0, b0:b1], drop_scales[i, 1, b0:b1], ws._drop_zero[r0:r1], N))
                     else:
                         self._mlp_half(p, [t[r0:r1] for t in (x, bw.attn, bw.x_mid, bw.ln2, bw.mean2, bw.rstd2, bw.h_pre, bw.h_act,
                                                               bw.x_out)], r1 - r0, i >= keep_from)
@@ -551,16 +581,38 @@ class BlockStack:
         k.linear_fwd(ln1, p["attn.qkv.weight"], p["attn.qkv.bias"], qkv, r1 - r0, 3 * D, D)
         k.attention_fwd(qkv, bw.attn[r0:r1], bw.lse[h0:h1], b1 - b0, N, g.heads, g.dh)
 
-    def _mlp_half(self, p, bufs, M: int, keep: bool) -> None:
+    def _mlp_half(self, p, bufs, M: int, keep: bool, drop=None) -> None:
         """The last four launches of a block over M rows: proj + residual, LayerNorm2, fc1 + GELU, fc2 + residual.  bufs: the row
         ranges (_MLP_HALF_BUFFERS) of a BlockWorkspace and the block's input, or of the compact cls-row buffers.  keep: fc1 stores
-        its pre-activation (a backward will run through this block)."""
+        its pre-activation (a backward will run through this block).
+        drop = (attention scales, MLP scales, zeros f32 [M, D], N) of these rows' samples: stochastic depth -- the two residual GEMMs
+        add their branch to zeros and pm_drop_path_add makes x_mid = x + s * branch (and x_out) in place: six launches."""
         k, D, Hd = self.k, self.g.dim, self.g.hidden
         x, attn, x_mid, ln2, mean2, rstd2, h_pre, h_act, x_out = bufs
-        k.linear_fwd(attn, p["attn.proj.weight"], p["attn.proj.bias"], x_mid, M, D, D, EPI_RESIDUAL, resid=x)
+        s_attn, s_mlp, zero, N = drop if drop is not None else (None, None, None, 0)
+        k.linear_fwd(attn, p["attn.proj.weight"], p["attn.proj.bias"], x_mid, M, D, D, EPI_RESIDUAL, resid=x if drop is None else zero)
+        if drop is not None:
+            k.drop_path_add(x, x_mid, x_mid, s_attn, M, N, D)
         k.layernorm_fwd(x_mid, p["norm2.weight"], p["norm2.bias"], ln2, mean2, rstd2, M, D)
         k.linear_fwd(ln2, p["mlp.fc1.weight"], p["mlp.fc1.bias"], h_act, M, Hd, D, EPI_GELU, aux=h_pre if keep else None)
-        k.linear_fwd(h_act, p["mlp.fc2.weight"], p["mlp.fc2.bias"], x_out, M, D, Hd, EPI_RESIDUAL, resid=x_mid)
+        k.linear_fwd(h_act, p["mlp.fc2.weight"], p["mlp.fc2.bias"], x_out, M, D, Hd, EPI_RESIDUAL, resid=x_mid if drop is None else zero)
+        if drop is not None:
+            k.drop_path_add(x_mid, x_out, x_out, s_mlp, M, N, D)
+
+    def _drop_plan(self, ws: StackWorkspace, drop_scales: Optional[torch.Tensor], drop_blocks: Optional[Sequence[bool]]):
+        """Which blocks run with the scale table (a list of depth flags), None without a table; the table is checked here."""
+        if drop_scales is None:
+            return None
+        depth = self.g.depth
+        if (tuple(drop_scales.shape) != (depth, 2, ws.B) or drop_scales.dtype != torch.float32 or not drop_scales.is_contiguous()
+                or not drop_scales.is_cuda):
+            raise _lib.PolypMaeError(f"drop_scales must be a contiguous f32 [{depth}, 2, {ws.B}] tensor on the device "
+                                     f"(got {drop_scales.dtype} {tuple(drop_scales.shape)})")
+        if drop_blocks is None:
+            return [True] * depth
+        if len(drop_blocks) != depth:
+            raise _lib.PolypMaeError(f"drop_blocks names {len(drop_blocks)} blocks, the stack has {depth}")
+        return [bool(t) for t in drop_blocks]
 
     @staticmethod
     def top_compact(ws: StackWorkspace, g: StackGeom, act_dtype, dev) -> dict:
@@ -638,7 +690,8 @@ class BlockStack:
                  last_bias_grad_done: bool, trainable: Sequence[bool], need_input_grad: bool,
                  accumulate: Callable[[str, int], bool], on_block_done: Optional[Callable[[int], None]] = None,
                  prev_bias_grad: Optional[torch.Tensor] = None,
-                 ends_pass: bool = True, defer_join: bool = False) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
+                 ends_pass: bool = True, defer_join: bool = False, drop_scales: Optional[torch.Tensor] = None,
+                 drop_blocks: Optional[Sequence[bool]] = None) -> Tuple[Optional[torch.Tensor], Optional[torch.Tensor]]:
         """dx / dx_act: gradient w.r.t. the stack output (f32 + act copy).  G[i][name] = f32 gradient
         tensors (vectors are += targets and must be zeroed or hold the running sum; matrices follow
         accumulate(name, i)).  `last_bias_grad_done`: the producer of dx already added colsum(dx) into the
@@ -650,9 +703,19 @@ class BlockStack:
         stream's last launches then run beside that work instead of in front of it.
         `ws.cls_top` (left by the forward): dx / dx_act are the head's gradient on the B cls rows ([B, D]); the top block's backward
         then runs on those rows up to its attention (see _top_block_sparse).
+        drop_scales / drop_blocks: what the forward got (stochastic depth).  The identity path carries the gradient unscaled and a
+        branch receives s o dy, and every operation of a branch backward is linear per sample: a block that ran with the table goes
+        kernel by kernel, with the act copy of its incoming gradient made by pm_drop_path_scale_cast with the MLP scales (fc2.bias
+        gets the column sums of the scaled rows) and dmid_act made the same way with the attention scales (attn.proj.bias); whoever
+        produced the f32 gradient is asked for neither the act copy nor that column sum -- the LayerNorm1 backward of the block above
+        here, the caller for the top block: dx_act is then the buffer to fill, and `last_bias_grad_done` must be False.
         Returns (dx_in f32, dx_in act) or (None, None) when nothing below needs it."""
         k, g = self.k, self.g
         B, N, M, D, Hd = ws.B, ws.N, ws.M, g.dim, g.hidden
+        drop = self._drop_plan(ws, drop_scales, drop_blocks)
+        if drop and drop[-1] and last_bias_grad_done:
+            raise _lib.PolypMaeError("stochastic depth: the top block's fc2.bias gradient is the column sum of the SCALED gradient; "
+                                     "the caller must not have added the unscaled one")
         lowest = min([i for i, t in enumerate(trainable) if t], default=g.depth)
         main = torch.cuda.current_stream()
         pending: Dict[int, Tuple[torch.cuda.Event, ...]] = {}  # block -> side-stream event(s) after its last weight-gradient kernels
@@ -694,7 +757,11 @@ class BlockStack:
                     pending[i] = ev_last
                 dx, dx_act = din, din_act
                 continue
-            if i == g.depth - 1 and not last_bias_grad_done and tr:
+            dropped = drop is not None and drop[i]
+            below_dropped = drop is not None and i > 0 and drop[i - 1]   # block i-1 makes its own act copy and fc2.bias gradient
+            if dropped:
+                k.drop_path_scale_cast(dx, drop_scales[i, 1], dx_act, gr["mlp.fc2.bias"] if tr else None, M, N, D)
+            elif i == g.depth - 1 and not last_bias_grad_done and tr:
                 k.colsum(dx, gr["mlp.fc2.bias"], M, D)
             # Weight gradients run on a side stream, concurrently with the dgrad chain on the main stream: the two
             # kernels' blocks share the CUs out of phase, so one's epilogue / partial last round hides under the
@@ -705,7 +772,7 @@ class BlockStack:
             # whole dgrad chain of the block is enqueued; it runs beside block i-1's chain.  A grouped launch carries the qkv / fc1
             # bias gradients (column sums of its dY); otherwise they are k.colsum launches on the side stream.
             grouped = tr and (not ends_pass or i - lowest >= k.UNGROUP_TAIL) and k.can_group_wgrad(M, dims)
-            if grouped and fast:
+            if grouped and fast and not dropped and not below_dropped:
                 # the whole block in ONE C call (pm_vit_block_bwd): the same launches, the same fork / done events, from a
                 # descriptor built once per block and kept (every buffer it names is persistent)
                 acc = (int(accumulate("attn.qkv.weight", i)) | int(accumulate("attn.proj.weight", i)) << 1 |
@@ -759,7 +826,7 @@ class BlockStack:
                         ev_mlp.record(side)
 
             self._mlp_dgrad(p, gr if tr else None, M, dx, dx_act, bw.h_pre, d_hidden, ws.d_ln, bw.x_mid, bw.mean2, bw.rstd2, dmid, dmid_act,
-                            wgrad_behind_dfc2 if tr else None)
+                            wgrad_behind_dfc2 if tr else None, drop=(drop_scales[i, 0], N) if dropped else None)
             # ---- attention branch ----
             if tr and not grouped:
                 self.fork(main, side)
@@ -792,7 +859,8 @@ class BlockStack:
             if not (need_dx_in or tr):
                 join(0)
                 return None, None
-            self._qkv_dgrad_ln1(p, gr if tr else None, M, d_qkv, ws.d_ln, xin, bw.mean1, bw.rstd1, dmid, din, din_act, below_bias)
+            self._qkv_dgrad_ln1(p, gr if tr else None, M, d_qkv, ws.d_ln, xin, bw.mean1, bw.rstd1, dmid, din,
+                                None if below_dropped else din_act, None if below_dropped else below_bias)
             dx, dx_act = din, din_act
             if on_block_done is not None and not tr:
                 on_block_done(i)
@@ -803,18 +871,23 @@ class BlockStack:
         return dx, dx_act
 
     def _mlp_dgrad(self, p, gr, M: int, dy, dy_act, h_pre, d_hidden, d_ln, x_mid, mean2, rstd2, dmid, dmid_act,
-                   behind_dfc2: Optional[Callable[[], None]] = None) -> None:
+                   behind_dfc2: Optional[Callable[[], None]] = None, drop=None) -> None:
         """The dgrad chain of a block's MLP branch over M rows, dense or compact: dfc2 + dGELU (dy_act -> d_hidden), dfc1 (-> d_ln),
         LayerNorm2' (+ the residual gradient dy -> dmid f32, dmid_act).  gr: the block's gradient tensors, None when it is frozen
         (LayerNorm2' then leaves out d gamma, d beta and the proj bias gradient it carries).  behind_dfc2(): the caller's weight
-        gradients that read d_hidden, enqueued between dfc2 and dfc1 -- on which stream is its business."""
+        gradients that read d_hidden, enqueued between dfc2 and dfc1 -- on which stream is its business.
+        drop = (attention scales, N): stochastic depth -- dy_act came in scaled by the MLP scales; LayerNorm2' makes dmid alone, and
+        dmid_act and the proj bias gradient are the attention branch's view of it (pm_drop_path_scale_cast)."""
         k, D, Hd = self.k, self.g.dim, self.g.hidden
         k.linear_dgrad(dy_act, p["mlp.fc2.weight"], d_hidden, M, D, Hd, EPI_DGELU, aux=h_pre)
         if behind_dfc2 is not None:
             behind_dfc2()
         k.linear_dgrad(d_hidden, p["mlp.fc1.weight"], d_ln, M, Hd, D)
-        k.layernorm_bwd(d_ln, x_mid, p["norm2.weight"], mean2, rstd2, dy, dmid, dmid_act,
-                        gr["norm2.weight"] if gr else None, gr["norm2.bias"] if gr else None, gr["attn.proj.bias"] if gr else None, M, D)
+        proj_bias = gr["attn.proj.bias"] if gr else None
+        k.layernorm_bwd(d_ln, x_mid, p["norm2.weight"], mean2, rstd2, dy, dmid, dmid_act if drop is None else None,
+                        gr["norm2.weight"] if gr else None, gr["norm2.bias"] if gr else None, proj_bias if drop is None else None, M, D)
+        if drop is not None:
+            k.drop_path_scale_cast(dmid, drop[0], dmid_act, proj_bias, M, drop[1], D)
 
     def _qkv_dgrad_ln1(self, p, gr, M: int, d_qkv, d_ln, xin, mean1, rstd1, dmid, din, din_act, below_bias) -> None:
         """The tail of a block's backward over M rows: qkv dgrad (d_qkv -> d_ln), LayerNorm1' (+ dmid -> din f32, din_act; colsum of

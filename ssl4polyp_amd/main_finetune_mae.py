@@ -15,8 +15,9 @@ for training; Resize(256) + CenterCrop in the workers for validation (--val_tran
 epoch e depend on (seed, e) alone, so a resumed run continues as the uninterrupted one.  The head, the pool and the loss run in f32 in every --precision.
 
 NOT BUILT -- accepted as flags at their "off" value only, refused otherwise:
-  --drop_path > 0      stochastic depth needs a per-row scale in the residual GEMM epilogues.  THE DEFAULT HERE IS 0.0; THE REFERENCE'S
-                       IS 0.1: results of the reference's default recipe are not reproduced until that exists.
+  --drop_path > 0      the MODEL has stochastic depth (models_vit.VisionTransformer(drop_path_rate=...), csrc/pm_droppath.hip); this
+                       command line does not pass the flag on yet -- the remaining step.  THE DEFAULT HERE IS 0.0; THE REFERENCE'S
+                       IS 0.1: results of the reference's default recipe are not reproduced until the flag is switched over.
   --aa, --reprob, --color_jitter   timm's create_transform (RandAugment, random erasing, colour jitter).
   --dist_eval and more than one process;  --input_size other than the model's (position-embedding interpolation)."""
 from __future__ import annotations

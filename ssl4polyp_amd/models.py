@@ -110,6 +110,9 @@ class _Runtime:
         # requires_grad flag says (ViT_from_MAE keeps the deleted decoder's positional table, models.py:171-175)
         self.unused: tuple = ()
         self.grad_enabled = True  # torch.is_grad_enabled() where the op was called (ops.py): it is already off inside Function.forward
+        # stochastic depth of the NEXT vit_finetune_forward: (scale table f32 [depth, 2, B], blocks that run with it), set by
+        # models_vit.VisionTransformer.forward and taken by _VitFinetuneFn.forward (the op's schema carries tensors of the model only)
+        self.drop_path: Optional[tuple] = None
 
     def wait_updates(self, mat_through: Optional[int] = None, also=()) -> None:
         """Make the current stream (and the streams in `also`) wait for pending optimizer updates: all of them

@@ -28,11 +28,23 @@ class VisionTransformer(_ClassifierBase):
     """mae/models_vit.py:20-53 (timm 0.4.12 VisionTransformer + global_pool), same seeded initialisation order as
     models.VisionTransformer_from_Any.  With the probe head (add_probe_head) forward(imgs) = head(forward_features(imgs)) over the
     frozen, forward-only encoder; with the plain Linear it is built with, forward is the trainable classifier of the fine-tune
-    recipe (main_finetune.py), one autograd node over the engine.  Stochastic depth (drop_path) is not built."""
+    recipe (main_finetune.py), one autograd node over the engine.
+    drop_path_rate: stochastic depth as the reference builds it (main_finetune.py:251; timm 0.4.12 DropPath): block i of `depth`
+    drops each of its two residual branches per sample with probability drop_path_rates[i] = linspace(0, rate, depth)[i] while the
+    model is in training mode, and scales the kept ones by 1 / (1 - p_i).  The trainable classifier only: the probe's forward-only
+    feature path never drops.  Rate 0.0 (the default) and eval() run exactly the launches of a model built without the argument."""
 
     def __init__(self, img_size=224, patch_size=16, embed_dim=768, depth=12, num_heads=12, num_classes=1000, global_pool=False,
-                 precision: Optional[str] = None):
+                 precision: Optional[str] = None, drop_path_rate: float = 0.0):
         super().__init__()
+        drop_path_rate = float(drop_path_rate)
+        if not 0.0 <= drop_path_rate < 1.0:
+            raise ValueError(f"drop_path_rate must be in [0, 1) (got {drop_path_rate})")
+        self.drop_path_rate = drop_path_rate
+        # timm 0.4.12 vision_transformer.py: dpr = [x.item() for x in torch.linspace(0, drop_path_rate, depth)]
+        self.drop_path_rates = [float(v) for v in torch.linspace(0, drop_path_rate, depth)]
+        self.last_drop_scales: Optional[torch.Tensor] = None   # the scale table of the last training forward (f32 [depth, 2, B])
+        self._drop_rates_dev: Optional[torch.Tensor] = None
         norm_layer = partial(nn.LayerNorm, eps=1e-6)
         self.num_features = self.embed_dim = embed_dim
         self.global_pool = bool(global_pool)
@@ -63,7 +75,8 @@ class VisionTransformer(_ClassifierBase):
 
     @torch.no_grad()
     def forward_features(self, imgs: torch.Tensor) -> torch.Tensor:
-        """f32 [B, D], detached: norm(x)[:, 0], or fc_norm(x[:, 1:].mean(1)) with global_pool."""
+        """f32 [B, D], detached: norm(x)[:, 0], or fc_norm(x[:, 1:].mean(1)) with global_pool.  Never drops a path, whatever
+        drop_path_rate and the training flag say: the probe's encoder is frozen and forward-only."""
         rt = self._rt
         rt.ensure(imgs.device)
         assert imgs.shape[2] == self.patch_embed.img_size[0] and imgs.shape[3] == self.patch_embed.img_size[1]
@@ -75,7 +88,8 @@ class VisionTransformer(_ClassifierBase):
 
     @torch.no_grad()
     def forward_tokens(self, imgs: torch.Tensor) -> torch.Tensor:
-        """f32 [B, N, D]: the output of the last block, before any final norm (a copy: the workspace goes back to the pool)."""
+        """f32 [B, N, D]: the output of the last block, before any final norm (a copy: the workspace goes back to the pool).  Like
+        forward_features it never drops a path."""
         rt = self._rt
         rt.ensure(imgs.device)
         k, g = rt.k, rt.enc_geom
@@ -93,10 +107,48 @@ class VisionTransformer(_ClassifierBase):
         """timm 0.4.12 VisionTransformer.no_weight_decay (main_finetune.py:306)."""
         return {"pos_embed", "cls_token"}
 
-    def forward(self, imgs: torch.Tensor) -> torch.Tensor:
+    @property
+    def drop_path_active(self) -> bool:
+        """Does the next forward of the trainable classifier draw a scale table?  In training mode at a rate above 0 only."""
+        return bool(self.training and self.drop_path_rate > 0.0)
+
+    def _draw_drop_scales(self, B: int, device) -> torch.Tensor:
+        """The scale table f32 [depth, 2, B] of one training forward: depth * 2 * B uniforms from pm_mae_noise, keyed like
+        MaskedAutoencoderViT._draw_noise (seed and running offset of torch's device generator, the offset advanced by the numbers
+        drawn, rounded up to 4: re-seeding replays the tables, consecutive forwards differ), then pm_drop_path_scales: sample b keeps
+        branch j of block i when fl32(keep_i + u) >= 1 and is scaled by fl32(1 / keep_i), as timm's drop_path computes it."""
+        if torch.cuda.is_current_stream_capturing():
+            raise _lib.PolypMaeError("ViT forward with stochastic depth under stream capture: the drop-path draw would be baked into "
+                                     "the graph (the same paths dropped at every replay) -- pass `drop_scales=` from a buffer the "
+                                     "caller refills between replays")
+        depth = len(self.drop_path_rates)
+        n = depth * 2 * B
+        index = device.index if device.index is not None else torch.cuda.current_device()
+        gen = torch.cuda.default_generators[index]
+        seed = int(gen.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        off = int(gen.get_offset())
+        gen.set_offset(off + 4 * ((n + 3) // 4))   # (multiples of 4, as the generator requires)
+        key = (seed ^ ((off >> 32) * 0x9E3779B97F4A7C15)) & 0xFFFFFFFFFFFFFFFF
+        lib = self._rt.k.lib
+        rates = self._drop_rates_dev
+        if rates is None or rates.device != device:
+            rates = self._drop_rates_dev = torch.tensor(self.drop_path_rates, dtype=torch.float32, device=device)
+        noise = torch.empty(depth, 2, B, dtype=torch.float32, device=device)
+        scales = torch.empty_like(noise)
+        _lib.check(lib.pm_mae_noise(_ptr(noise), n, key, off & 0xFFFFFFFF, _stream()), "pm_mae_noise")
+        _lib.check(lib.pm_drop_path_scales(_ptr(noise), _ptr(rates), _ptr(scales), depth, B, _stream()), "pm_drop_path_scales")
+        return scales
+
+    def forward(self, imgs: torch.Tensor, drop_scales: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Probe head (add_probe_head): head(forward_features(imgs)), the encoder frozen and forward-only.  Plain nn.Linear head
-        (the fine-tune recipe, main_finetune.py): front, block stack, pooling and head as one autograd node (_VitFinetuneFn)."""
+        (the fine-tune recipe, main_finetune.py): front, block stack, pooling and head as one autograd node (_VitFinetuneFn).
+        Stochastic depth (training mode, drop_path_rate > 0): a scale table is drawn per forward (_draw_drop_scales) and blocks
+        whose rate is above 0 run with it; `drop_scales` (f32 [depth, 2, B] on the device: the scale of sample b in the attention /
+        MLP branch of block i) replaces the draw, as `noise=` does for the MAE -- every block then runs with the caller's table.
+        The table of the last training forward stays in `last_drop_scales`."""
         if isinstance(self.head, ProbeHead):
+            if drop_scales is not None:
+                raise _lib.PolypMaeError("drop_scales: the probe's encoder is frozen and forward-only; it never drops a path")
             return self.head(self.forward_features(imgs))
         if not isinstance(self.head, nn.Linear):
             raise _lib.PolypMaeError(f"models_vit.VisionTransformer: the head must be the probe head or a plain nn.Linear "
@@ -105,6 +157,20 @@ class VisionTransformer(_ClassifierBase):
         rt.ensure(imgs.device)
         assert imgs.shape[2] == self.patch_embed.img_size[0] and imgs.shape[3] == self.patch_embed.img_size[1]
         from . import ops  # registers torch.ops.polypmae.* on first use
+        rt.drop_path = None
+        if self.drop_path_active:
+            if drop_scales is None:
+                rt.drop_path = (self._draw_drop_scales(imgs.shape[0], imgs.device), [p > 0.0 for p in self.drop_path_rates])
+            else:
+                want = (len(self.drop_path_rates), 2, imgs.shape[0])
+                if (tuple(drop_scales.shape) != want or drop_scales.dtype != torch.float32 or drop_scales.device != imgs.device
+                        or not drop_scales.is_contiguous()):
+                    raise _lib.PolypMaeError(f"drop_scales must be a contiguous f32 {list(want)} tensor on the images' device "
+                                             f"(got {drop_scales.dtype} {list(drop_scales.shape)} on {drop_scales.device})")
+                rt.drop_path = (drop_scales, None)
+            self.last_drop_scales = rt.drop_path[0]
+        elif drop_scales is not None:
+            raise _lib.PolypMaeError("drop_scales: stochastic depth is active in training mode at drop_path_rate > 0 only")
         return torch.ops.polypmae.vit_finetune_forward(imgs, ops.register_runtime(rt), list(rt.flat.params))
 
 
@@ -131,9 +197,12 @@ class _VitFinetuneFn(torch.autograd.Function):
         cols, x0 = _EncoderFrontMixin.front_fwd(rt, imgs, None, L)
         ws = rt.get_ws(g, B, N, below)
         W, _ = rt.stack_weights("blocks.", g.depth)
-        cls_top = (not pool) and k.SPARSE_TOP and N > 1 and (B % 8 == 0 or not training)
+        drop_scales, drop_blocks = rt.drop_path if rt.drop_path is not None else (None, None)   # (this forward's alone)
+        rt.drop_path = None
+        # the cls-row top block is off under stochastic depth: its compact launches have no scaled form
+        cls_top = (not pool) and k.SPARSE_TOP and N > 1 and (B % 8 == 0 or not training) and drop_scales is None
         x = BlockStack(k, g).forward(ws, x0, W, before_block=_update_gate(rt, "blocks."), keep_from=need.keep_from(g.depth),
-                                     cls_top=cls_top)
+                                     cls_top=cls_top, drop_scales=drop_scales, drop_blocks=drop_blocks)
         Nh = 1 if ws.cls_top else N
         rt.wait_updates()
         dev, f32 = imgs.device, torch.float32
@@ -156,6 +225,7 @@ class _VitFinetuneFn(torch.autograd.Function):
                                           _ptr(logits), _stream()), "pm_linear_head_fwd")
         if training:
             ctx.rt, ctx.names, ctx.ws = rt, names, ws
+            ctx.drop = (drop_scales, drop_blocks)
             xs = x
             if not below:   # nothing under the final norm trains: keep what its backward reads, release the stack's buffers
                 xs = None if pool else x.view(B, Nh, D)[:, 0].clone()
@@ -175,6 +245,7 @@ class _VitFinetuneFn(torch.autograd.Function):
         lib = k.lib
         cols, x0, x, feat, pooled, mean, rstd = ctx.saved
         B, L, N, D, C, pool, below, x_rows = ctx.dims
+        drop_scales, drop_blocks = ctx.drop
         norm = "fc_norm" if pool else "norm"
         needs = list(ctx.needs_input_grad[3:])
         need = _Needs(names, needs, rt.unused)
@@ -204,22 +275,25 @@ class _VitFinetuneFn(torch.autograd.Function):
                 dx = ws.dx[0] if below_head else None
                 dx_act = ws.dx_act[0] if below_head else None
             gamma = f.param_view(norm + ".weight")
+            # stochastic depth on the top block: the block makes the act copy of its incoming gradient itself (scaled per sample)
+            top_dropped = drop_scales is not None and (drop_blocks is None or drop_blocks[-1])
+            dx_act_out = None if top_dropped else dx_act
             if pool:
                 nbytes = _lib.workspace_bytes("pm_pool_norm_bwd_workspace", B, N, D)
                 scratch = torch.empty((nbytes + 3) // 4, dtype=f32, device=dev)
                 _lib.check(lib.pm_pool_norm_bwd(_ptr(dfeat), _ptr(pooled), _ptr(mean), _ptr(rstd), _ptr(gamma), B, N, D, _ptr(dx),
-                                                _ptr(dx_act), k.act, _ptr(dgamma), _ptr(dbeta), _ptr(scratch), scratch.numel() * 4,
+                                                _ptr(dx_act_out), k.act, _ptr(dgamma), _ptr(dbeta), _ptr(scratch), scratch.numel() * 4,
                                                 _stream()), "pm_pool_norm_bwd")
             else:
                 _lib.check(lib.pm_vit_head_bwd(None, _ptr(dfeat), _ptr(x), x_rows, 0, _ptr(gamma), None, None, None, _ptr(mean),
-                                               _ptr(rstd), _ptr(dx), _ptr(dx_act), k.act, None, None, _ptr(dgamma), _ptr(dbeta), B, D, 0,
+                                               _ptr(rstd), _ptr(dx), _ptr(dx_act_out), k.act, None, None, _ptr(dgamma), _ptr(dbeta), B, D, 0,
                                                _stream()), "pm_vit_head_bwd")
         sync = rt.grad_sync
         if below_head:
             W, G = rt.stack_weights("blocks.", g.depth)
             cb = (lambda i: sync.block_done("blocks.", i)) if sync is not None else None
             dx0, _ = BlockStack(k, g).backward(ws, x0, W, G, dx, dx_act, False, trainable, front, lambda n, i: accumulate, cb,
-                                               defer_join=True)
+                                               defer_join=True, drop_scales=drop_scales, drop_blocks=drop_blocks)
             if front and dx0 is not None:
                 _EncoderFrontMixin.front_bwd(rt, dx0, cols, None, B, L, accumulate, need, True)
             BlockStack.join_deferred(ws)
