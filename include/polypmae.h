@@ -572,7 +572,9 @@ int pm_dgelu(const void* dy, const void* pre, void* out, int dtype, long n, void
 
 /* Fused multi-tensor AdamW over one flat f32 parameter range (torch.optim.AdamW semantics,
  * tc.py:5766-5768 / main_pretrain.py:218) that also refreshes the act-typed shadow copy used by the GEMMs.
- * grad_scale multiplies the gradient (1/world, 1/accum).  step >= 1. */
+ * grad_scale multiplies the gradient (1/world, 1/accum).  step >= 1.  p, g, m, v and an f32 shadow are moved as 16-byte
+ * vectors, a 16-bit shadow as 8-byte ones: a pointer not so aligned is PM_EALIGN before any launch (pm_adamw_dev and the
+ * segments of pm_adamw_segments / _list likewise). */
 int pm_adamw(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, long n, float lr,
              float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, void* stream);
 
@@ -615,7 +617,7 @@ int pm_adamw_grid(long n, int max_blocks);
  * state: f32[8] = [0] scale [1] growth tracker [2] found_inf of the last step [3] skipped steps [4] steps [5] 1/scale used.
  * stats: the pm_grad_stats triple of THIS step's (scaled) gradients.  Writes the skip flag and 1/scale into the `n_groups`
  * AdamW records, then moves the scale: x backoff_factor after a non-finite step, x growth_factor after growth_interval
- * clean steps in a row.  Launch order on one stream: pm_grad_stats ..., pm_loss_scale_update, pm_adamw_tick, pm_adamw_dev ... */
+ * clean steps in a row (a grown scale that overflows f32 is not taken: the scale stays, as in torch).  Launch order on one stream: pm_grad_stats ..., pm_loss_scale_update, pm_adamw_tick, pm_adamw_dev ... */
 int pm_loss_scale_update(float* state, const float* stats, float* hyper, int n_groups, float growth_factor,
                          float backoff_factor, int growth_interval, void* stream);
 

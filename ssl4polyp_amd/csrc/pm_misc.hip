@@ -416,7 +416,8 @@ __global__ void loss_scale_update_kernel(float* __restrict__ state, const float*
     } else {
       const float t = tracker + 1.f;
       if (t >= (float)interval) {
-        state[0] = scale * growth;
+        const float grown = scale * growth;
+        state[0] = fabsf(grown) < INFINITY ? grown : scale;  // a growth that overflows keeps the scale (torch._amp_update_scale_)
         state[1] = 0.f;
       } else {
         state[1] = t;
@@ -582,11 +583,19 @@ extern "C" int pm_dgelu(const void* dy, const void* pre, void* out, int dtype, l
   return pm_check_launch();
 }
 
+// The AdamW kernels move p, g, m, v (and an f32 shadow) as 16-byte vectors and a 16-bit shadow as 8-byte ones.
+static bool adamw_aligned(const void* p, const void* g, const void* m, const void* v, const void* shadow, int shadow_dtype) {
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return false;
+  return !shadow || !((uintptr_t)shadow & (shadow_dtype == PM_F32 ? 15 : 7));
+}
+
 extern "C" int pm_adamw(float* p, const float* g, float* m, float* v, void* shadow, int shadow_dtype, long n, float lr,
                         float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale,
                         void* stream) {
   if (!p || !g || !m || !v) return PM_EINVAL;
   if (n <= 0 || (n & 3) || step < 1) return PM_ESHAPE;
+  if (shadow && shadow_dtype != PM_BF16 && shadow_dtype != PM_F16 && shadow_dtype != PM_F32) return PM_EINVAL;
+  if (!adamw_aligned(p, g, m, v, shadow, shadow_dtype)) return PM_EALIGN;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   const float rsqrt_bc2 = (float)(1.0 / sqrt(bc2));
@@ -618,6 +627,7 @@ static int adamw_dev_check(const float* p, const float* g, const float* m, const
   if (!p || !g || !m || !v || !hyper) return PM_EINVAL;
   if (n <= 0 || (n & 3)) return PM_ESHAPE;
   if (shadow && shadow_dtype != PM_BF16 && shadow_dtype != PM_F16 && shadow_dtype != PM_F32) return PM_EINVAL;
+  if (!adamw_aligned(p, g, m, v, shadow, shadow_dtype)) return PM_EALIGN;
   return PM_OK;
 }
 

@@ -70,3 +70,32 @@ def test_segments_refusals(lib):
     assert _call(lib, [], n_segs=0) == _lib.PM_ESHAPE                          # zero segments
     assert _call(lib, [_segment()], n_groups=0) == _lib.PM_ESHAPE
     assert _call(lib, [_segment()], max_blocks=-1) == _lib.PM_ESHAPE
+
+
+def test_alignment_refusals(lib):
+    """p, g, m, v and an f32 shadow are moved as 16-byte vectors, a 16-bit shadow as 8-byte ones: anything else is PM_EALIGN, from
+    pm_adamw_segments (any segment), pm_adamw_dev and pm_adamw alike -- after the NULL / shape / type refusals, before any launch."""
+    for field, base in (("p", 0x1000), ("g", 0x2000), ("m", 0x3000), ("v", 0x4000)):
+        for off in (4, 8, 12):
+            assert _call(lib, [_segment(), _segment(**{field: base + off})]) == _lib.PM_EALIGN, (field, off)
+    for dt in (_lib.PM_BF16, _lib.PM_F16):
+        for off in (2, 4, 6):
+            assert _call(lib, [_segment(shadow=0x5000 + off, shadow_dtype=dt)]) == _lib.PM_EALIGN, (dt, off)
+    for off in (4, 8, 12):
+        assert _call(lib, [_segment(shadow=0x5000 + off, shadow_dtype=_lib.PM_F32)]) == _lib.PM_EALIGN, off
+    # the earlier refusals keep their status on a misaligned segment
+    assert _call(lib, [_segment(p=0x1004, n=1030)]) == _lib.PM_ESHAPE
+    assert _call(lib, [_segment(p=0x1004, shadow_dtype=7)]) == _lib.PM_EINVAL
+    assert _call(lib, [_segment(p=0x1004, g=None)]) == _lib.PM_EINVAL
+    # pm_adamw_dev and pm_adamw (made-up addresses: every call here returns before a launch)
+    well = dict(p=0x1000, g=0x2000, m=0x3000, v=0x4000, s=0x5000, dt=_lib.PM_BF16)
+    args = lambda o: [{**well, **o}[k] for k in ("p", "g", "m", "v", "s", "dt")]
+    dev = lambda **o: lib.pm_adamw_dev(*args(o), 1028, 0x6000, None)
+    host = lambda **o: lib.pm_adamw(*args(o), 1028, 1e-3, 0.9, 0.95, 1e-8, 0.05, 1, 1.0, None)
+    for call in (dev, host):
+        for k, base in (("p", 0x1000), ("g", 0x2000), ("m", 0x3000), ("v", 0x4000)):
+            assert call(**{k: base + 8}) == _lib.PM_EALIGN, k
+        assert call(s=0x5004) == _lib.PM_EALIGN
+        assert call(s=0x5008, dt=_lib.PM_F32) == _lib.PM_EALIGN
+        assert call(p=0x1008, s=0x5000, dt=7) == _lib.PM_EINVAL
+    assert host(p=None) == _lib.PM_EINVAL
