@@ -929,6 +929,50 @@ int pm_drop_path_scale_cast(const float* dy, const float* scale, void* dy_act, i
                             void* workspace, size_t ws_bytes, void* stream);
 int pm_drop_path_scales(const float* noise, const float* rates, float* out, int depth, int B, void* stream);
 
+/* ---- timm's RandAugment and random erasing of the MAE fine-tune transform (pm_timm_aug.hip; mae/util/datasets.py:37-47:
+ * create_transform(auto_augment='rand-m9-mstd0.5-inc1', interpolation='bicubic', re_prob=0.25, re_mode='pixel')) ----
+ * One LAYER of the policy = one op per sample on u8 [B][H][W][3] frames, src != dst.  ops points at the layer's first record,
+ * sample b reads ops[b * stride] (a [B][n] plan is uploaded once: layer l is ops + l, stride n).  Every op restates the Pillow
+ * routine timm calls, byte for byte (tests/randaug_ref.py pins them to Pillow 12.2):
+ *   op  0 identity (a layer the op's probability skipped; posterize with 8 bits): copy
+ *       1 AutoContrast   ImageOps.autocontrast, cutoff 0        \  need the three 256-bin histograms of the sample
+ *       2 Equalize       ImageOps.equalize                      /
+ *       3 Invert   4 Posterize(iarg bits, 0..7)   5 Solarize(iarg threshold)   6 SolarizeAdd(iarg, threshold 128): point tables
+ *       7 Color   8 Contrast   9 Brightness   10 Sharpness: ImageEnhance, Image.blend(degenerate, image, farg) in C float, clipping
+ *         when farg is outside [0, 1]; Contrast needs the sample's luminance sum; Sharpness blends against ImageFilter.SMOOTH
+ *      11 Affine: Image.transform(size, AFFINE, a, BICUBIC, fillcolor): source point (a0 (x + .5) + a1 (y + .5) + a2, a3 .. a5) in
+ *         double, Geometry.c bicubic_filter32RGB; where it lies outside the frame the pixel is (fill_r, fill_g, fill_b).
+ *         ShearX / ShearY / TranslateX / TranslateY / Rotate all arrive as their matrix (Image.rotate's is built by the caller)
+ *      12 Transpose: iarg 2 = ROTATE_180, 3 = ROTATE_90, 4 = ROTATE_270 (H == W), Image.rotate's early returns
+ *   pm_randaug_stats: one workgroup per sample whose op is 1, 2 or 8 writes stats[b] (pm_randaug_workspace(B) bytes in all, 8-byte
+ *     aligned: per sample 768 u32 bins + the u64 luminance sum); the caller skips the launch when no sample needs it.  Integer
+ *     atomics in LDS only.
+ *   pm_randaug_apply: hflip (u8 [B], optional; the first layer only) mirrors the SOURCE frame before the op -- timm flips before
+ *     the policy.  stats may be NULL when no sample's op is 1, 2 or 8 (the caller knows its plan; a sample whose op needs
+ *     statistics that were not given is copied).  Records are device memory and are trusted as the other tables are; reads stay inside frame b and writes inside
+ *     dst whatever they hold (an unknown op copies).
+ * pm_random_erase_f32: in place on the normalised f32 [B][C][H][W].  boxes i32 [B][max_count][4] = (top, left, h, w); h <= 0 or
+ *   w <= 0: no box; a box that leaves the frame is skipped.  mode 0: zeros; 1: one normal per channel and box; 2: one per element.
+ *   The normal of element e (mode 2: e = (c h + y) w + x inside the box; mode 1: e = c) of box k of sample b is Box-Muller over
+ *   words of Philox4x32-10(counter = (e / 4, b max_count + k, counter lo, counter hi), key = seed lo, hi): words (0, 1) serve
+ *   e % 4 = 0 (cos) and 1 (sin), words (2, 3) serve 2 and 3; u1 = ((w >> 8) + 1) 2^-24, u2 = (w' >> 8) 2^-24, z = sqrt(-2 ln u1)
+ *   cos / sin(2 pi u2) in f32.  Where boxes of one sample overlap the later box holds, as in timm's loop.  Outside the boxes no
+ *   byte is written.  mode 3 writes the uniforms themselves where mode 2 writes a normal (u1 for an even e, u2 for an odd one:
+ *   exact 24-bit values), so that a test can hold the words to a host Philox with ==. */
+typedef struct pm_randaug_op {
+  int op, iarg;
+  float farg;
+  int reserved;
+  double a[6];
+} pm_randaug_op;
+int pm_randaug_workspace(int B, size_t* bytes);
+int pm_randaug_stats(const unsigned char* src, const pm_randaug_op* ops, int stride, void* stats, size_t stats_bytes, int B, int H,
+                     int W, void* stream);
+int pm_randaug_apply(const unsigned char* src, unsigned char* dst, const pm_randaug_op* ops, int stride, const unsigned char* hflip,
+                     const void* stats, size_t stats_bytes, int B, int H, int W, int fill_r, int fill_g, int fill_b, void* stream);
+int pm_random_erase_f32(float* x, const int* boxes, int max_count, int mode, unsigned long long seed, unsigned long long counter,
+                        int B, int C, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

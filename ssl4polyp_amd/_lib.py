@@ -118,6 +118,10 @@ SIGNATURES = {
     "pm_drop_path_workspace": [I, I, P],
     "pm_drop_path_scale_cast": [P, P, P, I, P, I, I, I, P, ctypes.c_size_t, P],
     "pm_drop_path_scales": [P, P, P, I, I, P],
+    "pm_randaug_workspace": [I, P],
+    "pm_randaug_stats": [P, P, I, P, ctypes.c_size_t, I, I, I, P],
+    "pm_randaug_apply": [P, P, P, I, P, P, ctypes.c_size_t, I, I, I, I, I, I, P],
+    "pm_random_erase_f32": [P, P, I, I, ctypes.c_ulonglong, ctypes.c_ulonglong, I, I, I, I, P],
 }
 
 ABI_VERSION = 16  # pm_abi_version() of the library these signatures describe

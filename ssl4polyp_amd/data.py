@@ -452,6 +452,34 @@ class DeviceAugmenter:
         flips = self._scratch.upload("mae_flips", torch.as_tensor(hflip).to(torch.uint8).numpy())
         return preprocess_u8(x, flips, self.mean, self.std, out=out)
 
+    def timm_tail(self, x: torch.Tensor, train_aug, plan=None, boxes=None, hflip=None, generator: Optional[torch.Generator] = None,
+                  rng=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """What timm's create_transform(is_training=True, auto_augment=..., re_prob=...) does after its crop, to an already cropped
+        uint8 batch [B, size, size, 3]: RandomHorizontalFlip -> RandAugment -> ToTensor -> Normalize -> RandomErasing, f32
+        [B, 3, size, size].  train_aug: a timm_aug.TrainAugment (either stage may be None).  The flips come from `generator` exactly
+        as mae_tail draws them; the plan and the boxes, unless given, from `rng` (default: train_aug.rng) in that order; the erasing
+        normals are keyed by train_aug.next_key().  With a RandAugment the flip is part of its first layer (the ops see timm's
+        flipped frame); without one this is mae_tail followed by the erasing."""
+        B = len(x)
+        if hflip is None:
+            hflip = (torch.rand(B, generator=generator) < 0.5)
+        hflip = torch.as_tensor(hflip).to(torch.uint8).numpy()
+        rng = train_aug.rng if rng is None else rng
+        ra, re = train_aug.rand_augment, train_aug.random_erasing
+        if ra is not None:
+            _check_u8_frames(x, "DeviceAugmenter.timm_tail")
+            if plan is None:
+                plan = ra.draw(B, rng, (x.shape[2], x.shape[1]))
+            x = ra.apply(x, plan, hflip=hflip, scratch=self._scratch)
+            res = preprocess_u8(x, None, self.mean, self.std, out=out)
+        else:
+            res = preprocess_u8(x, self._scratch.upload("mae_flips", hflip), self.mean, self.std, out=out)
+        if re is not None:
+            if boxes is None:
+                boxes = re.draw(B, tuple(res.shape[1:]), rng)
+            re.apply(res, boxes, train_aug.next_key(), scratch=self._scratch)
+        return res
+
     def __call__(self, frames, params: Optional[dict] = None, generator: Optional[torch.Generator] = None,
                  to_f32: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """frames uint8 [B, H, W, 3] or a RaggedFrames, on the device.  Returns f32 [B, 3, size, size] (normalised) or, with

@@ -5,7 +5,8 @@ Training frames: folder.folder_loader on DATA/train, the workers only decode; on
 (data.draw_linprobe_boxes -- not torchvision's sampler) through DeviceAugmenter.random_resized_crop(bicubic), then flip / ToTensor /
 Normalize (mae_tail).  Validation frames: the workers do Resize(256, bicubic) + CenterCrop(224) with Pillow, as the reference's workers
 do, and the device normalises (preprocess_u8).  The crops, flips and the sampler's order of epoch e depend on (seed, e) alone, so a
-resumed run continues as the uninterrupted one.
+resumed run continues as the uninterrupted one.  run_epochs(..., train_aug=timm_aug.TrainAugment(...)) puts timm's RandAugment and
+random erasing around the normalise (DeviceAugmenter.timm_tail), drawn from (seed, e) as well; without it nothing changes.
 
 Two flags move the remaining host work to the device without changing a byte of any batch; both default to `host`:
   --decode device          the train workers only read and pack the files (folder_loader(decode="device")); the step decodes the
@@ -151,7 +152,7 @@ def resolve_lr(args) -> None:
 
 
 def run_epochs(args, model, opt, device, train_epoch, *, crop_size: int, train_loader, val_loader, prepare_given: bool, scaler=None,
-               log_extra=None, log_encoding=None):
+               log_extra=None, log_encoding=None, train_aug=None):
     """Resume, build the loaders the caller did not pass, then --eval or the epoch loop -> (model, opt, history): history holds one
     {"epoch", "train", "test"} record per epoch run (--eval: one "test").
 
@@ -159,7 +160,10 @@ def run_epochs(args, model, opt, device, train_epoch, *, crop_size: int, train_l
     prepare_given: whether prepare_train / prepare_val (host batch -> device batch) are applied to loaders the CALLER passed as well
       (the probe), or only to the folder loaders built here, a passed loader yielding device batches as they are (the fine-tune).
     scaler: the fp16 loss scaler restored from / saved into the checkpoints.  log_extra: further keys of the log.txt line;
-    log_encoding: the encoding log.txt is opened with."""
+    log_encoding: the encoding log.txt is opened with.
+    train_aug: a timm_aug.TrainAugment -- prepare_train then runs DeviceAugmenter.timm_tail (flip -> RandAugment -> normalise ->
+      random erasing) instead of mae_tail, and every epoch reseeds its host generator and erasing key from (seed, epoch).  None:
+      every draw, launch and bit is the recipe's without it."""
     from .data import DeviceAugmenter, DeviceJpegDecoder, draw_linprobe_boxes
     from .folder import folder_loader
     from .jpeg import JpegBatch
@@ -177,7 +181,9 @@ def run_epochs(args, model, opt, device, train_epoch, *, crop_size: int, train_l
             frames = decoder(frames)
         hw = frames.sizes
         boxes = draw_linprobe_boxes(len(frames), hw[:, 0], hw[:, 1], gen)
-        return aug.mae_tail(aug.random_resized_crop(frames, boxes=boxes), generator=gen), labels.to(device, non_blocking=True)
+        crop = aug.random_resized_crop(frames, boxes=boxes)
+        images = aug.mae_tail(crop, generator=gen) if train_aug is None else aug.timm_tail(crop, train_aug, generator=gen)
+        return images, labels.to(device, non_blocking=True)
 
     prepare_val = _normalise_on(device)
     if val_loader is None:
@@ -200,6 +206,8 @@ def run_epochs(args, model, opt, device, train_epoch, *, crop_size: int, train_l
     max_accuracy = 0.0
     for epoch in range(args.start_epoch, args.epochs):
         gen.manual_seed(args.seed + epoch)
+        if train_aug is not None:
+            train_aug.reseed(args.seed, epoch)
         if sampler is not None:
             sampler.set_epoch(args.seed + epoch)
         train = train_epoch(epoch, train_loader, prepare_train)

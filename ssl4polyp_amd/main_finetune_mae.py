@@ -18,7 +18,11 @@ NOT BUILT -- accepted as flags at their "off" value only, refused otherwise:
   --drop_path > 0      the MODEL has stochastic depth (models_vit.VisionTransformer(drop_path_rate=...), csrc/pm_droppath.hip); this
                        command line does not pass the flag on yet -- the remaining step.  THE DEFAULT HERE IS 0.0; THE REFERENCE'S
                        IS 0.1: results of the reference's default recipe are not reproduced until the flag is switched over.
-  --aa, --reprob, --color_jitter   timm's create_transform (RandAugment, random erasing, colour jitter).
+  --aa, --reprob       RandAugment and random erasing ARE built (timm_aug.py, csrc/pm_timm_aug.hip) and reach the recipe through
+                       Python: run(args, train_aug=TrainAugment(RandAugment("rand-m9-mstd0.5-inc1", IMAGENET_MEAN),
+                       RandomErasing(0.25))).  The two flags still refuse anything but "off": switching --drop_path, --aa and
+                       --reprob to the reference's defaults (0.1, rand-m9-mstd0.5-inc1, 0.25) is one later change.
+  --color_jitter       timm's create_transform colour jitter (unused when --aa is given, as in timm).
   --dist_eval and more than one process;  --input_size other than the model's (position-embedding interpolation)."""
 from __future__ import annotations
 
@@ -46,9 +50,11 @@ def get_args_parser():
     p.add_argument("--clip_grad", type=float, default=None)
     p.add_argument("--layer_decay", type=float, default=0.75)
     p.add_argument("--color_jitter", type=float, default=None, help="NOT BUILT: only None is accepted")
-    p.add_argument("--aa", type=str, default=None, help="NOT BUILT: only None is accepted (the reference's default is rand-m9-mstd0.5-inc1)")
+    p.add_argument("--aa", type=str, default=None, help="only None is accepted on the command line (the reference's default is rand-m9-mstd0.5-inc1); RandAugment runs "
+                                                           "through run(args, train_aug=...)")
     p.add_argument("--smoothing", type=float, default=0.1)
-    p.add_argument("--reprob", type=float, default=0.0, help="NOT BUILT: only 0 is accepted (the reference's default is 0.25)")
+    p.add_argument("--reprob", type=float, default=0.0, help="only 0 is accepted on the command line (the reference's default is 0.25); random erasing runs through "
+                                                             "run(args, train_aug=...)")
     p.add_argument("--remode", type=str, default="pixel")
     p.add_argument("--recount", type=int, default=1)
     p.add_argument("--resplit", action="store_true", default=False)
@@ -69,9 +75,11 @@ def check_supported(args) -> None:
         gaps.append(f"--drop_path {args.drop_path}: stochastic depth is not built (it needs a per-row scale in the residual GEMM "
                     "epilogues); only 0.0 runs -- the reference's default is 0.1")
     if args.aa not in (None, "", "none"):
-        gaps.append(f"--aa {args.aa}: timm's AutoAugment / RandAugment policies are not built")
+        gaps.append(f"--aa {args.aa}: timm's AutoAugment / RandAugment policies are not wired to this flag yet (RandAugment runs "
+                    "through run(args, train_aug=timm_aug.TrainAugment(...)))")
     if float(args.reprob or 0.0) != 0.0:
-        gaps.append(f"--reprob {args.reprob}: random erasing is not built")
+        gaps.append(f"--reprob {args.reprob}: random erasing is not wired to this flag yet (it runs through run(args, "
+                    "train_aug=timm_aug.TrainAugment(...)))")
     if args.color_jitter is not None:
         gaps.append(f"--color_jitter {args.color_jitter}: timm's create_transform colour jitter is not built")
     if args.dist_eval or int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -103,8 +111,10 @@ def mix_rng(seed: int, epoch: int) -> np.random.RandomState:
     return np.random.RandomState([int(seed) & 0x7FFFFFFF, int(epoch)])
 
 
-def run(args, train_loader=None, val_loader=None):
-    """-> (model, optimizer, history): history holds one {"epoch", "train", "test"} record per epoch run (--eval: one "test")."""
+def run(args, train_loader=None, val_loader=None, train_aug=None):
+    """-> (model, optimizer, history): history holds one {"epoch", "train", "test"} record per epoch run (--eval: one "test").
+    train_aug: a timm_aug.TrainAugment(RandAugment(...), RandomErasing(...)) for the training frames of the folder input (the
+    Python way to the stages the --aa / --reprob flags still refuse); None: crop, flip, normalise."""
     check_supported(args)
     device = mae_recipe.start(args)
     mixup_fn = None
@@ -130,7 +140,7 @@ def run(args, train_loader=None, val_loader=None):
     # a loader passed in yields device batches as they are; log.txt as main_finetune.py:366-375 writes it
     return mae_recipe.run_epochs(args, model, opt, device, train_epoch, crop_size=args.input_size, train_loader=train_loader,
                                  val_loader=val_loader, prepare_given=False, scaler=scaler, log_extra={"n_parameters": n_parameters},
-                                 log_encoding="utf-8")
+                                 log_encoding="utf-8", train_aug=train_aug)
 
 
 if __name__ == "__main__":
