@@ -325,7 +325,8 @@ int pm_aug_resize_center_crop_ragged_u8(const unsigned char* src, const long lon
 /* ColorJitter: per sample, ops in `order` (0 brightness, 1 contrast, 2 saturation, 3 hue; -1 = none): ImageEnhance blends (float32,
  * truncating / clipping as Blend.c), contrast against int(mean luminance + 0.5) of the image as it stands before that op, hue as
  * an HSV round trip with H += hue_shift (uint8 wrap-around; hue_shift = uint8(hue_factor * 255)).  lsum: u64 [B] scratch.
- * Two launches (exact integer luminance sum, then the chain); src and dst may be the same buffer only if order has no contrast. */
+ * Two launches (exact integer luminance sum, then the chain); src and dst may be the same buffer only if order has no contrast.
+ * B <= 65535 (the sample is a grid dimension): a larger batch is refused with PM_ESHAPE before anything is enqueued. */
 typedef struct pm_aug_jitter {
   int order[4];
   float brightness, contrast, saturation;
@@ -362,6 +363,7 @@ int pm_aug_geometry_u8(const unsigned char* src, const pm_aug_geom* geom, void* 
  *            with r = _gaussian_blur_radius(sigma, passes) in float32 (built by the caller: data.py pil_box_blur_params);
  *            radius < 0: the sample passes through unchanged.  tmp: u8 [B][H][W][3] scratch; src may equal dst, tmp must not.
  *   "occ*":  ImageDraw.rectangle([x0, y0, x1, y1], fill=0), corners inclusive, clipped to the frame; x1 < x0: nothing.  In place.
+ *            B <= 65535 (the sample is a grid dimension), else PM_ESHAPE.
  *   "bc*":   pm_aug_color_jitter_u8 with order {0, 1, -1, -1}.
  *   "jpeg*": img.save(format="JPEG", quality=q, optimize=False, subsampling=0) and back (transforms.py:78-85) WITHOUT a bitstream:
  *            entropy coding is lossless, so the round trip is libjpeg's integer pipeline -- RGB -> YCbCr (jccolor.c), 4:4:4, islow

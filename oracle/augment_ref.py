@@ -89,29 +89,40 @@ def resize_bilinear(frames: np.ndarray, out_h: int, out_w: int) -> np.ndarray:
     return resize(frames, out_h, out_w, "bilinear")
 
 
-def resize(frames: np.ndarray, out_h: int, out_w: int, filt: str = "bilinear") -> np.ndarray:
-    """uint8 [B, H, W, C] -> uint8 [B, out_h, out_w, C]: horizontal pass, then vertical pass, each rounded to uint8
-    (ImagingResampleInner: a pass is skipped when the size does not change)."""
+def vertical_pass_first(H: int, W: int, out_h: int) -> bool:
+    """Image.resize's one exception to "horizontal pass first": a frame more than 100 times as tall as wide whose height shrinks is
+    resampled vertically first (two calls of the C routine; found by bisection against Pillow 12.2 and pinned at both sides of the
+    edge by tests/test_augment_edges_cpu.py).  Each pass rounds to uint8, so the order changes bytes -- by one grey level."""
+    return H > 100 * W and out_h < H
+
+
+def resize(frames: np.ndarray, out_h: int, out_w: int, filt: str = "bilinear", order: str | None = None) -> np.ndarray:
+    """uint8 [B, H, W, C] -> uint8 [B, out_h, out_w, C]: two passes, each rounded to uint8 (ImagingResampleInner: a pass is skipped
+    when the size does not change).  order "h": horizontal pass first, "v": vertical first, None: the order Image.resize takes
+    (vertical_pass_first).  The DEVICE path always runs the horizontal pass first (DESIGN.md says where that leaves Pillow)."""
     x = frames
     B, H, W, C = x.shape
-    if out_w != W:
-        bounds, ik, _ = _resample_coeffs(W, out_w, filt)
-        out = np.empty((B, H, out_w, C), dtype=np.uint8)
-        xi = x.astype(np.int64)
-        for xx in range(out_w):
-            xmin, n = bounds[xx]
-            ss = (1 << (PRECISION_BITS - 1)) + np.tensordot(xi[:, :, xmin:xmin + n, :], ik[xx, :n], axes=([2], [0]))
-            out[:, :, xx, :] = _clip8(ss)
-        x = out
-    if out_h != H:
-        bounds, ik, _ = _resample_coeffs(H, out_h, filt)
-        out = np.empty((B, out_h, x.shape[2], C), dtype=np.uint8)
-        xi = x.astype(np.int64)
-        for yy in range(out_h):
-            ymin, n = bounds[yy]
-            ss = (1 << (PRECISION_BITS - 1)) + np.tensordot(xi[:, ymin:ymin + n, :, :], ik[yy, :n], axes=([1], [0]))
-            out[:, yy, :, :] = _clip8(ss)
-        x = out
+    if order is None:
+        order = "v" if vertical_pass_first(H, W, out_h) else "h"
+    for axis in ("hv" if order == "h" else "vh"):
+        if axis == "h" and out_w != W:
+            bounds, ik, _ = _resample_coeffs(W, out_w, filt)
+            out = np.empty((B, x.shape[1], out_w, C), dtype=np.uint8)
+            xi = x.astype(np.int64)
+            for xx in range(out_w):
+                xmin, n = bounds[xx]
+                ss = (1 << (PRECISION_BITS - 1)) + np.tensordot(xi[:, :, xmin:xmin + n, :], ik[xx, :n], axes=([2], [0]))
+                out[:, :, xx, :] = _clip8(ss)
+            x = out
+        if axis == "v" and out_h != H:
+            bounds, ik, _ = _resample_coeffs(H, out_h, filt)
+            out = np.empty((B, out_h, x.shape[2], C), dtype=np.uint8)
+            xi = x.astype(np.int64)
+            for yy in range(out_h):
+                ymin, n = bounds[yy]
+                ss = (1 << (PRECISION_BITS - 1)) + np.tensordot(xi[:, ymin:ymin + n, :, :], ik[yy, :n], axes=([1], [0]))
+                out[:, yy, :, :] = _clip8(ss)
+            x = out
     return x
 
 

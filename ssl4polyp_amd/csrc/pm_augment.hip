@@ -946,6 +946,7 @@ extern "C" int pm_aug_color_jitter_u8(const unsigned char* src, unsigned char* d
                                       unsigned long long* lsum, int B, int H, int W, void* stream) {
   if (!src || !dst || !jitter || !lsum) return PM_EINVAL;
   if (B <= 0 || H <= 0 || W <= 0) return PM_ESHAPE;
+  if (B > 65535) return PM_ESHAPE;  // (the sample is blockIdx.y)
   hipStream_t s = pm_stream(stream);
   if (hipMemsetAsync(lsum, 0, (size_t)B * sizeof(unsigned long long), s) != hipSuccess) return PM_ELAUNCH;
   const int HW = H * W;
@@ -1007,6 +1008,7 @@ extern "C" int pm_aug_pil_gaussian_blur_u8(const unsigned char* src, unsigned ch
 extern "C" int pm_aug_occlude_u8(unsigned char* img, const int* rects, int B, int H, int W, void* stream) {
   if (!img || !rects) return PM_EINVAL;
   if (B <= 0 || H <= 0 || W <= 0) return PM_ESHAPE;
+  if (B > 65535) return PM_ESHAPE;  // (the sample is blockIdx.y)
   hipLaunchKernelGGL(occlude_kernel, dim3(64, B), dim3(256), 0, pm_stream(stream), img, rects, B, H, W);
   return pm_check_launch();
 }
